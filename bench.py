@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the SVOL hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: launched by the driver as  python -m torch.distributed.run --nnodes=1 --nproc-per-node N
      --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...; one rank per GPU over RCCL)
 
@@ -18,7 +18,10 @@ workload: BASELINE.json configs[1]  — B=8 videos per GPU, T=32 frames, P=196 t
           replays the step as one hipGraph instead.  --workload selects the other measured configurations (cfg4: ViT
           extractor online, cfg5: long video, encdec: enc/dec Transformer head, resnet: ResNet extractors online — frozen, or with
           --train-backbone in training mode and in the optimiser as the reference's train.py has them).
-Prints ONE JSON line on rank 0.
+The timed region is exactly --steps steps (--blocks N: N such blocks back to back, the line reports the median one);
+`ms_per_step` is the milliseconds one timed step took.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below); every step of such a run starts from the seeded initial parameters, so that the dump is the same
+from run to run.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -63,6 +66,68 @@ def _host_cores():
     return max(1, n), how
 
 
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: a larger array is written as this many entries at fixed, seeded positions
+
+
+def _dump_sample(flat):
+    """``flat`` (1-D) itself, or DUMP_SAMPLE of its entries at positions drawn once from a fixed seed (sorted)."""
+    import numpy as np
+    import torch
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat
+    idx = np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(path, last, params):
+    """--dump-outputs: what the LAST timed step computed, as ``path/<name>.npy`` (float32, float64 where the tensor is):
+      loss.npy                    the step's total loss (what the step returns)
+      losses.<term>.npy           every term of the criterion's loss dict
+      out.<key>[.<i>.<key>].npy   the model's forward outputs (pred_logits, pred_boxes, aux_outputs; eager steps — a replayed
+                                  graph hands back the losses only)
+      grad_sample.npy             param.grad as the step left it, all parameters of the optimiser flattened in its order
+                                  (the all-reduced SUM when N > 1 and times the loss scale, as the buckets hold it)
+    Arrays of more than DUMP_SAMPLE entries keep DUMP_SAMPLE entries at fixed seeded positions (_dump_sample), so the
+    whole dump stays a few MB.  Inputs, dropout seeds and — in a dumping run — the parameters every step starts from are
+    fixed: the same arguments give the same forward bit for bit and gradients equal to rounding (the backward's fp32
+    atomics), so two builds can be compared array by array.  The updated parameters are not written: AdamW moves an entry
+    whose gradient is rounding noise by +-lr with that noise's sign, so they differ by more than rounding from run to run.
+    Returns {name: shape}."""
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def add(name, v):
+        if isinstance(v, torch.Tensor):
+            t = v.detach()
+            t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+            if t.numel() > DUMP_SAMPLE:
+                name, t = name + '.sample', _dump_sample(t.reshape(-1))
+            arrays[name] = t.cpu().numpy()
+        elif isinstance(v, dict):
+            for k in sorted(v):
+                if not str(k).startswith('_'):   # (private keys: _svol_stacked repeats pred_* and aux_outputs)
+                    add('%s.%s' % (name, k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                add('%s.%d' % (name, i), x)
+
+    add('loss', last['loss'])
+    add('losses', last['losses'])
+    if 'out' in last:
+        add('out', last['out'])
+    with torch.no_grad():
+        grads = [p.grad.reshape(-1).float() if p.grad is not None else torch.zeros(p.numel(), device=p.device) for p in params]
+        arrays['grad_sample'] = _dump_sample(torch.cat(grads)).cpu().numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= 64 << 20, f'--dump-outputs: {total} bytes'
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(x))
+    return {name: list(x.shape) for name, x in arrays.items()}
+
+
 def cpu_baseline(seconds_budget=40.0):
     """Reference CPU path timed beside the GPU number: the oracle (CPU restatement proven equal to the
     reference by the golden vectors) on a BOUNDED sample of the same workload — one of the 8 videos of
@@ -101,10 +166,13 @@ def cpu_baseline(seconds_budget=40.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps')
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--blocks', type=int, default=5,
+    ap.add_argument('--blocks', type=int, default=1,
                     help='timed blocks of exactly --steps steps run back to back; the line reports the median block (ms_per_step_blocks lists all)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs); '
+                         'every step of the run then starts from the seeded initial parameters (a 4-byte-per-parameter copy per step)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp16', 'fp32'])
     ap.add_argument('--loss-scale', type=float, default=None,
                     help='static loss scale (default: 1024 with --dtype fp16 — fp16 gradients of ~1e-6 underflow otherwise; the reference '
@@ -131,6 +199,8 @@ def main():
                          '(svanet_variants, append_to_seq) instead of the cross-modal transformer; resnet = the reference\'s default backbone '
                          '(frozen ResNet-34 on the frames -> 49 tokens each, ResNet-18 on the sketch) online in front of the head')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if a.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, one process per GPU, through
@@ -282,6 +352,17 @@ def main():
 
     fence = parallel.StepFence(a.max_inflight) if a.max_inflight > 0 else None
 
+    last = {}   # --dump-outputs: the last step's results (references only, read after the timed region)
+    # --dump-outputs: every step starts from the seeded initial parameters.  The backward's fp32 atomics make gradients equal
+    # only to rounding from run to run, and AdamW turns a rounding-noise gradient into a +-lr step: over a few steps the weights,
+    # and with them every output, drift apart by far more than rounding.  Copying the parameters back (the optimiser's flat
+    # buffers: the model's weights are views into them) makes each step a function of the arguments alone; the moments and the
+    # step count still advance as in training.
+    pristine = None
+    if a.dump_outputs:
+        live = [st['p'] for st in opt.flat] if isinstance(opt, parallel.FlatAdamW) else [p.data for p in params]
+        pristine = [(t, t.clone()) for t in live]
+
     turn_sleep_cycles = int(float(os.environ.get('SVOL_BENCH_TURN_SLEEP_US', '0')) * 2309.0)   # (torch.cuda._sleep spins on the shader clock: 1e6 cycles = 433 us measured, tools/lab_power_bound.sh)
 
     def step():
@@ -297,6 +378,8 @@ def main():
         (scaler.scale(loss) if scaler is not None else (loss * loss_scale if loss_scale != 1.0 else loss)).backward()
         reducer.finish(mean=use_graph)   # the 1 / world of the gradient mean rides FlatAdamW's update kernel
         opt.step()
+        if a.dump_outputs:
+            last.update(loss=loss, losses=ld, out=out)
         return loss
 
     if use_graph:
@@ -307,11 +390,18 @@ def main():
         eager_step = step
 
         def step():  # noqa: F811
-            return gstep(inp, tg)[0]
+            loss_, losses_ = gstep(inp, tg)
+            if a.dump_outputs:
+                last.clear()
+                last.update(loss=loss_, losses=losses_)
+            return loss_
 
     raw_step = step
 
     def step():  # noqa: F811
+        if pristine is not None:
+            for t, t0 in pristine:
+                t.copy_(t0)
         out_ = raw_step()
         if fence is not None:
             fence.tick()
@@ -357,9 +447,12 @@ def main():
             el = float(t.item())
         return el, issued, host
 
-    # the timed region of the contract, --blocks times back to back (default 5): one 20-step block is 0.35 s, and box-to-box /
-    # run-to-run spread (+-3 %) is larger than a round's gains — the line reports the MEDIAN block and lists all of them
+    # the timed region of the contract: exactly --steps steps (--blocks N: N blocks back to back — one 20-step block is 0.35 s, and
+    # box-to-box / run-to-run spread (+-3 %) is larger than a round's gains — the line then reports the MEDIAN block and lists all)
     timed = [timed_block() for _ in range(max(1, a.blocks))]
+    dumped = None
+    if a.dump_outputs and rank == 0:   # before any further step: the clock block and the issue-time steps below train on
+        dumped = dump_outputs(a.dump_outputs, last, params)
     order = sorted(range(len(timed)), key=lambda i: timed[i][0])
     elapsed, t_issued, host_ms = timed[order[len(order) // 2]]
     if trace:
@@ -607,6 +700,8 @@ def main():
             res['host_cores_per_rank'] = cores_rank
         if roof:
             res['roofline'] = roof
+        if dumped is not None:
+            res['dumped_outputs'] = {'dir': a.dump_outputs, 'arrays': dumped}
         if world == 1 and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()
         print(json.dumps(res), flush=True)
