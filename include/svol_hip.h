@@ -491,6 +491,19 @@ int svol_attn_weights_mean(const void* q, int64_t ldq, const void* k, int64_t ld
  * layouts as svol_attn_fwd (rows = tokens, head h in columns [h*dh, (h+1)*dh)). */
 int svol_attn_small_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                         int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* ---- the same attention in TRAINING mode: the autograd of HF ViTSelfAttention (softmax(q k^T / sqrt(dh)) v, no dropout) that the
+ * reference's trainable ViT backbone runs (lib/modeling/backbone.py:30,48; preprocess/sketch_vit_finetune.py:43-69,103-143), restated
+ * in oracle/vit_oracle.py.  Limits as svol_attn_small_fwd (L <= 256, dh in {32, 64}, n_seq <= 65535, bf16; SVOL_E_UNSUPPORTED outside).
+ * svol_attn_small_fwd_lse: o bit-identical to svol_attn_small_fwd, plus lse2 [n_seq, H, L] fp32 = log2 sum_j exp(s_ij * scale)
+ *   (the log2 domain of svol_attn_fwd: P = exp2(s * scale * log2e - lse2)). */
+int svol_attn_small_fwd_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                            float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* dq, dk, dv (bf16, each with its own leading dimension: column slices of one packed [n_seq*L, 3*H*dh] buffer work) of the
+ * forward above from q, k, v, o, dout (layouts as the forward, 16-byte aligned, leading dimensions multiples of 8) and its lse2.
+ * One workgroup per (sequence, head) owns all of that head's gradients: no atomics, bit-reproducible; rows >= L are not written. */
+int svol_attn_small_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                        const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                        int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
 
 
 /* ---- composite block programs (round 3: the host off the critical path) ---------------------------------------------

@@ -15,6 +15,8 @@ reference command line parses unchanged.  Differences, all additive:
 * ``--train_backbone {0,1}`` (``--backbone resnet``): default = the reference's behaviour (its training step optimises the
   backbone, train.py:72), with the reference's dead ``--freeze_backbone`` honoured as the opt-out; ``--sync_bn`` is honoured
   by the trainable extractors (global-batch BatchNorm statistics across ranks, train.py:65-68).
+  With ``--backbone vit`` only an explicit ``--train_backbone 1`` trains the ViT extractors (the reference's ViT path cannot
+  run as shipped); ``--finetune_layers K`` restricts that to the last K layers and the final LayerNorm.
 """
 from __future__ import annotations
 
@@ -119,8 +121,14 @@ _EXTRA = [
     (('--feat_dim',), dict(type=int, default=512, help='feature width of the enc/dec heads (one width for sketch and video)')),
     # --backbone resnet: the reference optimises the backbone too (train.py:72); None = "as the reference": trainable unless
     # --freeze_backbone (a flag the reference parses and never reads) is given; 0 / 1 force the frozen / trainable extractors
+    # --backbone vit: only an explicit 1 trains the ViT extractors (default frozen: the reference's ViT path cannot run as
+    # shipped, backbone.py:30, so no reference run trains it); --finetune_layers K then trains the last K layers + final norm
     (('--train_backbone',), dict(type=int, default=None, choices=[0, 1],
-                                 help='ResNet extractors in training mode and in the optimiser (default: 1 unless --freeze_backbone)')),
+                                 help='backbone extractors in training mode and in the optimiser (resnet default: 1 unless '
+                                      '--freeze_backbone; vit default: 0, the reference ViT path cannot run as shipped)')),
+    (('--finetune_layers',), dict(type=int, default=None,
+                                  help='with --backbone vit --train_backbone 1: train only the last K ViT layers and the final '
+                                       'LayerNorm (preprocess/sketch_vit_finetune.py); default: every parameter')),
 ]
 
 

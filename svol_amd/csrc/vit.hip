@@ -1,4 +1,5 @@
-// ViT-B/16 feature extractor pieces (Hugging Face ViTModel semantics, inference only):
+// ViT-B/16 feature extractor pieces (Hugging Face ViTModel semantics; forward, and the attention backward of the
+// trainable extractor):
 //
 //   svol_patchify        pixel_values [n,C,H,W] fp32 -> patch rows [n*P, C*p*p] (the im2col of the stride-p conv, in the
 //                        conv weight's own (c, ky, kx) order) so that the patch embedding is ONE MFMA GEMM
@@ -10,6 +11,8 @@
 //                        softmax is a plain two-pass one — no running maximum, no rescale; swapped products keep the
 //                        statistics lane-local and feed P to the second MFMA straight from the accumulators, as in
 //                        attention_bf16.hip.  Attention is 4 % of ViT-B's FLOPs; the GEMMs (gemm_bf16.hip) carry it.
+//   svol_attn_small_fwd_lse  the same forward, plus lse2 per query (template flag: the plain forward's code is untouched)
+//   svol_attn_small_bwd      its backward, one workgroup per (image, head) (see attn_small_bwd_kernel)
 #include "common.h"
 
 namespace {
@@ -65,16 +68,25 @@ struct SmallArgs {
     int64_t ldq, ldk, ldv, ldo;
     int H, L, nkb;  // nkb = ceil(L / 32) <= 8
     float scale_log2e;
+    float* lse2;    // [n_seq, H, L] log2-sum-exp of the scaled scores (LSE instantiation only)
 };
 typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
 
 // image: row-major, DH bf16 per row (DH*2 bytes = DH/8 chunks of 16 bytes), chunk index XOR-ed with the row
+// 16 bytes from global memory, or zeros (a branch, not a select between the source and a zero local: that select puts the
+// local on the scratch stack and turns every staging load into a flat load)
+__device__ __forceinline__ uint4 ld16_or_zero(const bf16_t* src, bool valid) {
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (valid) v = *reinterpret_cast<const uint4*>(src);
+    return v;
+}
+
 template <int DH> __device__ __forceinline__ int img_off(int row, int ch) {
     constexpr int CPR = DH / 8;
     return row * (DH * 2) + (((ch ^ (row >> (DH == 32 ? 2 : 0))) & (CPR - 1)) << 4);
 }
 
-template <int DH>
+template <int DH, bool LSE>
 __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
     constexpr int CPR = DH / 8, KS = DH / 16, DB = DH / 32;
     constexpr int LMAX = 256;
@@ -91,9 +103,8 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
     // stage K and V (zero rows past L)
     for (int c = tid; c < Lp * CPR; c += 256) {
         const int row = c / CPR, ch = c % CPR;
-        const uint4 z = make_uint4(0, 0, 0, 0);
-        *reinterpret_cast<uint4*>(sK + img_off<DH>(row, ch)) = row < p.L ? *reinterpret_cast<const uint4*>(K + (int64_t)row * p.ldk + ch * 8) : z;
-        *reinterpret_cast<uint4*>(sV + img_off<DH>(row, ch)) = row < p.L ? *reinterpret_cast<const uint4*>(V + (int64_t)row * p.ldv + ch * 8) : z;
+        *reinterpret_cast<uint4*>(sK + img_off<DH>(row, ch)) = ld16_or_zero(K + (int64_t)row * p.ldk + ch * 8, row < p.L);
+        *reinterpret_cast<uint4*>(sV + img_off<DH>(row, ch)) = ld16_or_zero(V + (int64_t)row * p.ldv + ch * 8, row < p.L);
     }
     __syncthreads();
     for (int qb = wave; qb < p.nkb; qb += 4) {
@@ -102,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
         uint4 qf[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            qf[ks] = qvalid ? *reinterpret_cast<const uint4*>(Q + (int64_t)qrow * p.ldq + ks * 16 + h * 8) : make_uint4(0, 0, 0, 0);
+            qf[ks] = ld16_or_zero(Q + (int64_t)qrow * p.ldq + ks * 16 + h * 8, qvalid);
         // scores of this lane's query against every key: S[kb][i] <-> key kb*32 + 8*(i/4) + 4*h + i%4
         f32x16 S[8];
 #pragma unroll
@@ -189,11 +200,241 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
                     for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(O[db][4 * g + e] * inv);
                     *reinterpret_cast<bf16x4*>(out + db * 32 + 8 * g + 4 * h) = v4;
                 }
+            // lse2 = log2 sum_j exp2(s_j * scale_log2e) = m * scale_log2e + log2(l): P = exp2(s * scale_log2e - lse2)
+            if constexpr (LSE)
+                if (h == 0) p.lse2[((int64_t)seq * p.H + hh) * p.L + qrow] = -mc + log2f(l);
         }
     }
 }
 
+// ---- short-sequence attention backward ------------------------------------------------------------------------------
+// One workgroup of 8 waves per (image, head) owns ALL of that head's dQ / dK / dV: no atomics, bit-reproducible.  Q, K, V and
+// dO sit in LDS (same XOR-swizzled images as the forward, 4 x 32 KB at L = 256, dh = 64), with lse2 and
+// delta = rowsum(dO * O) beside them.  P = exp2(s * scale_log2e - lse2) and dS = P (dP - delta) are recomputed in two phases
+// that need no barrier between them (the images are read-only after staging):
+//   key-stationary    wave w owns keys [32w, 32w + 32): X = S[q][key] = mfma(Q rows, K rows) has the key on the lane and the
+//                     queries in the registers, so dV^T += dO^T P and dK^T += Q^T dS take P / dS straight from the
+//                     accumulators (dO^T and Q^T through ds_read_tr16_b64, as V in the forward)
+//   query-stationary  wave w owns queries [32w, 32w + 32): S^T = mfma(K rows, Q rows) as in the forward (lse2 / delta lane-local),
+//                     dQ^T += K^T dS^T
+// Outputs are stored like the forward's O (lane = row, 4 consecutive columns per store); rows >= L are never written, padded
+// keys and queries get P = 0.
+struct SmallBwdArgs {
+    const bf16_t *q, *k, *v, *o, *dout;
+    const float* lse2;
+    bf16_t *dq, *dk, *dv;
+    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
+    int H, L, nkb;
+    float scale, scale_log2e;
+};
+
+template <int DH> __device__ __forceinline__ uint4 row_frag(const char* img, int row, int ch) {
+    return *reinterpret_cast<const uint4*>(img + img_off<DH>(row, ch));
+}
+
+// A operand [row = column db*32 + (lane & 31) of the image][k = image rows r0 + 8(j>>2) + 4h + (j&3)], the transposed read
+// of the forward's V fragment
+template <int DH> __device__ __forceinline__ bf16x8 tr_frag(const char* img, int r0, int db, int lane) {
+    const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, pp = i16 & 3, hb = g >> 1;
+    const int col = db * 32 + 16 * (g & 1) + 4 * pp;
+    const int r1 = r0 + 4 * hb + q4;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(img + img_off<DH>(r1, col >> 3) + (col & 7) * 2));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(img + img_off<DH>(r1 + 8, col >> 3) + (col & 7) * 2));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ bf16x8 acc_frag(const f32x16& x, int s) {
+    bf16x8 b;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = (bf16_t)x[8 * s + j];
+    return b;
+}
+
+// rows of a [*, DH] bf16 output from an accumulator with the row on the lane and the columns in the registers
+template <int DB> __device__ __forceinline__ void store_rows(bf16_t* out, const f32x16 (&acc)[DB], float mul, int h) {
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            bf16x4 v4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(acc[db][4 * g + e] * mul);
+            *reinterpret_cast<bf16x4*>(out + db * 32 + 8 * g + 4 * h) = v4;
+        }
+}
+
+template <int DH>
+__global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) {
+    constexpr int CPR = DH / 8, KS = DH / 16, DB = DH / 32;
+    constexpr int LMAX = 256, IMG = LMAX * DH * 2;
+    __shared__ __attribute__((aligned(16))) char smem[4 * IMG];
+    __shared__ __attribute__((aligned(16))) float sLse[LMAX];
+    __shared__ __attribute__((aligned(16))) float sDel[LMAX];
+    char* sQ = smem;
+    char* sK = smem + IMG;
+    char* sV = smem + 2 * IMG;
+    char* sD = smem + 3 * IMG;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int seq = blockIdx.y, hh = blockIdx.x;
+    const int64_t row0 = (int64_t)seq * p.L;
+    const bf16_t* Q = p.q + row0 * p.ldq + hh * DH;
+    const bf16_t* K = p.k + row0 * p.ldk + hh * DH;
+    const bf16_t* V = p.v + row0 * p.ldv + hh * DH;
+    const bf16_t* O = p.o + row0 * p.ldo + hh * DH;
+    const bf16_t* dO = p.dout + row0 * p.lddo + hh * DH;
+    const float* lse = p.lse2 + ((int64_t)seq * p.H + hh) * p.L;
+    const int Lp = p.nkb * 32;
+    // stage Q, K, V, dO (zero rows past L); delta of a row = the sum over its CPR chunks, which sit in CPR consecutive lanes
+    // (Lp * CPR is a multiple of 128: every wave is wholly inside or outside the loop, the shuffles see full waves)
+    for (int c = tid; c < Lp * CPR; c += 512) {
+        const int row = c / CPR, ch = c % CPR;
+        const bool valid = row < p.L;
+        const uint4 qv = ld16_or_zero(Q + (int64_t)row * p.ldq + ch * 8, valid);
+        const uint4 kv = ld16_or_zero(K + (int64_t)row * p.ldk + ch * 8, valid);
+        const uint4 vv = ld16_or_zero(V + (int64_t)row * p.ldv + ch * 8, valid);
+        const uint4 dv = ld16_or_zero(dO + (int64_t)row * p.lddo + ch * 8, valid);
+        const uint4 ov = ld16_or_zero(O + (int64_t)row * p.ldo + ch * 8, valid);
+        *reinterpret_cast<uint4*>(sQ + img_off<DH>(row, ch)) = qv;
+        *reinterpret_cast<uint4*>(sK + img_off<DH>(row, ch)) = kv;
+        *reinterpret_cast<uint4*>(sV + img_off<DH>(row, ch)) = vv;
+        *reinterpret_cast<uint4*>(sD + img_off<DH>(row, ch)) = dv;
+        const bf16x8 a = __builtin_bit_cast(bf16x8, dv), b = __builtin_bit_cast(bf16x8, ov);
+        float part = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part = __builtin_fmaf((float)a[j], (float)b[j], part);
+#pragma unroll
+        for (int off = 1; off < CPR; off <<= 1) part += __shfl_xor(part, off, 64);
+        if (ch == 0) {
+            sDel[row] = part;
+            sLse[row] = valid ? lse[row] : 0.f;
+        }
+    }
+    __syncthreads();
+    const float c2 = p.scale_log2e;
+    // ---- key-stationary: dK, dV of this wave's 32 keys
+    for (int kb = wave; kb < p.nkb; kb += 8) {
+        uint4 kf[KS], vf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            kf[ks] = row_frag<DH>(sK, kb * 32 + r, ks * 2 + h);
+            vf[ks] = row_frag<DH>(sV, kb * 32 + r, ks * 2 + h);
+        }
+        f32x16 dVt[DB], dKt[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dVt[db][i] = dKt[db][i] = 0.f;
+        for (int qb = 0; qb < p.nkb; ++qb) {
+            // X[q][key] (lane = key, register i <-> query qb*32 + 8(i>>2) + 4h + (i&3)): scores and dP = dO V^T
+            f32x16 S, dP;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) S[i] = dP[i] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const uint4 qa = row_frag<DH>(sQ, qb * 32 + r, ks * 2 + h);
+                const uint4 da = row_frag<DH>(sD, qb * 32 + r, ks * 2 + h);
+                S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa), __builtin_bit_cast(bf16x8, kf[ks]), S, 0, 0, 0);
+                dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, da), __builtin_bit_cast(bf16x8, vf[ks]), dP, 0, 0, 0);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int q0 = qb * 32 + 8 * g + 4 * h;
+                const f32x4 ls = *reinterpret_cast<const f32x4*>(sLse + q0);
+                const f32x4 dl = *reinterpret_cast<const f32x4*>(sDel + q0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float pv = q0 + e < p.L ? __builtin_amdgcn_exp2f(__builtin_fmaf(S[4 * g + e], c2, -ls[e])) : 0.f;
+                    S[4 * g + e] = pv;
+                    dP[4 * g + e] = pv * (dP[4 * g + e] - dl[e]);
+                }
+            }
+            // dV^T[d][key] += dO^T[d][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 pb = acc_frag(S, s), sb = acc_frag(dP, s);
+#pragma unroll
+                for (int db = 0; db < DB; ++db) {
+                    dVt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sD, qb * 32 + 16 * s, db, lane), pb, dVt[db], 0, 0, 0);
+                    dKt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sQ, qb * 32 + 16 * s, db, lane), sb, dKt[db], 0, 0, 0);
+                }
+            }
+        }
+        const int key = kb * 32 + r;
+        if (key < p.L) {
+            store_rows<DB>(p.dv + (row0 + key) * p.lddv + hh * DH, dVt, 1.f, h);
+            store_rows<DB>(p.dk + (row0 + key) * p.lddk + hh * DH, dKt, p.scale, h);
+        }
+    }
+    // ---- query-stationary: dQ of this wave's 32 queries
+    for (int qb = wave; qb < p.nkb; qb += 8) {
+        const int qrow = qb * 32 + r;
+        uint4 qf[KS], df[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            qf[ks] = row_frag<DH>(sQ, qrow, ks * 2 + h);
+            df[ks] = row_frag<DH>(sD, qrow, ks * 2 + h);
+        }
+        const float ls = sLse[qrow], dl = sDel[qrow];
+        f32x16 dQt[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dQt[db][i] = 0.f;
+        for (int kb = 0; kb < p.nkb; ++kb) {
+            // S^T[key][q] (lane = query, register i <-> key kb*32 + 8(i>>2) + 4h + (i&3)) and dP^T = V dO^T
+            f32x16 S, dP;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) S[i] = dP[i] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const uint4 ka = row_frag<DH>(sK, kb * 32 + r, ks * 2 + h);
+                const uint4 va = row_frag<DH>(sV, kb * 32 + r, ks * 2 + h);
+                S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ka), __builtin_bit_cast(bf16x8, qf[ks]), S, 0, 0, 0);
+                dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, va), __builtin_bit_cast(bf16x8, df[ks]), dP, 0, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int key = kb * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
+                const float pv = key < p.L ? __builtin_amdgcn_exp2f(__builtin_fmaf(S[i], c2, -ls)) : 0.f;
+                dP[i] = pv * (dP[i] - dl);
+            }
+            // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 sb = acc_frag(dP, s);
+#pragma unroll
+                for (int db = 0; db < DB; ++db)
+                    dQt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sK, kb * 32 + 16 * s, db, lane), sb, dQt[db], 0, 0, 0);
+            }
+        }
+        if (qrow < p.L) store_rows<DB>(p.dq + (row0 + qrow) * p.lddq + hh * DH, dQt, p.scale, h);
+    }
+}
+
 }  // namespace
+
+static int attn_small_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                             float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    if (!q || !k || !v || !o || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
+    if (dtype != SVOL_BF16 || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(o) & 7))
+        return SVOL_E_UNSUPPORTED;
+    SmallArgs p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo, (int)H, (int)L,
+                (int)((L + 31) / 32), scale * LOG2E, lse2};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)H, (unsigned)n_seq);
+    if (lse2) {
+        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<64, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((attn_small_kernel<32, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<64, false>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((attn_small_kernel<32, false>), grid, dim3(256), 0, s, p);
+    }
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
 
 extern "C" {
 
@@ -226,18 +467,35 @@ int svol_vit_embed(const float* patch_proj, const float* cls_token, const float*
     return SVOL_OK;
 }
 
+
 int svol_attn_small_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                         int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    if (!q || !k || !v || !o || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, n_seq, H, L, dh, scale, dtype, stream);
+}
+
+int svol_attn_small_fwd_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                            float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    if (!lse2) return SVOL_E_INVALID;
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, dtype, stream);
+}
+
+int svol_attn_small_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                        const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                        int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    if (!q || !k || !v || !o || !dout || !lse2 || !dq || !dk || !dv || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
     if (dtype != SVOL_BF16 || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(o) & 7))
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
+        !aligned16(dout) || (reinterpret_cast<uintptr_t>(lse2) & 3))
         return SVOL_E_UNSUPPORTED;
-    SmallArgs p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo, (int)H, (int)L,
-                (int)((L + 31) / 32), scale * LOG2E};
+    if (lddq % 4 || lddk % 4 || lddv % 4 || ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 7))
+        return SVOL_E_UNSUPPORTED;
+    SmallBwdArgs p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse2,
+                   (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, (int)H, (int)L,
+                   (int)((L + 31) / 32), scale, scale * LOG2E};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)H, (unsigned)n_seq);
-    if (dh == 64) hipLaunchKernelGGL(attn_small_kernel<64>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(attn_small_kernel<32>, grid, dim3(256), 0, s, p);
+    if (dh == 64) hipLaunchKernelGGL(attn_small_bwd_kernel<64>, grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL(attn_small_bwd_kernel<32>, grid, dim3(512), 0, s, p);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }

@@ -18,10 +18,23 @@ consumes at BASELINE configs[3]: the sketch's [CLS] state [B,1,768] and ALL 196 
 [B, T*196, 768].
 LayerNorm uses the kernels' eps = 1e-5 where HF uses 1e-12: a relative change of 5e-6 at unit variance, three orders
 below the bf16 operand rounding.
+
+``ViTExtractor(trainable=True)`` in ``.train()`` mode is the extractor the reference optimises (train.py:72 hands every parameter
+of build_model(args) to AdamW) or fine-tunes (preprocess/sketch_vit_finetune.py:43-69,103-143: ``train_layers=K`` trains the last
+K layers and the final LayerNorm, the embeddings and the first 12 - K layers stay frozen and run without autograd).  Same kernels
+and the same forward bits as the frozen path, one autograd Function per piece:
+
+    _ViTEmbedFn   patchify + patch GEMM + [CLS] / position embeddings; backward dW, db = gemm_tn over the saved bf16 patch rows,
+                  dpos = colsum of the stream gradient viewed [n, (P+1)*d], dcls = its first row
+    per layer     LNStreamFn(layernorm_before) -> _ViTAttnFn (q|k|v GEMMs, svol_attn_small_fwd_lse, out-proj + fp32 residual;
+                  backward svol_attn_small_bwd into one packed dQKV, dx = dQKV [W_q; W_k; W_v] in one NT GEMM)
+                  -> LNStreamFn(layernorm_after) -> MLPLNFn(gamma=None, GELU)
+    final norm    LNStreamFn
+The trainable path casts its own bf16 weights at the start of every training forward: ops.weights is refreshed by the head's
+forward, which runs AFTER the backbone, and fused AdamW on ROCm does not bump ``_version``.
 """
 from __future__ import annotations
 
-import math
 from types import SimpleNamespace
 
 import torch
@@ -75,8 +88,140 @@ class _Embeddings(nn.Module):
         self.patch_embeddings = _PatchEmbeddings(cfg)
 
 
+def _patch_rows(pixel_values, p):
+    """[n, C, H, W] fp32 -> (bf16 patch rows [n*P, C*p*p], P)."""
+    n, C, Hh, Ww = pixel_values.shape
+    P = (Hh // p) * (Ww // p)
+    pix = pixel_values.float().contiguous()
+    patches = torch.empty((n * P, C * p * p), dtype=torch.bfloat16, device=pix.device)
+    _lib.check(_lib.lib().svol_patchify(_ptr(pix), _ptr(patches), n, C, Hh, Ww, p, _DT[torch.bfloat16], _stream()), 'svol_patchify')
+    return patches, P
+
+
+def _embed(proj, cls, pos, n, P, d):
+    x32 = torch.empty((n * (P + 1), d), dtype=torch.float32, device=proj.device)
+    _lib.check(_lib.lib().svol_vit_embed(_ptr(proj), _ptr(cls), _ptr(pos), _ptr(x32), 0, n, P, d, _DT[torch.bfloat16], _stream()),
+               'svol_vit_embed')
+    return x32
+
+
+def _wgrad(sinks, shapes, A, B, has_colsum=True):
+    """gemm_tn of the weight (and with has_colsum the bias) gradient of A^T B: into the gradient sinks when the reducer owns
+    both, else into one fresh zeroed buffer.  -> (dW or None, db or None) as the Function returns them."""
+    sW, sb = sinks
+    if sW is not None and (sb is not None or not has_colsum):
+        ops.gemm_tn_sink(A, B, out=sW.view.view(A.shape[1], B.shape[1]), colsum=sb.view if sb is not None else None)
+        return None, None
+    N, K = A.shape[1], B.shape[1]
+    buf = torch.zeros((N * K + N,), dtype=torch.float32, device=A.device)
+    dW, db = buf[:N * K].view(N, K), buf[N * K:]
+    ops.gemm_tn(A, B, out=dW, colsum=db if has_colsum else None)
+    if sW is not None:
+        sW.view.add_(dW.view(sW.view.shape))
+        dW = None
+    if sb is not None:
+        sb.view.add_(db)
+        db = None
+    return (dW.view(shapes[0]) if dW is not None else None), (db if has_colsum else None)
+
+
+class _ViTEmbedFn(torch.autograd.Function):
+    """patchify -> patch GEMM (+ bias, fp32 out) -> [CLS] + position embeddings: the fp32 stream [n*(P+1), d].  No pixel gradient."""
+
+    @staticmethod
+    def forward(ctx, pixel_values, W, b, cls, pos, p):
+        n = pixel_values.shape[0]
+        d = W.shape[0]
+        patches, P = _patch_rows(pixel_values, p)
+        Wc = ops.cast(W.detach().reshape(d, -1).contiguous(), torch.bfloat16)
+        proj = ops.gemm_nt(patches, Wc, b, out_f32=True)
+        x32 = _embed(proj, cls, pos, n, P, d)
+        ctx.save_for_backward(patches)
+        ctx.dims, ctx.wshape = (n, P, d), W.shape
+        nig = ctx.needs_input_grad
+        ctx.sinks = tuple(ops._claim(t, nig[i]) for i, t in ((1, W), (2, b), (3, cls), (4, pos)))
+        return x32
+
+    @staticmethod
+    def backward(ctx, dx32):
+        (patches,) = ctx.saved_tensors
+        n, P, d = ctx.dims
+        sW, sb, sc, sp = ctx.sinks
+        nig = ctx.needs_input_grad
+        dx32 = dx32 if dx32.is_contiguous() else dx32.contiguous()
+        dW = db = dcls = dpos = None
+        if nig[1] or nig[2]:
+            dproj = ops.cast(dx32.view(n, P + 1, d)[:, 1:].reshape(n * P, d), torch.bfloat16)
+            dW, db = _wgrad((sW, sb), (ctx.wshape,), dproj, patches)
+        if nig[3] or nig[4]:
+            # position embeddings: the stream gradient summed over the images; the [CLS] token: the same sum's first row
+            g = ops.colsum(dx32.view(n, (P + 1) * d))
+            if sc is not None:
+                sc.view.view(-1).add_(g[:d])
+            elif nig[3]:
+                dcls = g[:d].clone().view(1, 1, d)
+            if sp is not None:
+                sp.view.view(-1).add_(g)
+            elif nig[4]:
+                dpos = g.view(1, P + 1, d)
+        return None, dW, db, dcls, dpos, None
+
+
+class _ViTAttnFn(torch.autograd.Function):
+    """x32 + o_proj(attention(q_proj(y), k_proj(y), v_proj(y))): the attention half of a pre-norm ViT layer (y = LN_before(x32),
+    bf16).  wc = (W_qkv [3d, d], W_qkv^T [d, 3d], W_o, W_o^T) bf16, cast by the caller this forward."""
+
+    @staticmethod
+    def forward(ctx, x32, y, Wq, bq, Wk, bk, Wv, bv, Wo, bo, wc, dims):
+        n, L, H = dims
+        d = Wq.shape[0]
+        dh = d // H
+        Wqkv, WqkvT, Woc, WoT = wc
+        dev = y.device
+        qkv = torch.empty((n * L, 3 * d), dtype=torch.bfloat16, device=dev)
+        for j, b in enumerate((bq, bk, bv)):
+            ops.gemm_nt(y, Wqkv[j * d:(j + 1) * d], b, out=qkv[:, j * d:(j + 1) * d])
+        o, lse2 = ops.attn_small_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], n, H, L, dh, want_lse=True)
+        out = ops.gemm_nt(o, Woc, bo, residual=x32, out_f32=True)
+        ctx.save_for_backward(y, qkv, o, lse2)
+        ctx.dims, ctx.WqkvT, ctx.WoT = dims, WqkvT, WoT
+        nig = ctx.needs_input_grad
+        ctx.sinks = tuple(ops._claim(t, nig[i]) for i, t in enumerate((Wq, bq, Wk, bk, Wv, bv, Wo, bo), start=2))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout32):
+        y, qkv, o, lse2 = ctx.saved_tensors
+        n, L, H = ctx.dims
+        d = o.shape[1]
+        dout32 = dout32 if dout32.is_contiguous() else dout32.contiguous()
+        ds = ops.cast(dout32, torch.bfloat16)
+        sk = ctx.sinks
+        dWo, dbo = _wgrad((sk[6], sk[7]), ((d, d),), ds, o)
+        do = ops.gemm_nt(ds, ctx.WoT)
+        dqkv = torch.empty((n * L, 3 * d), dtype=torch.bfloat16, device=y.device)
+        ops.attn_small_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse2, n, H, L, d // H,
+                           dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:])
+        g = []
+        if all(s is not None for s in sk[:6]):
+            for j in range(3):
+                g += list(_wgrad((sk[2 * j], sk[2 * j + 1]), ((d, d),), dqkv[:, j * d:(j + 1) * d], y))
+        else:   # one launch for the three projections, split into views
+            dW, db = _wgrad((None, None), ((3 * d, d),), dqkv, y)
+            for j in range(3):
+                gw, gb = dW[j * d:(j + 1) * d], db[j * d:(j + 1) * d]
+                for s_, t_ in ((sk[2 * j], gw), (sk[2 * j + 1], gb)):
+                    if s_ is not None:
+                        s_.view.add_(t_)
+                g += [None if sk[2 * j] is not None else gw, None if sk[2 * j + 1] is not None else gb]
+        dy = ops.gemm_nt(dqkv, ctx.WqkvT) if ctx.needs_input_grad[1] else None
+        return (dout32, dy) + tuple(g) + (dWo, dbo, None, None)
+
+
 class ViTExtractor(nn.Module):
-    def __init__(self, cfg=None, compute_dtype='bf16'):
+    def __init__(self, cfg=None, compute_dtype='bf16', trainable=False, train_layers=None):
+        """trainable=False: the frozen extractor (no parameter requires grad).  trainable=True: every parameter trains
+        (train.py:72), or with train_layers=K only the last K layers and the final LayerNorm (sketch_vit_finetune.py:43-69)."""
         super().__init__()
         cfg = cfg or vit_base_config()
         if compute_dtype != 'bf16':
@@ -87,6 +232,18 @@ class ViTExtractor(nn.Module):
         self.layernorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
         self.requires_grad_(False)
         self._wcache = {}
+        self.trainable = bool(trainable)
+        nl = cfg.num_hidden_layers
+        if train_layers is not None and not 0 <= int(train_layers) <= nl:
+            raise ValueError(f'train_layers must be in [0, {nl}], got {train_layers}')
+        self.train_layers = None if train_layers is None else int(train_layers)
+        if self.trainable:
+            first = 0 if self.train_layers is None else nl - self.train_layers
+            if self.train_layers is None:
+                self.embeddings.requires_grad_(True)
+            for lyr in self.layers[first:]:
+                lyr.requires_grad_(True)
+            self.layernorm.requires_grad_(True)
 
     def load_hf_state_dict(self, sd):
         """state dict of transformers.ViTModel, 5.x names or the 4.x ``encoder.layer.N.attention.attention.query`` style."""
@@ -114,46 +271,94 @@ class ViTExtractor(nn.Module):
             self._wcache[id(src)] = ent
         return ent[1]
 
-    @torch.no_grad()
+    def uses_autograd(self) -> bool:
+        return self.training and self.trainable and torch.is_grad_enabled()
+
     def forward(self, pixel_values: torch.Tensor, return_pre_norm: bool = False):
         """[n, C, H, W] fp32 (normalised) -> last_hidden_state [n, 1 + P, d] fp32."""
         if not pixel_values.is_cuda:
             raise RuntimeError('svol_amd ViTExtractor runs on the MI355X HIP kernels only (no CPU path)')
+        if self.uses_autograd():
+            return self._forward_train(pixel_values, return_pre_norm)
+        with torch.no_grad():
+            return self._forward_frozen(pixel_values, return_pre_norm)
+
+    def _first_trained(self):
+        nl = self.cfg.num_hidden_layers
+        return 0 if self.train_layers is None else nl - self.train_layers
+
+    def _forward_train(self, pixel_values, return_pre_norm):
+        """autograd through the trained part (module docstring); the frozen prefix runs as in _forward_frozen, without autograd.
+        The bf16 copies of the trained weights are cast here, every call; the frozen path's copies of them are dropped."""
         cfg = self.cfg
         dt = torch.bfloat16
-        n, C, Hh, Ww = pixel_values.shape
+        n = pixel_values.shape[0]
         p, d, H = cfg.patch_size, cfg.hidden_size, cfg.num_attention_heads
-        P = (Hh // p) * (Ww // p)
-        L = P + 1
-        dev = pixel_values.device
-        L_ = _lib.lib()
-        pix = pixel_values.float().contiguous()
-        patches = torch.empty((n * P, C * p * p), dtype=dt, device=dev)
-        _lib.check(L_.svol_patchify(_ptr(pix), _ptr(patches), n, C, Hh, Ww, p, _DT[dt], _stream()), 'svol_patchify')
+        first = self._first_trained()
+        for t in self.parameters():
+            if t.requires_grad:
+                self._wcache.pop(id(t), None)
+        if self.train_layers is None:
+            emb = self.embeddings
+            x32 = _ViTEmbedFn.apply(pixel_values, emb.patch_embeddings.projection.weight, emb.patch_embeddings.projection.bias,
+                                    emb.cls_token, emb.position_embeddings, p)
+            L = x32.shape[0] // n
+        else:
+            with torch.no_grad():
+                x32, L = self._embed_frozen(pixel_values)
+                for lyr in self.layers[:first]:
+                    x32 = self._layer_frozen(lyr, x32, n, L)
+        for lyr in self.layers[first:]:
+            a = lyr.attention
+            wqkv, wqkvT = ops.cast_transpose(torch.cat([a.q_proj.weight.detach(), a.k_proj.weight.detach(), a.v_proj.weight.detach()]), dt)
+            woc, woT = ops.cast_transpose(a.o_proj.weight.detach(), dt)
+            y = ops.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, dt, False)
+            x32 = _ViTAttnFn.apply(x32, y, a.q_proj.weight, a.q_proj.bias, a.k_proj.weight, a.k_proj.bias, a.v_proj.weight,
+                                   a.v_proj.bias, a.o_proj.weight, a.o_proj.bias, (wqkv, wqkvT, woc, woT), (n, L, H))
+            y = ops.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
+            m = lyr.mlp
+            w1c, w1T = ops.cast_transpose(m.fc1.weight.detach(), dt)
+            w2c, w2T = ops.cast_transpose(m.fc2.weight.detach(), dt)
+            x32 = ops.MLPLNFn.apply(x32, y, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, None, None, ops.ACT_GELU, None,
+                                    (w1c, w1T, w2c, w2T))
+        last, _ = ops.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, dt, True)
+        if return_pre_norm:
+            return last.view(n, L, d), x32.view(n, L, d)
+        return last.view(n, L, d)
+
+    def _embed_frozen(self, pixel_values):
+        """-> (fp32 stream [n*L, d], L)"""
+        cfg = self.cfg
         emb = self.embeddings
+        n, d = pixel_values.shape[0], cfg.hidden_size
+        patches, P = _patch_rows(pixel_values, cfg.patch_size)
         proj = ops.gemm_nt(patches, self._w(emb.patch_embeddings.projection.weight), emb.patch_embeddings.projection.bias,
                            out_f32=True)
-        x32 = torch.empty((n * L, d), dtype=torch.float32, device=dev)
-        _lib.check(L_.svol_vit_embed(_ptr(proj), _ptr(emb.cls_token), _ptr(emb.position_embeddings), _ptr(x32), 0, n, P, d,
-                                     _DT[dt], _stream()), 'svol_vit_embed')
-        del patches, proj
-        scale = 1.0 / math.sqrt(d // H)
+        del patches
+        return _embed(proj, emb.cls_token, emb.position_embeddings, n, P, d), P + 1
+
+    def _layer_frozen(self, lyr, x32, n, L):
+        cfg = self.cfg
+        dt = torch.bfloat16
+        d, H = cfg.hidden_size, cfg.num_attention_heads
+        dev = x32.device
+        a = lyr.attention
+        _, y, _, _, _ = ops.layernorm_fwd(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, dt)
+        qkv = torch.empty((n * L, 3 * d), dtype=dt, device=dev)
+        for j, lin in enumerate((a.q_proj, a.k_proj, a.v_proj)):
+            ops.gemm_nt(y, self._w(lin.weight), lin.bias, out=qkv[:, j * d:(j + 1) * d])
+        o, _ = ops.attn_small_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], n, H, L, d // H)
+        x32 = ops.gemm_nt(o, self._w(a.o_proj.weight), a.o_proj.bias, residual=x32, out_f32=True)
+        _, y, _, _, _ = ops.layernorm_fwd(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, dt)
+        hmid = ops.gemm_nt(y, self._w(lyr.mlp.fc1.weight), lyr.mlp.fc1.bias, ops.ACT_GELU)
+        return ops.gemm_nt(hmid, self._w(lyr.mlp.fc2.weight), lyr.mlp.fc2.bias, residual=x32, out_f32=True)
+
+    def _forward_frozen(self, pixel_values, return_pre_norm):
+        n, d = pixel_values.shape[0], self.cfg.hidden_size
+        x32, L = self._embed_frozen(pixel_values)
         for lyr in self.layers:
-            a = lyr.attention
-            _, y, _, _, _ = ops.layernorm_fwd(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, dt)
-            qkv = torch.empty((n * L, 3 * d), dtype=dt, device=dev)
-            for j, lin in enumerate((a.q_proj, a.k_proj, a.v_proj)):
-                ops.gemm_nt(y, self._w(lin.weight), lin.bias, out=qkv[:, j * d:(j + 1) * d])
-            o = torch.empty((n * L, d), dtype=dt, device=dev)
-            q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-            _lib.check(L_.svol_attn_small_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o),
-                                              o.stride(0), n, H, L, d // H, scale, _DT[dt], _stream()), 'svol_attn_small_fwd')
-            x32 = ops.gemm_nt(o, self._w(a.o_proj.weight), a.o_proj.bias, residual=x32, out_f32=True)
-            _, y, _, _, _ = ops.layernorm_fwd(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, dt)
-            hmid = ops.gemm_nt(y, self._w(lyr.mlp.fc1.weight), lyr.mlp.fc1.bias, ops.ACT_GELU)
-            x32 = ops.gemm_nt(hmid, self._w(lyr.mlp.fc2.weight), lyr.mlp.fc2.bias, residual=x32, out_f32=True)
-            del qkv, o, hmid, y
-        last, _, _, _, _ = ops.layernorm_fwd(x32, self.layernorm.weight, self.layernorm.bias, dt, want32=True, want_t=False)
+            x32 = self._layer_frozen(lyr, x32, n, L)
+        last, _, _, _, _ = ops.layernorm_fwd(x32, self.layernorm.weight, self.layernorm.bias, torch.bfloat16, want32=True, want_t=False)
         if return_pre_norm:
             return last.view(n, L, d), x32.view(n, L, d)
         return last.view(n, L, d)
@@ -170,13 +375,14 @@ class ViTBackbone(nn.Module):
         self.use_sketch_cls_token = use_sketch_cls_token
         self.frames_per_launch = frames_per_launch
 
-    @torch.no_grad()
     def forward(self, src_sketch, src_video):
-        B, T = src_video.shape[:2]
-        sk = self.sketch_backbone(src_sketch.reshape(-1, *src_sketch.shape[2:]))
-        sk = sk[:, :1] if self.use_sketch_cls_token else sk[:, 1:].mean(1, keepdim=True)  # backbone.py:35-38
-        frames = src_video.reshape(-1, *src_video.shape[2:])
-        outs = [self.video_backbone(frames[i:i + self.frames_per_launch])[:, 1:]
-                for i in range(0, frames.shape[0], self.frames_per_launch)]
-        vd = outs[0] if len(outs) == 1 else torch.cat(outs)
-        return sk.reshape(B, -1, sk.shape[-1]).contiguous(), vd.reshape(B, -1, vd.shape[-1])
+        # gradients flow only where an extractor takes its autograd path (trainable, .train(), grad mode on)
+        with torch.set_grad_enabled(self.sketch_backbone.uses_autograd() or self.video_backbone.uses_autograd()):
+            B, T = src_video.shape[:2]
+            sk = self.sketch_backbone(src_sketch.reshape(-1, *src_sketch.shape[2:]))
+            sk = sk[:, :1] if self.use_sketch_cls_token else sk[:, 1:].mean(1, keepdim=True)  # backbone.py:35-38
+            frames = src_video.reshape(-1, *src_video.shape[2:])
+            outs = [self.video_backbone(frames[i:i + self.frames_per_launch])[:, 1:]
+                    for i in range(0, frames.shape[0], self.frames_per_launch)]
+            vd = outs[0] if len(outs) == 1 else torch.cat(outs)
+            return sk.reshape(B, -1, sk.shape[-1]).contiguous(), vd.reshape(B, -1, vd.shape[-1])

@@ -4,7 +4,10 @@
 src_video_mask)`` keep the reference's signatures and the ``backbone.`` / ``head.`` state-dict
 prefixes.  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
 ``--backbone vit`` runs the ViT-B/16 extractor of ``backbone.py`` on the device for every frame and the sketch
-(frozen); ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4), frozen by default,
+(SURVEY.md §8 f1), frozen unless ``args.train_backbone`` is 1 (``--finetune_layers K``: only the last K layers and the final
+LayerNorm train, as preprocess/sketch_vit_finetune.py does).  Its default stays frozen, unlike the ResNet's: the reference's
+ViT backbone cannot run as shipped (``device`` is undefined in ViTBackbone.forward, backbone.py:30), so no reference run
+trains it, and existing users of ``--backbone vit`` keep the frozen extractors; ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4), frozen by default,
 trained with the head when ``args.train_backbone`` is set (what the reference's train.py does).
 """
 from __future__ import annotations
@@ -36,8 +39,12 @@ def build_backbone(args):
         args.input_vid_dim = 768
         args.input_skch_dim = 768
         # the pretrained google/vit-base-patch16-224-in21k weights are loaded by the caller
-        # (ViTExtractor.load_hf_state_dict); nothing is downloaded here
-        return ViTBackbone(ViTExtractor(vit_base_config()), ViTExtractor(vit_base_config()))
+        # (ViTExtractor.load_hf_state_dict); nothing is downloaded here.  Trained only on an explicit --train_backbone 1 (module
+        # docstring: why the default differs from the ResNet's)
+        tb = bool(getattr(args, 'train_backbone', None) or False)
+        tl = getattr(args, 'finetune_layers', None) if tb else None
+        return ViTBackbone(ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl),
+                           ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl))
     if 'resnet' in args.backbone:  # backbone.py:133-152: ResNet-34 on the frames (7x7 tokens), ResNet-18 + avgpool on the sketch
         from .resnet import ResNetBackbone, resnet18, resnet34
         args.input_vid_dim = 512

@@ -483,6 +483,28 @@ def attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, pre
     _lib.check(rc, 'svol_attn_bwd')
 
 
+def attn_small_fwd(q, k, v, n, H, L, dh, want_lse=False):
+    """short-sequence attention (L <= 256, bf16): q/k/v 2-D [n*L, >= H*dh] views (column slices allowed).
+    -> (o [n*L, H*dh], lse2 [n, H, L] fp32 with want_lse, else None)."""
+    o = torch.empty((n * L, H * dh), dtype=q.dtype, device=q.device)
+    args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0))
+    tail = (n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream())
+    if want_lse:
+        lse2 = torch.empty((n, H, L), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().svol_attn_small_fwd_lse(*args, _ptr(lse2), *tail), 'svol_attn_small_fwd_lse')
+        return o, lse2
+    _lib.check(_lib.lib().svol_attn_small_fwd(*args, *tail), 'svol_attn_small_fwd')
+    return o, None
+
+
+def attn_small_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
+    """gradients of attn_small_fwd into dq / dk / dv (2-D bf16 views, column slices allowed)."""
+    _lib.check(_lib.lib().svol_attn_small_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                              _ptr(do), do.stride(0), _ptr(lse2), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0),
+                                              _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
+               'svol_attn_small_bwd')
+
+
 def im2col(x, N, H, W, C, kh, kw, stride, pad, dtype, strides=None, ldcols=None):
     """x: image batch addressed by element `strides` (sn, sh, sw, sc) — default NHWC contiguous — -> (cols [N*Ho*Wo, ldcols]
     in `dtype`, Ho, Wo); column order (ky, kx, c), zero padding outside the image and in columns >= kh*kw*C."""
@@ -1010,9 +1032,10 @@ class MLPLNFn(torch.autograd.Function):
     (pre-norm layers, transformer.py:205-207: x is then LN(x32), not a copy of x32)."""
 
     @staticmethod
-    def forward(ctx, x32, x, W1, b1, W2, b2, gamma, beta, pos_out, act=ACT_GELU, drop=None):
+    def forward(ctx, x32, x, W1, b1, W2, b2, gamma, beta, pos_out, act=ACT_GELU, drop=None, wc=None):
         """drop = (p, seed_hidden, seed_residual): training-mode dropout of the enc/dec FFN — linear2(dropout(act(linear1 x))) and
-        x + dropout2(.) (transformer.py:168,171,238-240)."""
+        x + dropout2(.) (transformer.py:168,171,238-240).  wc = (W1, W1^T, W2, W2^T) in the compute dtype, cast by the caller
+        (a module that runs before the forward that advances ``weights``' epoch); None: from ``weights``."""
         ctx.set_materialize_grads(False)
         if drop is not None and drop[0] <= 0.0:
             drop = None
@@ -1021,8 +1044,11 @@ class MLPLNFn(torch.autograd.Function):
         D = shp[-1]
         dt = x.dtype
         x2, x32_2 = x.reshape(-1, D), x32.reshape(-1, D)
-        W1c, W1T = weights.get(W1, dt)
-        W2c, W2T = weights.get(W2, dt)
+        if wc is not None:
+            W1c, W1T, W2c, W2T = wc
+        else:
+            W1c, W1T = weights.get(W1, dt)
+            W2c, W2T = weights.get(W2, dt)
         if act == ACT_GELU:
             hid, aux = gemm_nt(x2, W1c, b1, ACT_GELU, want_pre=True)   # aux = pre-activation
         elif act == ACT_RELU:
@@ -1101,7 +1127,7 @@ class MLPLNFn(torch.autograd.Function):
                     s_.view.add_(g_)
         n_ = lambda s_, g_: None if s_ is not None else g_
         return (ds32.view(ctx.shp), dx.view(ctx.shp), n_(sW1, dW1), n_(sb1, db1), n_(sW2, dW2), n_(sb2, db2), n_(sg, dg),
-                n_(sbt, dbt), dpos, None, None)
+                n_(sbt, dbt), dpos, None, None, None)
 
 
 # bf16 mode: the VALUE projections of every attention block multiply by split weights W_hi + W_lo (two bf16 operands = 16
