@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the SVOL hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by the driver as  python -m torch.distributed.run --nnodes=1 --nproc-per-node N
      --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...; one rank per GPU over RCCL)
 
@@ -22,6 +22,12 @@ The timed region is exactly --steps steps (--blocks N: N such blocks back to bac
 `ms_per_step` is the milliseconds one timed step took.  --dump-outputs DIR writes what the last timed step computed
 (dump_outputs below); every step of such a run starts from the seeded initial parameters, so that the dump is the same
 from run to run.  Prints ONE JSON line on rank 0.
+A plain run does only what that line's headline needs: set up, warm up, the timed steps, the dump, the line (plus what the timed
+steps record themselves: their host wall times, the in-step attention timers behind `roofline`, the all-reduce spans).  --full adds
+the measurements that take work of their own: the shader clock the step holds (`sclk_ghz`, --steps more untimed steps), the host
+issue time on an empty queue (`host_issue_ms_per_step` / `_per_rank`, 3 more steps), the attention launches alone
+(`roofline.same_launches_alone`), a --graph run's per-kernel times (eager steps of their own) and `cpu_baseline` (the CPU oracle,
+~40 s; --no-cpu-baseline leaves it out).
 """
 import argparse
 import json
@@ -177,7 +183,10 @@ def main():
     ap.add_argument('--loss-scale', type=float, default=None,
                     help='static loss scale (default: 1024 with --dtype fp16 — fp16 gradients of ~1e-6 underflow otherwise; the reference '
                          'uses apex amp dynamic scaling for fp16 — else 1); folded back out inside the AdamW kernel')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline does not need (sclk_ghz, host_issue_ms_per_step, the attention '
+                         'launches alone, per-kernel times under --graph, cpu_baseline; see the docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     ap.add_argument('--max-inflight', type=int, default=2,
                     help='steps the host may run ahead of the GPU (svol_amd.parallel.StepFence; 0 = unbounded)')
     ap.add_argument('--graph', action='store_true',
@@ -421,7 +430,7 @@ def main():
 
     def timed_block():
         """EXACTLY --steps steps between barrier + synchronize on both sides; returns (seconds — max over ranks —, host seconds until
-        the last step was ISSUED, per-step host wall times)."""
+        the last step was ISSUED, per-step host wall times, the last step's loss)."""
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -431,7 +440,7 @@ def main():
             ts = time.perf_counter()
             if trace:
                 faulthandler.dump_traceback_later(0.06, repeat=False)
-            step()
+            loss_ = step()
             if trace:
                 faulthandler.cancel_dump_traceback_later()
             host.append((time.perf_counter() - ts) * 1e3)
@@ -445,7 +454,7 @@ def main():
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, issued, host
+        return el, issued, host, loss_
 
     # the timed region of the contract: exactly --steps steps (--blocks N: N blocks back to back — one 20-step block is 0.35 s, and
     # box-to-box / run-to-run spread (+-3 %) is larger than a round's gains — the line then reports the MEDIAN block and lists all)
@@ -454,7 +463,8 @@ def main():
     if a.dump_outputs and rank == 0:   # before any further step: the clock block and the issue-time steps below train on
         dumped = dump_outputs(a.dump_outputs, last, params)
     order = sorted(range(len(timed)), key=lambda i: timed[i][0])
-    elapsed, t_issued, host_ms = timed[order[len(order) // 2]]
+    elapsed, t_issued, host_ms = timed[order[len(order) // 2]][:3]
+    raw_loss = timed[-1][3]   # the loss of the last step this run takes (--full: of the last free-running step below)
     if trace:
         print('host_ms per step:', [round(x, 1) for x in host_ms], file=sys.stderr)
     ops.timer.disable()
@@ -495,7 +505,7 @@ def main():
                 'how': 's_memtime / s_memrealtime in one probe wave beside an untimed block of --steps steps right after the timed blocks'}
 
     sclk = None
-    if not use_graph and os.environ.get('SVOL_NO_CLOCK_PROBE') is None:
+    if a.full and not use_graph and os.environ.get('SVOL_NO_CLOCK_PROBE') is None:
         if rank == 0 and world == 1:
             try:
                 sclk = clock_block(True)
@@ -506,12 +516,13 @@ def main():
     # host time to ISSUE one step, measured on an EMPTY queue right after the timed region (3 free-running steps): inside the timed
     # region the host runs ahead until the HIP queue pushes back (a few steps), after which a step's host wall time is the GPU's
     free_ms = []
-    for _ in range(3):
-        ts = time.perf_counter()
-        raw_loss = raw_step()   # (unfenced: this measures issue time alone)
-        free_ms.append((time.perf_counter() - ts) * 1e3)
-    torch.cuda.synchronize()
-    if use_graph:
+    if a.full:
+        for _ in range(3):
+            ts = time.perf_counter()
+            raw_loss = raw_step()   # (unfenced: this measures issue time alone)
+            free_ms.append((time.perf_counter() - ts) * 1e3)
+        torch.cuda.synchronize()
+    if use_graph and a.full:
         # per-kernel durations cannot be bracketed inside a graph replay: time the SAME kernels with HIP events on
         # the launch stream over eager steps run right after the timed region (same process, same shapes, same data)
         crit.static_packed = None
@@ -524,7 +535,7 @@ def main():
     # the same two attention launches ALONE (nothing else on the device), right after the timed region: inside the step the query
     # stream's and the weight-gradient stream's kernels run beside them
     alone = None
-    if rank == 0 and a.dtype != 'fp32':
+    if a.full and rank == 0 and a.dtype != 'fp32':
         try:
             L_ = T * P + (1 if a.workload == 'encdec' else 0)
             Hh, Dm = args.nheads, args.hidden_dim
@@ -555,7 +566,7 @@ def main():
             alone = {'error': repr(e)}
     ar_report = reducer.allreduce_report() if (world > 1 or force_ar) else None   # last issued step (the device is idle: events are final)
     issue_per_rank = None
-    if world > 1:
+    if world > 1 and a.full:
         mine_t = torch.tensor([sorted(free_ms)[1]], device=dev, dtype=torch.float64)
         allt = [torch.zeros_like(mine_t) for _ in range(world)]
         dist.all_gather(allt, mine_t)
@@ -662,7 +673,7 @@ def main():
     if rank == 0:
         res = {
             'metric': 'frames/sec (fwd+matcher+bwd), T=%d·P=%d·d=256' % (T, P),
-            'value': fps, 'unit': 'frames/sec', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+            'value': fps, 'unit': 'frames/sec', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'full': a.full,
             'ms_per_step': ms_per_step, 'ms_per_step_blocks': [round(b_[0] / a.steps * 1e3, 4) for b_ in timed], 'sclk_ghz': sclk,
             'timed_blocks': ('%d blocks of exactly --steps steps, each between barrier + synchronize, max over ranks; value / ms_per_step = the '
                              'median block' % len(timed)),
@@ -680,7 +691,7 @@ def main():
             'n_ranks_seen': n_ranks_seen, 'dist_backend': backend if world > 1 else None,
             'final_loss': final_loss,
             # host time to ISSUE a step (Python + launches, no sync): when it approaches ms_per_step the run is host-bound
-            'host_issue_ms_per_step': sorted(free_ms)[1],            # median of 3 steps issued into an empty queue (see above)
+            'host_issue_ms_per_step': sorted(free_ms)[1] if free_ms else None,   # median of 3 steps issued into an empty queue (--full)
             'host_wall_ms_per_step_in_timed_region': t_issued / a.steps * 1e3,   # includes queue back-pressure
             'host_wall_ms_first_last': [round(x, 2) for x in host_ms[:3] + host_ms[-3:]],
             'launch_mode': 'hipGraph replay (whole step captured)' if use_graph else 'eager',
@@ -702,7 +713,7 @@ def main():
             res['roofline'] = roof
         if dumped is not None:
             res['dumped_outputs'] = {'dir': a.dump_outputs, 'arrays': dumped}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if world > 1 or force_ar:

@@ -367,7 +367,7 @@ def test_bench_world4_gloo_rehearsal_reports_per_rank_issue_time():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY='0', SVOL_DIST_BACKEND='gloo')
     root = os.path.dirname(HERE)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l_ for l_ in p.stdout.splitlines() if l_.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -7,7 +7,7 @@ cd $R
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o r${RN:-5} -- python3 bench.py --steps 10 --warmup 3 --blocks 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 F=$(find $O/kt -name "*kernel_stats.csv" | head -1)
 cp $F $O/round${RN:-5}_kernel_stats.csv
-python tools/prof_summary.py $F 16 > $O/round${RN:-5}_kernel_stats.txt
+python tools/prof_summary.py $F 13 > $O/round${RN:-5}_kernel_stats.txt
 python tools/trace_timeline.py $(find $O/kt -name "*kernel_trace.csv" | head -1) > $O/round${RN:-5}_timeline.txt 2>&1 || true
 python - <<PY > $O/round${RN:-5}_turnaround.txt
 import csv,glob

@@ -9,7 +9,7 @@ O=$R/gpurun_out/refresh_r$RN
 rm -rf $O; mkdir -p $O
 cd $R
 echo "== default bench"
-python bench.py --steps 20 --warmup 5 > $O/round${RN}_bench.json 2> $O/bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/round${RN}_bench.json 2> $O/bench.err
 echo "== traffic + kernel stats (cfg2)"
 RN=$RN bash tools/traffic_step.sh $HEAD > $O/traffic.log 2>&1
 cp gpurun_out/traffic_r$RN/round${RN}_* $O/ 2>/dev/null
@@ -26,16 +26,16 @@ cp $(find $O/kt5 -name "*kernel_stats.csv" | head -1) $O/round${RN}_cfg5_fp16_ke
 python tools/fwd_traffic.py $(find $O/kt5 -name "*kernel_trace.csv" | head -1) $O/round${RN}_cfg5_fp16_hbm_traffic.json 224 "cfg5 (B=1, T=128, P=256, L=32768, fp16)" > $O/round${RN}_cfg5_fp16_roofline.txt 2>&1 || true
 rm -rf $O/fetch5 $O/write5 $O/kt5
 echo "== the other bench modes"
-python bench.py --workload cfg5 --dtype fp16 --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_cfg5_fp16.json 2>> $O/bench.err
-python bench.py --workload cfg5 --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_cfg5_bf16.json 2>> $O/bench.err
-python bench.py --dtype fp16 --steps 20 --warmup 5 --no-cpu-baseline > $O/round${RN}_bench_fp16.json 2>> $O/bench.err
-python bench.py --dtype fp32 --steps 6 --warmup 2 --no-cpu-baseline > $O/round${RN}_bench_fp32.json 2>> $O/bench.err
-python bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_cfg4.json 2>> $O/bench.err
-python bench.py --workload encdec --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_encdec.json 2>> $O/bench.err
-python bench.py --workload resnet --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_resnet.json 2>> $O/bench.err
-python bench.py --workload resnet --train-backbone --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_resnet_trained.json 2>> $O/bench.err
-python bench.py --workload encdec --dropout 0.1 --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_encdec_dropout.json 2>> $O/bench.err
-SVOL_DETERMINISTIC=1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/round${RN}_bench_deterministic.json 2>> $O/bench.err
+python bench.py --workload cfg5 --dtype fp16 --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_cfg5_fp16.json 2>> $O/bench.err
+python bench.py --workload cfg5 --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_cfg5_bf16.json 2>> $O/bench.err
+python bench.py --dtype fp16 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/round${RN}_bench_fp16.json 2>> $O/bench.err
+python bench.py --dtype fp32 --steps 6 --warmup 2 --full --no-cpu-baseline > $O/round${RN}_bench_fp32.json 2>> $O/bench.err
+python bench.py --workload cfg4 --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_cfg4.json 2>> $O/bench.err
+python bench.py --workload encdec --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_encdec.json 2>> $O/bench.err
+python bench.py --workload resnet --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_resnet.json 2>> $O/bench.err
+python bench.py --workload resnet --train-backbone --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_resnet_trained.json 2>> $O/bench.err
+python bench.py --workload encdec --dropout 0.1 --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_encdec_dropout.json 2>> $O/bench.err
+SVOL_DETERMINISTIC=1 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/round${RN}_bench_deterministic.json 2>> $O/bench.err
 echo "== trained-backbone step: kernel statistics"
 bash tools/prof_resnet_train.sh > $O/prof_resnet_train.log 2>&1
 cp gpurun_out/prof_rn/kernel_stats.txt $O/round${RN}_resnet_train_kernel_stats.txt
