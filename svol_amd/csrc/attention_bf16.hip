@@ -43,12 +43,12 @@ struct Args {
     const int* tile_flags;        // [B][ceil(Lk/KT)] key-tile classes of the masked fast kernels (attn_tile_flags_bf16)
     int head_xcd, nxt;            // != 0: 1-D grid of B*H*nxt workgroups with the heads dealt to the 8 XCDs (block_coords)
     int tail_last;                // != 0 (with head_xcd): every head's LAST x tile is dispatched after all the others
-    int* redo;                    // [grid] written by attn_fwd_bf16_fast (1 = a row sum overflowed), read by the safe kernel behind it
+    int* redo;                    // [grid] written by attn_fwd_bf16_fast2 (1 = a row sum overflowed), read by the safe kernel behind it
     unsigned *nl2, *nd2;          // [B,H,Lq] -lse2 / -delta as (hi, lo) bf16 pairs: written by the fast dQ kernel, DMA'd by the dK/dV kernel
     // attention-probability dropout (general kernels only; see attention.hip AttnArgs): keep mask of ((b*H + h)*Lq + q)*Lk + key
     float drop_p, drop_inv;
     uint64_t drop_seed;
-    int dq_rot;                   // != 0: the unmasked dQ kernel runs its rotated schedule (dq_phase; SVOL_ATTN_NO_DQ_ROT=1 clears it)
+    int dq_rot;                   // unused (once the switch to the rotated dQ schedule); kept so the kernel arguments keep their layout
 };
 __device__ __forceinline__ float attn_drop(uint64_t seed, uint64_t row, int key, float p, float inv) {
     return dropout_scale(seed, row, (uint32_t)key, p, inv);
@@ -932,7 +932,7 @@ __device__ __forceinline__ void attn_fwd_pre_body(const Args p) {
 // VGPRs (2 waves per SIMD) instead of this body's 163 (3 waves), 4 % slower.
 __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_pre(Args p) {
     __shared__ __attribute__((aligned(16))) char smem[4 * IMG];
-    // behind attn_fwd_bf16_fast: only the workgroups whose rows overflowed there run (normally none)
+    // behind attn_fwd_bf16_fast2: only the workgroups whose rows overflowed there run (normally none)
     if (p.redo && !p.redo[blockIdx.x]) return;
     char* sK = smem;
     char* sV = smem + 2 * IMG;
@@ -1032,100 +1032,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_pre(Args p) {
     if (qvalid && h == 0) p.lse2[((int64_t)b * p.H + hh) * p.Lq + qrow] = m + __builtin_amdgcn_logf(lt);
 }
 __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_pre_masked(Args p) { attn_fwd_pre_body<true>(p); }
-
-// The fast forward (round 2).  In-kernel ablations of attn_fwd_bf16_pre at the benchmark shape (tools/micro/attn_lab.hip,
-// profiles/round2_attention_lab.md) showed a kernel bound by instruction ISSUE, every class of instruction costing its own
-// time (v_exp ~6, any other VALU ~3, an MFMA ~17, a global load ~75 cycles of SIMD time): the per-tile running maximum (33
-// v_max3 + the exchange + a 20-cycle hazard fence per 128-key tile) and the register staging (4 ds_write_b128 + 16 VGPRs)
-// are pure overhead.  Here the softmax reference is anchored ONCE, at the row maximum of key tile 0, and every tile is
-// exponentiated against it: P = 2^(s - m0) is exact in floating point whatever m0 is (bf16 P keeps its relative precision
-// at any magnitude, l and O accumulate in fp32), as long as nothing overflows — a later score more than ~2^100 above the
-// anchor.  That cannot be ruled out, so it is DETECTED: an inf / NaN row sum flags the workgroup in `redo`, and
-// attn_fwd_bf16_pre, launched right behind this kernel, recomputes exactly the flagged workgroups with per-tile maxima
-// (it exits at once everywhere else).  K / V tiles are staged by LDS-DMA.  0.507 -> 0.447 ms at B 8, H 8, L 6272.
-__global__ __launch_bounds__(256, 2) void attn_fwd_bf16_fast(Args p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * IMG];
-    char* sK = smem;
-    char* sV = smem + 2 * IMG;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    int xt, hh, b;
-    block_coords(p, xt, hh, b);
-    const int qrow = xt * 128 + wave * 32 + r;
-    const bool qvalid = qrow < p.Lq;
-    const h16_t* Q = reinterpret_cast<const h16_t*>(p.q) + (int64_t)b * p.Lq * p.ldq + hh * p.dh;
-    const h16_t* K = reinterpret_cast<const h16_t*>(p.k) + (int64_t)b * p.Lk * p.ldk + hh * p.dh;
-    const h16_t* V = reinterpret_cast<const h16_t*>(p.v) + (int64_t)b * p.Lk * p.ldv + hh * p.dh;
-    uint4 qb[2];
-    load_lane_block(qb, Q, p.ldq, qrow, qvalid, p.dh, h);
-    const int nt = p.Lk / KT;     // launcher guarantees Lk % KT == 0 and dh == 32
-    dma_tile(sK, K, p.ldk, 0, wave, lane);
-    dma_tile(sV, V, p.ldv, 0, wave, lane);
-    dma_wait_all();
-    __syncthreads();
-    float m;                      // the anchor: this query's largest score in key tile 0 (log2 domain)
-    {
-        float mm = -INFINITY;
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            uint4 ka[2];
-            read_rows(ka, sK, sub * 32 + r, h);
-            const f32x16 S = mma_first(ka, qb);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mm = fmaxf(mm, S[i]);
-        }
-        const HalfPair sw = swap_halves(__builtin_bit_cast(unsigned, mm));
-        m = fmaxf(__builtin_bit_cast(float, sw.lo), __builtin_bit_cast(float, sw.hi));
-    }
-    const f32x16 Cm = splat16(-m);
-    f32x16 O = zero16();
-    float l = 0.f;
-    for (int t = 0; t < nt; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < nt) {         // the other buffer was last read in tile t-1, behind that tile's barrier
-            dma_tile_async(sK + (cur ^ 1) * IMG, K, p.ldk, (t + 1) * KT, wave, lane);   // (waited for at the tile boundary)
-            dma_tile_async(sV + (cur ^ 1) * IMG, V, p.ldv, (t + 1) * KT, wave, lane);
-        }
-        const char* kimg = sK + cur * IMG;
-        const char* vimg = sV + cur * IMG;
-        f32x16 S[4];
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            uint4 ka[2];
-            read_rows(ka, kimg, sub * 32 + r, h);
-            S[sub] = mma_first_c(ka, qb, Cm);  // = score - anchor
-        }
-        f32x2 ls[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};   // row sums as v_pk_add_f32 over register pairs (32 instead of 64 adds)
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                S[sub][i] = __builtin_amdgcn_exp2f(S[sub][i]);
-                S[sub][i + 1] = __builtin_amdgcn_exp2f(S[sub][i + 1]);
-                ls[sub] += f32x2{S[sub][i], S[sub][i + 1]};
-            }
-        {
-            const f32x2 t2 = (ls[0] + ls[1]) + (ls[2] + ls[3]);
-            l += t2[0] + t2[1];
-        }
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            uint4 va[2];
-            read_tr(va, vimg, sub, lane);
-            mma_second(O, va, S[sub]);
-        }
-        dma_wait_all();           // this wave's pieces of tile t+1 have landed; the barrier publishes everyone's
-        __syncthreads();
-    }
-    const float lt = l + __shfl_xor(l, 32, 64);
-    const int bad = __syncthreads_or(qvalid && !(lt < SVOL_H16_PSUM_MAX));   // inf / NaN (fp16: any P near 65504): a score left the anchor's range
-    if (tid == 0) p.redo[blockIdx.x] = bad ? 1 : 0;
-    if (bad) return;              // attn_fwd_bf16_pre (next launch on the stream) recomputes this workgroup
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    h16_t* Oo = reinterpret_cast<h16_t*>(p.out_o) + (int64_t)b * p.Lq * p.ldo + hh * p.dh;
-    store_acc(O, Oo, p.ldo, qrow, qvalid, p.dh, h, inv);
-    if (qvalid && h == 0) p.lse2[((int64_t)b * p.H + hh) * p.Lq + qrow] = m + __builtin_amdgcn_logf(lt);
-}
 
 // ---- pieces of the ROTATED dQ loop (round 3) ----------------------------------------------------------------------------------
 // The round-2 loop issued the eight score / dP products of a 32-key step back to back (256 cycles in which the wave issues nothing
@@ -1945,8 +1851,9 @@ constexpr int SP_OFF_Q = 4 * KT * 4 + 512;        // LDS map: [2][KT] -lse2 | [2
 constexpr int SP_OFF_T = SP_OFF_Q + 4 * IMG;
 constexpr int SP_OFF_P = SP_OFF_Q + 8 * IMG;
 
-// NKB = 32-key blocks per wave: 4 in every full workgroup (512 keys); the last workgroup of a head whose key count is not a multiple
-// of 512 spreads its 128 / 256 / 384 keys over all four waves (NKB = 1 / 2 / 3) instead of leaving waves without work.
+// NKB = 32-key blocks per wave.  This template serves the last workgroup of a head whose key count is not a multiple of 512: it
+// spreads its 128 / 256 / 384 keys over all four waves (NKB = 1 / 2 / 3) instead of leaving waves without work.  The full
+// workgroups (512 keys, NKB = 4) run attn_bwd_sp_body4 below: the same algorithm as a hand-placed stream.
 //
 // The kernel is ONE uniform stream of blocks j = step * NKB + kb (32 queries x 32 keys each).  Block j
 //   * issues the score / dP products of block j + 1 (slots 1-4; across a step boundary they use the next step's operands, which were
@@ -1957,14 +1864,12 @@ constexpr int SP_OFF_P = SP_OFF_Q + 8 * IMG;
 // The dQ partial of a step is therefore complete in block 1 of the NEXT step (block 0 two steps later when NKB = 1): it is written to LDS
 // there, published by that step's barrier and added to the fp32 image (atomics) one step later.  DW + 1 extra DRAIN steps flush the
 // pipeline: their row constant is -inf, so P = dS = 0 and the accumulators do not move — no epilogue code, no special cases.
-// ABL: timing-only ablations for tools/micro/attn_lab_sp (results invalid): 1 no vector fillers, 2 no MFMAs, 4 no step barrier,
-// 8 no dS round trip through LDS, 16 no tile DMA / waits.  The product instantiates ABL = 0 only.
 //
 // hh, b: head, batch.  kbase: first key of the workgroup.  [t_begin, t_end): the 128-query tiles it sweeps — all of them for a full
 // workgroup; the tail workgroup of a head (fewer than 512 keys, NKB < 4) exists FOUR times, each sweeping a quarter of the tiles and
 // leaving its dK / dV as an fp32 partial in `tail_out` (attn_dq_round_bf16 adds the four): a tail of 128 keys then costs a sixth of a
 // full workgroup's time instead of 0.6 of it (measured), which is what the partial fourth round of workgroups cost the launch.
-template <int NKB, int ABL = 0>
+template <int NKB>
 __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int hh, int b, int kbase, int t_begin, int t_end, float* tail_out) {
     // every LDS-DMA destination (row constants, Q / dO tiles, the prologue's K / V staging) sits in the first 64 KiB: the existing
     // kernels never put an M0 base above 0xFFFF, and nothing here depends on how many bits of M0 the transfer honours
@@ -2109,13 +2014,8 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
     auto reduce_add = [&](const f32x4 (&v)[4], int qstep) {
         const f32x4 acc = (v[0] + v[1]) + (v[2] + v[3]);
         float* dst = dq_base + (int64_t)min(max(qstep, 0), last_step) * 32 * dqw + dq_lane;
-#ifdef SP_ABLATE   // lab only (tools/micro/attn_lab_sp -DSP_ABLATE=1): plain stores in place of the atomics — same instruction and vmcnt counts
-#pragma unroll
-        for (int e = 0; e < 4; ++e) __builtin_nontemporal_store(acc[e], dst + e * dqw);
-#else
 #pragma unroll
         for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dst + e * dqw, acc[e]);
-#endif
     };
 
     sp_barrier();                          // every wave is done with its staging quarter; zeros / -inf are in place
@@ -2148,7 +2048,7 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
         const int st = 4 * tl + sub;
-        if (!(ABL & 16) && sub == 0 && tl >= 1 && tl + 1 < ntl) {   // the other tile buffers were last read in the step before, behind its barrier
+        if (sub == 0 && tl >= 1 && tl + 1 < ntl) {   // the other tile buffers were last read in the step before, behind its barrier
             dma_tile_at(tl + 1, (tl + 1) & 1);
             asm volatile("" ::: "memory");   // the atomics below stay BEHIND these five transfers (the counted vmcnt below relies on it)
         }
@@ -2170,13 +2070,13 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
             // emptied the filler slots; pinning them with empty asm statements costs an s_nop behind every statement.  So the fillers
             // are asm volatile too: volatile statements keep their order, the instruction stream of a block IS the source below.
             // (Hazards then ours: v_exp result -> VALU read 1 wait state, VALU write -> MFMA operand 2: see the slot comments.)
-#define SP_SLOT(stmt) do { SP_FENCE(); if (!(ABL & 2)) { stmt; } SP_FENCE(); } while (0)
-#define SP_E(i) do { if (!(ABL & 1)) asm volatile("v_exp_f32 %0, %0" : "+v"(S[i])); } while (0)
-#define SP_CP(j) if (!(ABL & 1)) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? pw0 : pw1)[(j) & 3]) : "v"(S[2 * (j)]), "v"(S[2 * (j) + 1]))
-#define SP_M2(i) do { if (ABL & 1) break; f32x2 d_ = {dP[i], dP[(i) + 1]}; const f32x2 s_ = {S[i], S[(i) + 1]}; asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(d_) : "v"(s_)); dP[i] = d_[0]; dP[(i) + 1] = d_[1]; } while (0)
-#define SP_CD(j) if (!(ABL & 1)) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? dw0 : dw1)[(j) & 3]) : "v"(dP[2 * (j)]), "v"(dP[2 * (j) + 1]))
-#define SP_W(g) if (!(ABL & 8)) *reinterpret_cast<uint2*>(img + o_w[g]) = (g) < 2 ? make_uint2(dw0[2 * ((g) & 1)], dw0[2 * ((g) & 1) + 1]) \
-                                                                  : make_uint2(dw1[2 * ((g) & 1)], dw1[2 * ((g) & 1) + 1])
+#define SP_SLOT(stmt) do { SP_FENCE(); stmt; SP_FENCE(); } while (0)
+#define SP_E(i) asm volatile("v_exp_f32 %0, %0" : "+v"(S[i]))
+#define SP_CP(j) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? pw0 : pw1)[(j) & 3]) : "v"(S[2 * (j)]), "v"(S[2 * (j) + 1]))
+#define SP_M2(i) do { f32x2 d_ = {dP[i], dP[(i) + 1]}; const f32x2 s_ = {S[i], S[(i) + 1]}; asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(d_) : "v"(s_)); dP[i] = d_[0]; dP[(i) + 1] = d_[1]; } while (0)
+#define SP_CD(j) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? dw0 : dw1)[(j) & 3]) : "v"(dP[2 * (j)]), "v"(dP[2 * (j) + 1]))
+#define SP_W(g) *reinterpret_cast<uint2*>(img + o_w[g]) = (g) < 2 ? make_uint2(dw0[2 * ((g) & 1)], dw0[2 * ((g) & 1) + 1]) \
+                                                     : make_uint2(dw1[2 * ((g) & 1)], dw1[2 * ((g) & 1) + 1])
             // slot 1
             SP_SLOT(sp_mfma_c(Sn, f.qa[0], kbk[kn][0], f.Cl));
             SP_E(0); SP_E(1); SP_E(2); SP_E(3);
@@ -2223,7 +2123,7 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
 #pragma unroll
             for (int s = 0; s < 2; ++s) { dsa0[s] = dsa1[s]; }
 #pragma unroll
-            for (int s = 0; s < ((ABL & 8) ? 0 : 2); ++s) {  // this block's dS, transposed: consumed in slots 6 / 8 of the block after next
+            for (int s = 0; s < 2; ++s) {  // this block's dS, transposed: consumed in slots 6 / 8 of the block after next
                 const h16x4 lo = SVOL_DS_READ_TR16_H16((lds_bf16x4_ptr)(img + o_rl + 1024 * s));
                 const h16x4 hi = SVOL_DS_READ_TR16_H16((lds_bf16x4_ptr)(img + o_rh + 1024 * s));
                 dsa1[s] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -2239,12 +2139,10 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
         }
         // tile tl + 1 (5 LDS-DMA instructions, issued at the top of this tile) is first read when the operands of its step 0 are
         // fetched: two steps ahead with one block per wave, in the last step of this tile otherwise; 4 atomics per step behind it
-        if (ABL & 16) { }
-        else if (sub == (NKB == 1 ? 1 : 2) && tl >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NKB == 1 ? 8 : 12) : "memory");
+        if (sub == (NKB == 1 ? 1 : 2) && tl >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NKB == 1 ? 8 : 12) : "memory");
         // the partial written in block KBW must be in LDS before the barrier.  LDS operations of a wave complete in order and the
         // step's last eight are W(0..3) and the four transposed reads of its last block: at most those may still be in flight
-        if (ABL & 4) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(8)\n\ts_barrier" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(8)\n\ts_barrier" ::: "memory");
         }
     }
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // the last asm MFMAs' results are read by compiler-generated code below
@@ -2284,7 +2182,6 @@ __device__ __forceinline__ void attn_bwd_sp_body(const Args& p, char* smem, int 
 //     the MFMAs behind gaps 5 / 7 — five gaps of latency cover; 8 registers less.
 // Gap k = what follows MFMA k.  MFMAs: 1, 3 score of the next block, 2, 4 its dP (alternating: no product waits for the accumulator of
 // the MFMA right in front of it), 5 / 9 dV, 7 / 10 dK, 6 / 8 dQ of the previous block.
-template <int ABL = 0>
 __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int hh, int b, int kbase, int t_begin, int t_end) {
     constexpr int NKB = 4;
     float* sL = reinterpret_cast<float*>(smem);   // [2][KT] -lse2
@@ -2449,18 +2346,13 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
     for (int s = 0; s < 2; ++s) dsa[s] = make_uint4(0, 0, 0, 0);
     f32x16 dQp = zero16();
     asm volatile("s_nop 15\n\ts_nop 15" : "+v"(S), "+v"(dP), "+v"(dQp));   // the four products above are complete
-#define SP4_E(X, i) do { if (!(ABL & 1)) asm volatile("v_exp_f32 %0, %0" : "+v"(X[i])); } while (0)
-#define SP4_M(i) do { if (!(ABL & 1)) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(dP[i]) : "v"(S[i])); } while (0)
-#define SP4_CP(j) do { if (!(ABL & 1)) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? pw0 : pw1)[(j) & 3]) : "v"(S[2 * (j)]), "v"(S[2 * (j) + 1])); } while (0)
-#define SP4_CD(j) do { if (!(ABL & 1)) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? dw0 : dw1)[(j) & 3]) : "v"(dP[2 * (j)]), "v"(dP[2 * (j) + 1])); } while (0)
-#define SP4_W(g) do { if (!(ABL & 8)) *reinterpret_cast<uint2*>(img + o_w[g]) = (g) < 2 ? make_uint2(dw0[2 * ((g) & 1)], dw0[2 * ((g) & 1) + 1]) \
-                                                                             : make_uint2(dw1[2 * ((g) & 1)], dw1[2 * ((g) & 1) + 1]); } while (0)
-#define SP4_MF(stmt) do { SP_FENCE(); if (!(ABL & 2)) { stmt; } SP_FENCE(); } while (0)
-#ifdef SP_ABLATE   // lab only: plain stores in place of the atomics — same instruction and vmcnt counts
-#define SP4_ATOM(ptr, val) __builtin_nontemporal_store(val, ptr)
-#else
-#define SP4_ATOM(ptr, val) unsafeAtomicAdd(ptr, val)
-#endif
+#define SP4_E(X, i) asm volatile("v_exp_f32 %0, %0" : "+v"(X[i]))
+#define SP4_M(i) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(dP[i]) : "v"(S[i]))
+#define SP4_CP(j) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? pw0 : pw1)[(j) & 3]) : "v"(S[2 * (j)]), "v"(S[2 * (j) + 1]))
+#define SP4_CD(j) asm volatile("v_cvt_pk_" SVOL_H16_ASM "_f32 %0, %1, %2" : "=v"(((j) < 4 ? dw0 : dw1)[(j) & 3]) : "v"(dP[2 * (j)]), "v"(dP[2 * (j) + 1]))
+#define SP4_W(g) *reinterpret_cast<uint2*>(img + o_w[g]) = (g) < 2 ? make_uint2(dw0[2 * ((g) & 1)], dw0[2 * ((g) & 1) + 1]) \
+                                                      : make_uint2(dw1[2 * ((g) & 1)], dw1[2 * ((g) & 1) + 1])
+#define SP4_MF(stmt) do { SP_FENCE(); stmt; SP_FENCE(); } while (0)
 #define SP4_ADD(d, x, y) do { _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) { float o_; asm volatile("v_add_f32 %0, %1, %2" : "=v"(o_) : "v"((x)[e_]), "v"((y)[e_])); (d)[e_] = o_; } } while (0)
     SP4_E(S, 0); SP4_E(S, 1); SP4_E(S, 2); SP4_E(S, 3); SP4_E(S, 4);   // (the loop does these five in the last two gaps of the block before)
     f32x4 red[4], rsum;
@@ -2476,7 +2368,7 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
         const int st = 4 * tl + sub;
-        if (!(ABL & 16) && sub == 0 && tl >= 1 && tl + 1 < ntl) {   // the other tile buffers were last read in the step before, behind its barrier
+        if (sub == 0 && tl >= 1 && tl + 1 < ntl) {   // the other tile buffers were last read in the step before, behind its barrier
             dma_tile_at(tl + 1, (tl + 1) & 1);
             asm volatile("" ::: "memory");   // the atomics below stay BEHIND these five transfers (the counted vmcnt below relies on it)
         }
@@ -2496,7 +2388,7 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
             const char* img_prev = sT + ks * 2048;
             // ---- gap 1
             SP4_MF(sp_mfma_c(Sn, qa[0], kbk[kn][0], Cl));
-            if (!(ABL & 8)) ds_tr_one(dsa[1], img_prev, 1);
+            ds_tr_one(dsa[1], img_prev, 1);
             if (kb == 1) *reinterpret_cast<f32x4*>(sPart + ((sub - 1) & 1) * SP_PART + ((wave * 4 + 0) * 64 + lane) * 16) = f32x4{dQp[0], dQp[1], dQp[2], dQp[3]};
             if (kb == 2) load_c2(Cl, cln, 0);
             SP_FENCE();
@@ -2508,8 +2400,8 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
             if (kb == 2) load_c2(Cl, cln, 1);
             if (kb == 3) {   // the sum of the partial published by the last barrier -> fp32 image (rows of this workgroup only: see the template)
                 float* dst = dq_base + (int64_t)min(max(st - 2, 0), last_step) * 32 * dqw + dq_lane;
-                SP4_ATOM(dst, rsum[0]);
-                SP4_ATOM(dst + dqw, rsum[1]);
+                unsafeAtomicAdd(dst, rsum[0]);
+                unsafeAtomicAdd(dst + dqw, rsum[1]);
             }
             SP_FENCE();
             SP4_E(S, 7); SP4_M(1); SP4_M(2); SP4_M(3); SP4_CD(0); SP4_CP(2);
@@ -2519,8 +2411,8 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
             if (kb == 2) load_c2(Cd, cdn, 0);   // (the dP product of gap 2 was the old constants' last reader)
             if (kb == 3) {
                 float* dst = dq_base + (int64_t)min(max(st - 2, 0), last_step) * 32 * dqw + dq_lane;
-                SP4_ATOM(dst + 2 * dqw, rsum[2]);
-                SP4_ATOM(dst + 3 * dqw, rsum[3]);
+                unsafeAtomicAdd(dst + 2 * dqw, rsum[2]);
+                unsafeAtomicAdd(dst + 3 * dqw, rsum[3]);
             }
             SP_FENCE();
             SP4_E(S, 8); SP4_E(S, 9); SP4_M(4); SP4_M(5); SP4_CD(1);
@@ -2578,19 +2470,17 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
             // ---- gap 10: dK, second k-step
             SP4_MF(sp_mfma_a(dK[kb], qt[1], dw1));
             SP4_W(3);
-            if (!(ABL & 8)) ds_tr_one(dsa[0], img, 0);
+            ds_tr_one(dsa[0], img, 0);
             SP_FENCE();
             SP4_E(Sn, 2); SP4_E(Sn, 3); SP4_E(Sn, 4);
             if (kb == 2) { SP4_ADD(rsum, rsum, red[3]); }
             S = Sn;
             dP = dPn;
         }
-        if (ABL & 16) { }
-        else if (sub == 2 && tl >= 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        if (sub == 2 && tl >= 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         // the partial written in block 1 must be in LDS before the barrier: LDS operations of a wave complete in order and more than
         // eight follow those stores inside the step
-        if (ABL & 4) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(8)\n\ts_barrier" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(8)\n\ts_barrier" ::: "memory");
         }
     }
 #undef SP4_E
@@ -2600,7 +2490,6 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
 #undef SP4_W
 #undef SP4_MF
 #undef SP4_ADD
-#undef SP4_ATOM
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // the last asm MFMAs' results are read by compiler-generated code below
     h16_t* dKo = reinterpret_cast<h16_t*>(p.dk) + (int64_t)b * p.Lk * p.lddk + hh * 32;
     h16_t* dVo = reinterpret_cast<h16_t*>(p.dv) + (int64_t)b * p.Lk * p.lddv + hh * 32;
@@ -2610,10 +2499,18 @@ __device__ __forceinline__ void attn_bwd_sp_body4(const Args& p, char* smem, int
         store_acc(dV[kb], dVo, p.lddv, key0 + kb * 32 + r, true, 32, h, 1.f);
     }
 }
-// ---- round 5: the fast forward as a hand-placed stream (same algorithm as attn_fwd_bf16_fast: anchored once, LDS-DMA tiles,
-// overflow flag + attn_fwd_bf16_pre behind it).  attn_fwd_bf16_fast is hipcc-scheduled: per 128-key tile it issues, beside 16 MFMAs,
-// 64 exp and 32 cvt_pk, 26 v_pk_add_f32 (row sums in register pairs), 31 v_mov (to build those pairs) and 16 s_nop — and a packed
-// fp32 instruction does not overlap an MFMA at all (profiles/round5_mfma_fillers.md): ~390 cycles per 32 x 32 block against an issue
+// ---- the fast forward.  In-kernel ablations of attn_fwd_bf16_pre at the benchmark shape (profiles/round2_attention_lab.md) showed
+// a kernel bound by instruction ISSUE, every class of instruction costing its own time (v_exp ~6, any other VALU ~3, an MFMA ~17, a
+// global load ~75 cycles of SIMD time): the per-tile running maximum (33 v_max3 + the exchange + a 20-cycle hazard fence per 128-key
+// tile) and the register staging (4 ds_write_b128 + 16 VGPRs) are pure overhead.  Here the softmax reference is anchored ONCE, at the
+// row maximum of key tile 0, and every tile is exponentiated against it: P = 2^(s - m0) is exact in floating point whatever m0 is
+// (bf16 P keeps its relative precision at any magnitude, l and O accumulate in fp32), as long as nothing overflows — a later score
+// more than ~2^100 above the anchor.  That cannot be ruled out, so it is DETECTED: an inf / NaN row sum flags the workgroup in
+// `redo`, and attn_fwd_bf16_pre, launched right behind this kernel, recomputes exactly the flagged workgroups with per-tile maxima
+// (it exits at once everywhere else).  K / V tiles are staged by LDS-DMA.
+// The instruction stream is placed by hand.  Left to hipcc's scheduler, a 128-key tile issues, beside its 16 MFMAs, 64 exp and 32
+// cvt_pk, 26 v_pk_add_f32 (row sums in register pairs), 31 v_mov (to build those pairs) and 16 s_nop — and a packed fp32
+// instruction does not overlap an MFMA at all (profiles/round5_mfma_fillers.md): ~390 cycles per 32 x 32 block against an issue
 // floor of ~264 (4 MFMAs x 8 + 16 exp x 8 + 16 add x 4 + 8 cvt x 5).  Here every MFMA and every vector instruction is an asm statement
 // in source order: a block = [V^T fragments + the next block's K rows from LDS] E0-7 | S' k-step 0 | E8-11 A0-7 | S' k-step 1 |
 // C0-3 E12-15 | PV k-step 0 | C4-7 A8-15 | PV k-step 1, the next block's scores (S') one block ahead and ITS K rows fetched a block before that —
@@ -2793,13 +2690,10 @@ __device__ __forceinline__ float* sp_tail_ptr(const Args& p, const SpWork& w) {
     const int tk = p.Lk % SP_KEYS;
     return p.ws_dq + (int64_t)p.B * p.Lq * p.H * 32 + ((int64_t)(w.b * p.H + w.hh) * 4 + w.part) * 2 * tk * 32;
 }
-// V9: the round-4 body for the full workgroups too (A/B: SVOL_ATTN_SP_V9=1)
-template <int ABL, bool V9 = false>
 __device__ __forceinline__ void attn_bwd_sp_dispatch(const Args& p, char* smem) {
     const SpWork w = sp_work(p);
     if (!w.tail) {
-        if (V9) attn_bwd_sp_body<4, ABL>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, nullptr);
-        else attn_bwd_sp_body4<ABL>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1);
+        attn_bwd_sp_body4(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1);
         return;
     }
     float* to = sp_tail_ptr(p, w);
@@ -2808,24 +2702,13 @@ __device__ __forceinline__ void attn_bwd_sp_dispatch(const Args& p, char* smem) 
         for (int i = threadIdx.x; i < 2 * tk * 32; i += 256) to[i] = 0.f;
         return;
     }
-    if (tk == 384) attn_bwd_sp_body<3, ABL>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
-    else if (tk == 256) attn_bwd_sp_body<2, ABL>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
-    else attn_bwd_sp_body<1, ABL>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
+    if (tk == 384) attn_bwd_sp_body<3>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
+    else if (tk == 256) attn_bwd_sp_body<2>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
+    else attn_bwd_sp_body<1>(p, smem, w.hh, w.b, w.kbase, w.t0, w.t1, to);
 }
-#ifdef SP_LAB
-template <int ABL>
-__global__ __launch_bounds__(256, 1) void attn_bwd_sp_lab(Args p) {
-    __shared__ __attribute__((aligned(1024))) char smem[SP_LDS];
-    attn_bwd_sp_dispatch<ABL>(p, smem);
-}
-#endif
 __global__ __launch_bounds__(256, 1) void attn_bwd_sp_bf16(Args p) {
     __shared__ __attribute__((aligned(1024))) char smem[SP_LDS];
-    attn_bwd_sp_dispatch<0>(p, smem);
-}
-__global__ __launch_bounds__(256, 1) void attn_bwd_sp_bf16_v9(Args p) {
-    __shared__ __attribute__((aligned(1024))) char smem[SP_LDS];
-    attn_bwd_sp_dispatch<0, true>(p, smem);
+    attn_bwd_sp_dispatch(p, smem);
 }
 // workgroups of the launch above
 // blocks of attn_dq_round_bf16: the image (8 elements per thread, rounded up to whole blocks), then the tail partials
@@ -2839,13 +2722,15 @@ static inline unsigned sp_grid(int B, int H, int Lk) { return (unsigned)(B * H *
 // entry points used by attention.hip's C-ABI functions
 // key-split decision shared by forward and backward: only launches whose (query tiles x heads x batch) grid leaves most
 // CUs idle and whose key loop is long; the workspace must hold the partials.  Returns ksplit (1 = no split).
+// workgroups a key-split launch aims for (these launches run on the query stream beside the video half: 256 -> 18.98 / 19.07 ms
+// per step, 512 -> 19.12, 1024 -> 19.28)
+constexpr int KSPLIT_WGS = 256;
 static int plan_ksplit(int B, int H, int Lq, int Lk, int dh, int64_t ws_floats, int* tiles_per_split) {
     const int nt = (Lk + KT - 1) / KT;
     const int64_t wgs = (int64_t)((Lq + 127) / 128) * H * B;
     *tiles_per_split = nt;
     if (wgs >= 192 || nt < 8) return 1;
-    static const int target = getenv("SVOL_ATTN_KSPLIT_WGS") ? atoi(getenv("SVOL_ATTN_KSPLIT_WGS")) : 256;   // (these launches run on the query stream beside the video half: 256 -> 18.98 / 19.07 ms per step, 512 -> 19.12, 1024 -> 19.28)
-    int want = (int)((target + wgs - 1) / wgs);
+    int want = (int)((KSPLIT_WGS + wgs - 1) / wgs);
     if (want > 16) want = 16;
     int tps = (nt + want - 1) / want;
     if (tps < 2) tps = 2;
@@ -2856,7 +2741,8 @@ static int plan_ksplit(int B, int H, int Lq, int Lk, int dh, int64_t ws_floats, 
     return ks;
 }
 // shapes the single-pass backward (attn_bwd_sp_bf16) serves: full 128-row tiles both ways, heads dealt to the XCDs, enough keys for
-// the 512-key workgroups to fill the chip (SVOL_ATTN_SP_MIN_LK lowers the bar: tests drive small shapes through it)
+// the 512-key workgroups to fill the chip
+constexpr int SP_MIN_LK = 2 * SP_KEYS;
 // SVOL_DETERMINISTIC=1: no floating-point atomics in the attention backward — the two-pass kernels (dQ by a query-stationary pass)
 // instead of the single pass, no key split for launches with few queries (their dQ partials meet through atomics).  Gradients are
 // then bit-identical from run to run (tests/test_gpu_ops.py::test_attention_backward_is_bit_reproducible_in_deterministic_mode).
@@ -2865,9 +2751,7 @@ static bool attn_deterministic() {
     return det;
 }
 static bool sp_shape_ok(int B, int H, int Lq, int Lk, int dh) {
-    static const bool no_sp = getenv("SVOL_ATTN_NO_SP") != nullptr || attn_deterministic();
-    static const int min_lk = getenv("SVOL_ATTN_SP_MIN_LK") ? atoi(getenv("SVOL_ATTN_SP_MIN_LK")) : 2 * SP_KEYS;
-    return !no_sp && dh == 32 && H == 8 && (B * H) % 8 == 0 && Lq % KT == 0 && Lk % KT == 0 && Lk >= min_lk;
+    return !attn_deterministic() && dh == 32 && H == 8 && (B * H) % 8 == 0 && Lq % KT == 0 && Lk % KT == 0 && Lk >= SP_MIN_LK;
 }
 // the single-pass few-query backward (attn_bwd_fq_bf16): <= 128 queries, the key-split path's fp32 dQ image bound (ksplit > 1: few
 // query tiles, many key tiles, workspace large enough), head width 32, no attention dropout; SVOL_ATTN_NO_FEWQ=1: the two-pass kernels
@@ -2878,21 +2762,20 @@ static bool fewq_ok(const Args& p) {
 static int64_t sp_ws_floats(int B, int H, int Lq, int Lk) { return (int64_t)B * Lq * H * 32 + (int64_t)B * H * 4 * 2 * (Lk % SP_KEYS) * 32; }
 // an unmasked, pre-multiplied, dropout-free launch of this shape with this workspace runs the single pass
 static bool sp_taken(int B, int H, int Lq, int Lk, int dh, const void* ws, int64_t ws_bytes) {
-    static const bool no_head_xcd = getenv("SVOL_ATTN_NO_HEAD_XCD") != nullptr;
-    return !no_head_xcd && sp_shape_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= 4 * sp_ws_floats(B, H, Lq, Lk);
+    return sp_shape_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= 4 * sp_ws_floats(B, H, Lq, Lk);
 }
 // bytes of the fp32 dQ image at the head of the workspace when the single pass serves the shape, else 0 (svol_attn_bwd_sp_image_bytes)
 int64_t svol_attn_sp_image_bytes_bf16(int B, int H, int Lq, int Lk, int dh, int64_t ws_bytes) {
     return sp_taken(B, H, Lq, Lk, dh, reinterpret_cast<const void*>(16), ws_bytes) ? (int64_t)B * Lq * H * 32 * 4 : 0;
 }
+// few workgroups: the launch runs BESIDE a single-pass kernel whose workgroups own their CUs' register files; a wide grid takes
+// dispatch slots from that kernel's first round (measured: 2048 workgroups cost it 30 us, more than the fill saves)
+constexpr int SP_ZERO_WGS = 64;
 int svol_attn_sp_zero_bf16_launch(float* ws, int64_t ws_bytes, int B, int H, int Lq, int Lk, int dh, hipStream_t s) {
     if (!sp_taken(B, H, Lq, Lk, dh, ws, ws_bytes)) return SVOL_E_UNSUPPORTED;
     const int64_t n4 = (int64_t)B * Lq * H * 32 / 4;
-    // few workgroups: the launch runs BESIDE a single-pass kernel whose workgroups own their CUs' register files; a wide grid takes
-    // dispatch slots from that kernel's first round (measured: 2048 workgroups cost it 30 us, more than the fill saves)
-    static const int wgs = getenv("SVOL_SP_ZERO_WGS") ? atoi(getenv("SVOL_SP_ZERO_WGS")) : 64;
     const int64_t want = (n4 + 255) / 256;
-    hipLaunchKernelGGL(attn_sp_zero_image, dim3((unsigned)(want < wgs ? want : (wgs > 0 ? wgs : 1))), dim3(256), 0, s, ws, n4);
+    hipLaunchKernelGGL(attn_sp_zero_image, dim3((unsigned)(want < SP_ZERO_WGS ? want : SP_ZERO_WGS)), dim3(256), 0, s, ws, n4);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
 int64_t svol_attn_ws_floats_bf16(int B, int H, int Lq, int Lk, int dh) {
@@ -2930,18 +2813,15 @@ int svol_attn_fwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t
     p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.dh = dh; p.scale = scale; p.premul = premul;
     const bool masked = kbias != nullptr || (Lk % KT) != 0;
     // pre-multiplied q: the fast kernels; masked launches with few queries keep the key-split path below
-    static const bool no_pre_masked = getenv("SVOL_ATTN_NO_PRE_MASKED") != nullptr;
     const int ntk = (Lk + KT - 1) / KT;
     const bool pre = premul != 0.f && drop_p == 0.f &&   // (attention dropout lives in the general kernels only)
-                     (!masked || (!no_pre_masked && pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
+                     (!masked || (pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
     p.ksplit = (ws && !pre) ? plan_ksplit(B, H, Lq, Lk, dh, ws_bytes / 4, &p.tiles_per_split) : 1;
     if (p.ksplit == 1) p.tiles_per_split = ntk;
     else bind_ws(p, ws);
     dim3 grid((unsigned)(((Lq + 127) / 128) * p.ksplit), (unsigned)H, (unsigned)B);
-    static const bool no_head_xcd = getenv("SVOL_ATTN_NO_HEAD_XCD") != nullptr;
-    static const bool head_pair = getenv("SVOL_ATTN_NO_HEAD_PAIR") == nullptr;
-    if (pre && !no_head_xcd && (B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
-        p.head_xcd = (head_pair && (B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
+    if (pre && (B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
+        p.head_xcd = ((B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
         p.nxt = (Lq + 127) / 128;
         grid = dim3((unsigned)(B * H * p.nxt));
     }
@@ -2950,13 +2830,10 @@ int svol_attn_fwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t
         hipLaunchKernelGGL(attn_tile_flags_bf16, dim3((unsigned)ntk, (unsigned)B), dim3(64), 0, s, kbias, Lk, ntk, reinterpret_cast<int*>(ws));
         hipLaunchKernelGGL(attn_fwd_bf16_pre_masked, grid, dim3(256), 0, s, p);
     } else if (pre) {
-        static const bool no_fast = getenv("SVOL_ATTN_NO_FAST_FWD") != nullptr;
         const int64_t nwg = (int64_t)grid.x * grid.y * grid.z;
-        if (!no_fast && p.head_xcd && dh == 32 && ws && ws_bytes >= nwg * 4) {
+        if (p.head_xcd && dh == 32 && ws && ws_bytes >= nwg * 4) {
             p.redo = reinterpret_cast<int*>(ws);
-            static const bool fwd_v1 = getenv("SVOL_ATTN_FWD_V1") != nullptr;   // round 2's hipcc-scheduled fast forward (A/B)
-            if (fwd_v1) hipLaunchKernelGGL(attn_fwd_bf16_fast, grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL(attn_fwd_bf16_fast2, grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL(attn_fwd_bf16_fast2, grid, dim3(256), 0, s, p);
         }
         hipLaunchKernelGGL(attn_fwd_bf16_pre, grid, dim3(256), 0, s, p);  // all workgroups, or (p.redo) only the flagged ones
     } else if (masked) hipLaunchKernelGGL(attn_fwd_bf16<true>, grid, dim3(256), 0, s, p);
@@ -2988,10 +2865,9 @@ int svol_attn_bwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t
     p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.dh = dh; p.scale = scale; p.premul = premul;
     const int64_t total = (int64_t)B * Lq * H;
     const bool masked = kbias != nullptr || (Lk % KT) != 0;
-    static const bool no_pre_masked = getenv("SVOL_ATTN_NO_PRE_MASKED") != nullptr;
     const int ntk = (Lk + KT - 1) / KT;
     const bool pre = premul != 0.f && drop_p == 0.f &&
-                     (!masked || (!no_pre_masked && pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
+                     (!masked || (pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
     p.ksplit = (ws && !pre && !attn_deterministic()) ? plan_ksplit(B, H, Lq, Lk, dh, ws_bytes / 4, &p.tiles_per_split) : 1;
     if (p.ksplit == 1) p.tiles_per_split = ntk;
     else bind_ws(p, ws);
@@ -3000,13 +2876,11 @@ int svol_attn_bwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t
     dim3 gk((unsigned)((Lk + 127) / 128), (unsigned)H, (unsigned)B);
     if (!pre) hipLaunchKernelGGL(attn_delta_bf16, gd, dim3(256), 0, s, p);  // (the fast dQ kernel computes delta in its prologue)
     if (pre) {
-        static const bool no_head_xcd = getenv("SVOL_ATTN_NO_HEAD_XCD") != nullptr;
         Args pq = p, pk = p;
         dim3 gq2((unsigned)((Lq + 255) / 256), (unsigned)H, (unsigned)B);
         dim3 gk2 = gk;
-        if (!no_head_xcd && (B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
-            static const bool head_pair = getenv("SVOL_ATTN_NO_HEAD_PAIR") == nullptr;
-            pq.head_xcd = pk.head_xcd = (head_pair && (B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
+        if ((B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
+            pq.head_xcd = pk.head_xcd = ((B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
             pq.nxt = (Lq + 255) / 256;
             pk.nxt = (Lk + 127) / 128;
             pq.tail_last = (Lq % 256 >= 1 && Lq % 256 <= 128 && pq.nxt > 1) ? 1 : 0;
@@ -3029,23 +2903,18 @@ int svol_attn_bwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t
                 if (flags & SVOL_ATTN_DQ_PREZEROED) hipLaunchKernelGGL(attn_bwd_sp_prep_bf16<false>, dim3((unsigned)((int64_t)B * Lq / 32)), dim3(256), 0, s, ps);
                 else hipLaunchKernelGGL(attn_bwd_sp_prep_bf16<true>, dim3((unsigned)((int64_t)B * Lq / 32)), dim3(256), 0, s, ps);
                 prep_ev.fire();
-                static const bool sp_v9 = getenv("SVOL_ATTN_SP_V9") != nullptr;   // round 4's placement of the full workgroups' stream (A/B)
-                if (sp_v9) hipLaunchKernelGGL(attn_bwd_sp_bf16_v9, dim3(sp_grid(B, H, Lk)), dim3(256), 0, s, ps);
-                else hipLaunchKernelGGL(attn_bwd_sp_bf16, dim3(sp_grid(B, H, Lk)), dim3(256), 0, s, ps);
+                hipLaunchKernelGGL(attn_bwd_sp_bf16, dim3(sp_grid(B, H, Lk)), dim3(256), 0, s, ps);
                 hipLaunchKernelGGL(attn_dq_round_bf16, dim3(sp_round_grid(B, H, Lq, Lk)), dim3(256), 0, s, ps);
                 return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
             }
-            static const bool no_dq_rot = getenv("SVOL_ATTN_NO_DQ_ROT") != nullptr;
-            pq.dq_rot = no_dq_rot ? 0 : 1;
             // delta is a 3 x [B,H,Lq] scratch: fp32 delta | -lse2 pairs | -delta pairs (the last two for the DMA dK/dV kernel)
-            static const bool no_dma = getenv("SVOL_ATTN_NO_DKDV_DMA") != nullptr;
-            const bool dma = !no_dma && dh == 32 && Lq % KT == 0;
+            const bool dma = dh == 32 && Lq % KT == 0;
             if (dma) {
                 const int64_t n = (int64_t)B * H * Lq;
                 pq.nl2 = pk.nl2 = reinterpret_cast<unsigned*>(delta + n);
                 pq.nd2 = pk.nd2 = reinterpret_cast<unsigned*>(delta + 2 * n);
             }
-            if (pq.dq_rot && dh == 32) hipLaunchKernelGGL(attn_bwd_dq_bf16_rot, gq2, dim3(256), 0, s, pq);
+            if (dh == 32) hipLaunchKernelGGL(attn_bwd_dq_bf16_rot, gq2, dim3(256), 0, s, pq);
             else hipLaunchKernelGGL(attn_bwd_dq_bf16_pre, gq2, dim3(256), 0, s, pq);
             if (dma) hipLaunchKernelGGL(attn_bwd_dkdv_bf16_pre_dma, gk2, dim3(256), 0, s, pk);
             else hipLaunchKernelGGL(attn_bwd_dkdv_bf16_pre, gk2, dim3(256), 0, s, pk);

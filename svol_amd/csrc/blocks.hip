@@ -95,9 +95,6 @@ const char* const kVhNames = SVOL_VH_SLOTS(SLOT_NAME);
 const char* const kQsNames = SVOL_QS_SLOTS(SLOT_NAME);
 const char* const kQcNames = SVOL_QC_SLOTS(SLOT_NAME);
 
-// the video half's MLP saves gelu' instead of the pre-activation (SVOL_VH_GELU_PRE=1: round 2's form, for A/B runs)
-const int kVhGelu = getenv("SVOL_VH_GELU_PRE") ? SVOL_ACT_GELU : SVOL_ACT_GELU_D;
-
 inline void record(void* ev, void* stream) {
     if (ev) (void)hipEventRecord(static_cast<hipEvent_t>(ev), static_cast<hipStream_t>(stream));
 }
@@ -210,7 +207,7 @@ int svol_video_half_fwd(const int64_t* dims, void* const* p, void* s) {
     // (PRE holds gelu'(pre-activation): SVOL_ACT_GELU_D — the backward's epilogue is then a multiply)
     // (the MLP as ONE launch per direction — round 4's svol_mlp_chain — measured +-0.05 ms in the step in two rounds and left the
     // library in round 5: tools/micro/mlp_chain_bf16.hip, profiles/round4_mlp_chain_lab.md)
-    RUN(svol_gemm_nt(P(Y2), D, nullptr, 0, P(W_FC1), D, P(HID), F, f32(P(B_FC1)), nullptr, kVhGelu, P(PRE), F, nullptr, 0, 0, M, F, D, dt, s));
+    RUN(svol_gemm_nt(P(Y2), D, nullptr, 0, P(W_FC1), D, P(HID), F, f32(P(B_FC1)), nullptr, SVOL_ACT_GELU_D, P(PRE), F, nullptr, 0, 0, M, F, D, dt, s));
     RUN(nt_res(P(HID), F, P(W_FC2), F, P(S3), P(B_FC2), P(Y2_32), M, D, F, dt, s));
     if (P(U_NEXT) && P(GATE_WS_NEXT))   // ... and the NEXT layer's gate scores from the row just normalised (S3 is fp32 in every mode)
         RUN(svol_layernorm_gate_scores_fwd(f32(P(S3)), f32(P(G3)), f32(P(BT3)), f32(P(M32)), P(M), P(MPOS), P(POS), f32(P(MEAN3)),
@@ -232,7 +229,7 @@ int svol_video_half_bwd(const int64_t* dims, void* const* p, int phase, void* s)
         // LN3' -> (ds32, ds), b_fc2' ; (ds W2) * gelu'(pre), b_fc1' ; dpre W1 -> dy2
         RUN(svol_layernorm_bwd(f32(P(DM32)), P(DM), P(DMPOS), P(S3), xf, f32(P(G3)), f32(P(MEAN3)), f32(P(RSTD3)), f32(P(DS32_3)), P(DS3),
                                f32(P(DG3)), f32(P(DBT3)), f32(P(DB_FC2)), M, D, 0.f, 0, nullptr, dt, s));
-        RUN(svol_gemm_nt_dact(P(DS3), D, P(W_FC2_T), D, P(DPRE), F, P(PRE), F, kVhGelu, f32(P(DB_FC1)), M, F, D, dt, s));
+        RUN(svol_gemm_nt_dact(P(DS3), D, P(W_FC2_T), D, P(DPRE), F, P(PRE), F, SVOL_ACT_GELU_D, f32(P(DB_FC1)), M, F, D, dt, s));
         RUN(nt(P(DPRE), F, P(W_FC1_T), F, P(DY2), D, nullptr, nullptr, M, D, F, dt, s));
         // LN2' -> (ds32_2, g), b_o' ; do = g Wo
         RUN(svol_layernorm_bwd(f32(P(DS32_3)), P(DY2), nullptr, P(S2), xf, f32(P(G2)), f32(P(MEAN2)), f32(P(RSTD2)), f32(P(DS32_2)), P(G2D),

@@ -181,107 +181,16 @@ __device__ __forceinline__ double unmono_f64(unsigned long long k) {
     const unsigned long long m = (k >> 63) ? 0x8000000000000000ull : ~0ull;
     return __builtin_bit_cast(double, k ^ m);
 }
-__device__ __forceinline__ bool lsap_reg(const float* __restrict__ Cs, int nr, int nc, int lane, int (&col4row_out)) {
-    const int j0 = lane, j1 = lane + 64;
-    const bool ok0 = j0 < nc, ok1 = j1 < nc;
-    const int j0c = ok0 ? j0 : 0, j1c = ok1 ? j1 : 0;  // clamped cost-row offsets (the value is discarded for a missing column)
-    double v0 = 0.0, v1 = 0.0, spc0 = INFINITY, spc1 = INFINITY, u = 0.0;
-    int path0 = -1, path1 = -1, r4c0 = -1, r4c1 = -1, pos0 = -1, pos1 = -1, c4r = -1;
-    bool sc0 = false, sc1 = false, sr = false;
-    const unsigned long long K_INF = 0xFFF0000000000000ull;  // mono_f64(+inf)
-    for (int cur = 0; cur < nr; ++cur) {
-        pos0 = ok0 ? nc - 1 - j0 : -1;  // remaining[it] = nc - it - 1
-        pos1 = ok1 ? nc - 1 - j1 : -1;
-        sc0 = sc1 = sr = false;
-        spc0 = spc1 = INFINITY;
-        int num_remaining = nc, i = cur, sink = -1;
-        double min_val = 0.0;
-        while (sink == -1) {
-            sr = sr || lane == i;
-            const double ui = readlane_f64(u, i);
-            const float* crow = Cs + i * nc;
-            const double r0 = min_val + (double)crow[j0c] - ui - v0;
-            const double r1 = min_val + (double)crow[j1c] - ui - v1;
-            const bool a0 = pos0 >= 0, a1 = pos1 >= 0;
-            const bool up0 = a0 && r0 < spc0, up1 = a1 && r1 < spc1;
-            spc0 = up0 ? r0 : spc0;
-            path0 = up0 ? i : path0;
-            spc1 = up1 ? r1 : spc1;
-            path1 = up1 ? i : path1;
-            // (cost, preference) of the lane's two columns.  scipy's rule over the remaining columns: lowest cost; among equal costs the
-            // LAST unassigned column visited, else the FIRST column visited -> preference = [unassigned][pos | 127 - pos], larger wins;
-            // slot and lane ride in the low bits (positions are unique, they never decide)
-            const unsigned long long k0 = a0 ? mono_f64(spc0) : ~0ull, k1 = a1 ? mono_f64(spc1) : ~0ull;
-            const unsigned t0 = a0 ? (0x100000u | ((r4c0 == -1 ? 0x80u | (unsigned)pos0 : 127u - (unsigned)pos0) << 8) | (unsigned)lane) : 0u;
-            const unsigned t1 = a1 ? (0x100000u | ((r4c1 == -1 ? 0x80u | (unsigned)pos1 : 127u - (unsigned)pos1) << 8) | 0x40u | (unsigned)lane) : 0u;
-            const bool second = k1 < k0 || (k1 == k0 && t1 > t0);
-            const unsigned long long k = second ? k1 : k0;
-            const unsigned t = second ? t1 : t0;
-            const unsigned hi = (unsigned)(k >> 32), lo = (unsigned)k;
-            const unsigned mh = wave_min_u32(hi);
-            // usually ONE lane holds the smallest upper word (sign, exponent, 20 mantissa bits): it is the arg-min, whatever the rest says
-            const unsigned long long cand = __ballot(hi == mh);
-            unsigned ml, mt;
-            if ((cand & (cand - 1)) == 0) {
-                const int w = __builtin_ctzll(cand);
-                ml = (unsigned)__builtin_amdgcn_readlane((int)lo, w);
-                mt = (unsigned)__builtin_amdgcn_readlane((int)t, w);
-            } else {
-                ml = wave_min_u32(hi == mh ? lo : 0xffffffffu);
-                mt = wave_max_u32((hi == mh && lo == ml) ? t : 0u);
-            }
-            const unsigned long long kmin = ((unsigned long long)mh << 32) | ml;
-            if (kmin >= K_INF) return false;  // infeasible: the cheapest remaining column costs +inf
-            min_val = unmono_f64(kmin);
-            const unsigned pf = (mt >> 8) & 0xffu;
-            const int index = (pf & 0x80u) ? (int)(pf & 0x7fu) : 127 - (int)pf;
-            const int lj = (int)(mt & 0x3fu), slot = (int)((mt >> 6) & 1u);
-            const int j = lj + 64 * slot;
-            const int r4 = __builtin_amdgcn_readlane(slot ? r4c1 : r4c0, lj);
-            if (r4 == -1) sink = j; else i = r4;
-            const int last = num_remaining - 1;
-            // SC[j] = true; remaining[index] = remaining[last]; --num_remaining
-            const bool me0 = lane == lj && slot == 0, me1 = lane == lj && slot == 1;
-            sc0 = sc0 || me0;
-            sc1 = sc1 || me1;
-            pos0 = me0 ? -1 : (pos0 == last ? index : pos0);
-            pos1 = me1 ? -1 : (pos1 == last ? index : pos1);
-            num_remaining = last;
-        }
-        // dual update
-        if (lane == cur) u += min_val;
-        {
-            const int c = c4r < 0 ? 0 : c4r;
-            const double s0 = __shfl(spc0, c & 63, 64), s1 = __shfl(spc1, c & 63, 64);
-            if (sr && lane != cur && lane < nr) u += min_val - ((c >> 6) ? s1 : s0);
-        }
-        if (sc0) v0 -= min_val - spc0;
-        if (sc1) v1 -= min_val - spc1;
-        // augment along the path
-        int j = sink;
-        for (;;) {
-            const int lj = j & 63, slot = j >> 6;
-            const int ii = slot ? __builtin_amdgcn_readlane(path1, lj) : __builtin_amdgcn_readlane(path0, lj);
-            if (lane == lj) { if (slot) r4c1 = ii; else r4c0 = ii; }
-            const int t = __builtin_amdgcn_readlane(c4r, ii);
-            if (lane == ii) c4r = j;
-            j = t;
-            if (ii == cur) break;
-        }
-    }
-    col4row_out = c4r;
-    return true;
-}
-
-// Round 6: the same solver with a shorter step.  One search step of lsap_reg is ~150 instructions of ONE wave (~900 cycles: the 48
-// problems of a training step run one wave each on 48 CUs, and the launch — 0.2 ms — sits on the forward -> backward dependency
-// chain with the rest of the chip idle).  What the step needs per column pair is the smallest UPPER word of the two keys; the lower
-// word, the tie preference and the per-lane pre-selection only matter when two candidates share an upper word (sign, exponent, 20
-// mantissa bits) — then the full procedure of lsap_reg runs (`slow`), bit for bit.  Otherwise the one candidate IS the arg-min:
-// its value, list position and row are four v_readlane.  Scanned-column flags are the removed positions (pos < 0), scanned rows a
-// scalar bit mask, the row index a scalar (v_readfirstlane: the cost row's address is SALU), the second column's cost an immediate
-// offset from the first (the staged block is padded: the value of a column >= nc is discarded).  Same arithmetic in the same
-// order, same visiting order, same tie rule: assignments bit-identical to lsap_reg's (tests: scipy blocks incl. ties, goldens).
+// The search step is kept short: it is ONE wave's work (the 48 problems of a training step run one wave each on 48 CUs, and the
+// launch — 0.2 ms — sits on the forward -> backward dependency chain with the rest of the chip idle), and a step that runs the full
+// (cost, preference) arg-min every time is ~150 instructions (~900 cycles).  What the step needs per column pair is the smallest
+// UPPER word of the two keys; the lower word, the tie preference and the per-lane pre-selection only matter when two candidates
+// share an upper word (sign, exponent, 20 mantissa bits) — then the full (cost, preference) arg-min runs (`slow`), bit for bit.
+// Otherwise the one candidate IS the arg-min: its value, list position and row are four v_readlane.  Scanned-column flags are the
+// removed positions (pos < 0), scanned rows a scalar bit mask, the row index a scalar (v_readfirstlane: the cost row's address is
+// SALU), the second column's cost an immediate offset from the first (the staged block is padded: the value of a column >= nc is
+// discarded).  Same arithmetic in the same order, same visiting order, same tie rule as the LDS version: assignments bit-identical
+// (tests: scipy blocks incl. ties, goldens).
 __device__ __forceinline__ unsigned mono_hi32(unsigned hi) { return hi ^ ((unsigned)((int)hi >> 31) | 0x80000000u); }
 __device__ __forceinline__ bool lsap_reg2(const float* __restrict__ Cs, int nr, int nc, int lane, int (&col4row_out)) {
     const int j0 = lane, j1 = lane + 64;
@@ -327,7 +236,10 @@ __device__ __forceinline__ bool lsap_reg2(const float* __restrict__ Cs, int nr, 
                     index = __builtin_amdgcn_readlane(pos1, lj);
                     r4 = __builtin_amdgcn_readlane(r4c1, lj);
                 }
-            } else {   // `slow`: several candidates share the upper word — lsap_reg's full (cost, preference) arg-min
+            } else {   // `slow`: several candidates share the upper word — the full (cost, preference) arg-min
+                // scipy's rule over the remaining columns: lowest cost; among equal costs the LAST unassigned column visited, else the
+                // FIRST column visited -> preference = [unassigned][pos | 127 - pos], larger wins; slot and lane ride in the low bits
+                // (positions are unique, they never decide)
                 const bool a0 = pos0 >= 0, a1 = pos1 >= 0;
                 const unsigned long long k0 = a0 ? mono_f64(spc0) : ~0ull, k1 = a1 ? mono_f64(spc1) : ~0ull;
                 const unsigned t0 = a0 ? (0x100000u | ((r4c0 == -1 ? 0x80u | (unsigned)pos0 : 127u - (unsigned)pos0) << 8) | (unsigned)lane) : 0u;
@@ -382,7 +294,7 @@ __global__ __launch_bounds__(64) void lsap_kernel(const float* __restrict__ cost
                                                   const int32_t* __restrict__ pred_off, const int32_t* __restrict__ pred_cnt,
                                                   const int32_t* __restrict__ tgt_off, const int32_t* __restrict__ tgt_cnt,
                                                   int32_t* __restrict__ match, int32_t* __restrict__ status, int max_dim,
-                                                  int stage_floats, int v1) {
+                                                  int stage_floats) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     double* u = reinterpret_cast<double*>(lds);
     double* v = u + max_dim;
@@ -426,10 +338,10 @@ __global__ __launch_bounds__(64) void lsap_kernel(const float* __restrict__ cost
         if (lane == 0) status[p] = 1;
         return;
     }
-    if (staged && nr <= 64 && nc <= 128) {  // register-resident path (see lsap_reg)
+    if (staged && nr <= 64 && nc <= 128) {  // register-resident path (see lsap_reg2)
         __syncthreads();
         int c4 = -1;
-        if (!(v1 ? lsap_reg(Cs, nr, nc, lane, c4) : lsap_reg2(Cs, nr, nc, lane, c4))) {
+        if (!lsap_reg2(Cs, nr, nc, lane, c4)) {
             if (lane == 0) status[p] = 2;
             return;
         }
@@ -691,10 +603,9 @@ int svol_lsap_batched(const float* cost, const int64_t* cost_off, const int32_t*
     const size_t pad = 512;   // lsap_reg2 reads column lane + 64 of a cost row unconditionally (discarded when >= nc)
     if (base + stage + pad > 65536) stage = base + pad < 65536 ? (65536 - base - pad) / 16 * 16 : 0;
     const size_t lds = base + stage + pad;
-    static const int v1 = getenv("SVOL_LSAP_V1") != nullptr;   // round 2's search step (A/B)
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(lsap_kernel, dim3((unsigned)n_problems), dim3(64), lds, s, cost, cost_off, pred_off, pred_cnt, tgt_off,
-                       tgt_cnt, match, status, md, (int)(stage / 4), v1);
+                       tgt_cnt, match, status, md, (int)(stage / 4));
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }

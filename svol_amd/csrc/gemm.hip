@@ -575,9 +575,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_skinny(SkArgs p) {
 // 16-byte aligned rows everywhere
 inline bool skinny_f32_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* A, const void* B,
                           const void* C) {
-    static const bool off = getenv("SVOL_GEMM_NO_F32_SKINNY") != nullptr;
-    static const int64_t max_m = getenv("SVOL_F32_SKINNY_M") ? atoll(getenv("SVOL_F32_SKINNY_M")) : 2048;   // (8192 would put the fp32 heads of the bf16 mode, M = 4800, on this kernel: -0.07 ms per step — but also the fp32 mode's video GEMMs at B = 1, whose summation order the golden assignments are pinned on)
-    return !off && M <= max_m && K % 128 == 0 && N % 32 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(A) &&
+    constexpr int64_t max_m = 2048;   // (8192 would put the fp32 heads of the bf16 mode, M = 4800, on this kernel: -0.07 ms per step — but also the fp32 mode's video GEMMs at B = 1, whose summation order the golden assignments are pinned on)
+    return M <= max_m && K % 128 == 0 && N % 32 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(A) &&
            aligned16(B) && aligned16(C) && (M + 31) / 32 <= 65535;
 }
 
@@ -617,13 +616,12 @@ static int tn_generic_plan(const void* A, int64_t lda, const void* B, int64_t ld
     // split the contraction so that ~TARGET workgroups exist, chunk a multiple of CT
     // (measured on MI355X: the fp32 atomics of the final accumulation dominate small outputs, so few, long-running
     //  workgroups win there: 256x256 outputs 0.065 ms at 1024 workgroups vs 0.032 ms at 256)
-    static const int force_wgs = getenv("SVOL_TN_WGS") ? atoi(getenv("SVOL_TN_WGS")) : 0;
     // fp32 with few rows (the query stream's weight gradients, Mc = 800): every split adds a full tile of fp32 atomics — 13 splits of the
     // [256, 2048] MLP gradients were 6.8 M atomics per problem, which is what their 87 us were (atomic rate ~128 per clock, tools/micro/
     // atomic_rate) — so few splits: ~64 workgroups per problem
     // (round 4, in the step: 64 -> 18.75-18.92 ms, 128 -> 18.94-18.97, 32 -> 18.82, 256 -> 18.90: these launches run beside the video half)
-    static const int small_wgs = getenv("SVOL_TN_SMALL_WGS") ? atoi(getenv("SVOL_TN_SMALL_WGS")) : 64;
-    const int target_wgs = force_wgs ? force_wgs : ((dtype == SVOL_F32 && Mc <= 4096) ? small_wgs : (tiles <= 8 ? 256 : 512));
+    constexpr int small_wgs = 64;
+    const int target_wgs = (dtype == SVOL_F32 && Mc <= 4096) ? small_wgs : (tiles <= 8 ? 256 : 512);
     int64_t want = (target_wgs + tiles - 1) / tiles;
     if (svol_deterministic()) want = 1;   // no contraction split: one adder per output element
     int64_t chunk = (Mc + want - 1) / want;
@@ -766,8 +764,7 @@ int svol_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* 
     if (!A || !B || !C || Mc < 0 || N <= 0 || K <= 0) return SVOL_E_INVALID;
     if (Mc == 0) return SVOL_OK;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
-    static const bool no_fast_tn = getenv("SVOL_TN_GENERIC") != nullptr;
-    if (svol_is16(dtype) && !no_fast_tn) {
+    if (svol_is16(dtype)) {
         const int rc = (dtype == SVOL_BF16 ? svol_gemm_tn_bf16_fast : svol_gemm_tn_f16_fast)(A, lda, B, ldb, C, ldc, colsum, Mc, N, K,
                                                                                               reinterpret_cast<hipStream_t>(stream));
         if (rc != SVOL_E_UNSUPPORTED) return rc;
@@ -790,11 +787,10 @@ int svol_gemm_tn_grouped(const svol_tn_problem* pr, int32_t n, int dtype, void* 
     if (!pr || n < 0) return SVOL_E_INVALID;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    static const bool no_group = getenv("SVOL_TN_NO_GROUP") != nullptr;
     for (int32_t i0 = 0; i0 < n; i0 += SVOL_TN_GROUP_MAX) {
         const int m = (int)((n - i0 < SVOL_TN_GROUP_MAX) ? n - i0 : SVOL_TN_GROUP_MAX);
         int rc = SVOL_E_UNSUPPORTED;
-        bool ok = !no_group && m > 1;
+        bool ok = m > 1;
         for (int i = 0; ok && i < m; ++i) ok = pr[i0 + i].A && pr[i0 + i].B && pr[i0 + i].C && pr[i0 + i].Mc > 0 && pr[i0 + i].N > 0 && pr[i0 + i].K > 0;
         if (ok && svol_is16(dtype)) {
             rc = (dtype == SVOL_BF16 ? svol_gemm_tn_bf16_grouped : svol_gemm_tn_f16_grouped)(pr + i0, m, s);
@@ -818,7 +814,7 @@ int svol_gemm_tn_grouped(const svol_tn_problem* pr, int32_t n, int dtype, void* 
                 rc = SVOL_E_UNSUPPORTED;
             }
         }
-        if (rc == SVOL_E_UNSUPPORTED) {   // one by one (odd shapes, a single problem, SVOL_TN_NO_GROUP)
+        if (rc == SVOL_E_UNSUPPORTED) {   // one by one (odd shapes, a single problem)
             for (int i = 0; i < m; ++i) {
                 const svol_tn_problem& q = pr[i0 + i];
                 const int r1 = svol_gemm_tn(q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.colsum, q.Mc, q.N, q.K, dtype, stream);

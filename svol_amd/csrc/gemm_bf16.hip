@@ -455,8 +455,7 @@ int svol_gemm_nt_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ld
         const int rc = svol_gemm_n256_bf16(A, lda, B, ldb, C, ldc, bias, act, pre, res, ldr, out_f32, epi, colscale, M, N, K, kwrap, s);
         if (rc != SVOL_E_UNSUPPORTED) return rc;
     }
-    static const int skinny_max = getenv("SVOL_GEMM_SKINNY_M") ? atoi(getenv("SVOL_GEMM_SKINNY_M")) : 2048;
-    if (M <= skinny_max && K % 256 == 0 && N % SK_BN == 0 && kwrap % (K / 4) == 0) {
+    if (M <= 2048 && K % 256 == 0 && N % SK_BN == 0 && kwrap % (K / 4) == 0) {
         dim3 g((unsigned)(N / SK_BN), (unsigned)((M + SK_BM - 1) / SK_BM));
         if (out_f32) hipLaunchKernelGGL(gemm_nt_bf16_skinny_f32, g, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(gemm_nt_bf16_skinny_b16, g, dim3(256), 0, s, p);
@@ -466,9 +465,7 @@ int svol_gemm_nt_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ld
     if (grid.y > 65535u) return SVOL_E_UNSUPPORTED;
     // K-step 32 keeps the two-stage ring at 32 KiB per workgroup (4-5 workgroups per CU hide the DMA latency of the
     // short K = 256 loops); deep-K launches use 64-deep steps (half the barriers)
-    static const int force_bk = getenv("SVOL_GEMM_BK") ? atoi(getenv("SVOL_GEMM_BK")) : 0;
-    const bool bk64 = force_bk ? (force_bk == 64) : (K % 64 == 0 && K >= 1024);
-    if (bk64 && K % 64 == 0 && kwrap % 64 == 0) {
+    if (K % 64 == 0 && K >= 1024 && kwrap % 64 == 0) {
         if (out_f32) hipLaunchKernelGGL(gemm_nt_bf16_f32_k64, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(gemm_nt_bf16_b16_k64, grid, dim3(256), 0, s, p);
     } else {

@@ -206,8 +206,7 @@ __global__ __launch_bounds__(256, 2) void gemm_n256_bf16_b16(N256Args p) { gemm_
 int svol_gemm_n256_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
                         void* pre, const void* res, int64_t ldr, int out_f32, int epi, const float* colscale, int64_t M,
                         int64_t N, int64_t K, int64_t kwrap, hipStream_t s) {
-    static const bool off = getenv("SVOL_GEMM_NO_N256") != nullptr;
-    if (off || N % BN || K % BK || K < 512 || M < 4096) return SVOL_E_UNSUPPORTED;
+    if (N % BN || K % BK || K < 512 || M < 4096) return SVOL_E_UNSUPPORTED;
     if (epi != 0 || pre || colscale) return SVOL_E_UNSUPPORTED;
     if (kwrap != K && (kwrap % BK || 2 * kwrap != K)) return SVOL_E_UNSUPPORTED;
     if (act != SVOL_ACT_NONE && ((act != SVOL_ACT_GELU && act != SVOL_ACT_RELU) || out_f32)) return SVOL_E_UNSUPPORTED;   // (GELU_D: needs `pre`, not here)

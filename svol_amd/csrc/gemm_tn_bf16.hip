@@ -295,17 +295,13 @@ bool tn_plan(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, i
     // backward's critical path (it runs on the weight-gradient stream): ~128 workgroups per problem.  Round 4, same box, ms per step
     // of bench.py against this target: 32 -> 20.1, 64 -> 19.0, 96 -> 18.9, **128 -> 18.6-18.8**, 160 -> 18.9, 256 / 512 by tile count
     // (rounds 2-3: the best for the kernel ALONE, 146 us against ~200 for the MLP pair) -> 19.1, 512 -> 19.5, 1024 -> 20.9.  A
-    // multiple of the 8 XCDs so that the tiles of one row chunk share an L2.  SVOL_TN_WGS / SVOL_TN_WGS2 (problems with more
-    // than 8 output tiles) override.
-    static const int force_wgs = getenv("SVOL_TN_WGS") ? atoi(getenv("SVOL_TN_WGS")) : 0;
-    static const int force_wgs2 = getenv("SVOL_TN_WGS2") ? atoi(getenv("SVOL_TN_WGS2")) : force_wgs;
-    const int target_wgs = wgs_override ? wgs_override : (tiles <= 8 ? (force_wgs ? force_wgs : 128) : (force_wgs2 ? force_wgs2 : 128));
+    // multiple of the 8 XCDs so that the tiles of one row chunk share an L2.
+    const int target_wgs = wgs_override ? wgs_override : 128;
     int64_t want = (target_wgs + tiles - 1) / tiles;
     if (want > 8) want = want / 8 * 8;
     // split-major mapping (tn_dma_body): needs a multiple of 8 row chunks; taken when that costs at most 2 x the target
-    static const int split_major_on = getenv("SVOL_TN_SPLIT_MAJOR") ? atoi(getenv("SVOL_TN_SPLIT_MAJOR")) : 1;
     bool split_major = false;
-    if (split_major_on && !wgs_override && 8 * tiles <= 2 * target_wgs) {
+    if (!wgs_override && 8 * tiles <= 2 * target_wgs) {
         if (want < 8) want = 8;
         split_major = true;
     }
@@ -356,8 +352,8 @@ int svol_conv_wgrad_bf16_fast(const void* dz, const void* x, float* dwp, int64_t
     TnConvArgs a{};
     int64_t wgs = 0;
     // the convolutions' weight gradients are most of the backbone's backward, not a side dish beside an attention kernel: fill the chip
-    // (SVOL_CONV_WGRAD_WGS: lab override; measured in profiles/round5_resnet_train_kernel_stats.txt)
-    static const int conv_wgs = getenv("SVOL_CONV_WGRAD_WGS") ? atoi(getenv("SVOL_CONV_WGRAD_WGS")) : 256;   // 128 -> 34.2, 256 -> 29.6, 512 -> 29.9, 1024 -> 30.6 ms per step
+    // (measured in profiles/round5_resnet_train_kernel_stats.txt)
+    constexpr int conv_wgs = 256;   // 128 -> 34.2, 256 -> 29.6, 512 -> 29.9, 1024 -> 30.6 ms per step
     if (!tn_plan(dz, Cout, x, 8, dwp, Kp, nullptr, M, Cout, Kp, a.t, wgs, conv_wgs)) return SVOL_E_UNSUPPORTED;   // (ldb is not used by the gather)
     a.g = TnConvGeom{(int)H, (int)W, (int)C, (int)Ho, (int)Wo, (int)kw, (int)stride, (int)pad, (int)K, (int)(N * H * W * C * 2)};
     hipLaunchKernelGGL(gemm_tn_bf16_conv, dim3((unsigned)wgs), dim3(256), 0, stream, a);

@@ -608,8 +608,7 @@ WSP_KERNEL(gemm_wsp_bf16_drelu, 2, SVOL_ACT_RELU, false, false, 3)
 int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
                       void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux, int64_t ldaux,
                       float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K, hipStream_t s) {
-    static const bool off = getenv("SVOL_GEMM_NO_WS") != nullptr;
-    if (off || K != WS_K || N % 64 || M < 4096) return SVOL_E_UNSUPPORTED;
+    if (K != WS_K || N % 64 || M < 4096) return SVOL_E_UNSUPPORTED;
     int mode;
     if (epi == 1) {
         if (!aux || out_f32) return SVOL_E_UNSUPPORTED;
@@ -631,12 +630,9 @@ int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, vo
     const int64_t ncg = (N + 255) / 256;
     // slabs per workgroup: every workgroup first reads its 128 KiB slice of W, so few long-lived workgroups win as
     // long as they fill the chip (measured, M = 50176: N = 256 best at ~250 workgroups, N = 2048 at ~512)
-    static const int force_tpw = getenv("SVOL_WS_TPW") ? atoi(getenv("SVOL_WS_TPW")) : 0;
-    int64_t tpw = force_tpw ? force_tpw : (ntile * ncg + (ncg <= 2 ? 255 : 511)) / (ncg <= 2 ? 256 : 512);
-    if (!force_tpw) {
-        if (tpw < 4) tpw = 4;
-        if (tpw > 64) tpw = 64;
-    }
+    int64_t tpw = (ntile * ncg + (ncg <= 2 ? 255 : 511)) / (ncg <= 2 ? 256 : 512);
+    if (tpw < 4) tpw = 4;
+    if (tpw > 64) tpw = 64;
     const int64_t ldmax = lda > ldr * 2 ? lda : ldr * 2;
     int64_t ldbig = ldmax > ldaux ? ldmax : ldaux;  // 32-bit buffer offsets inside one workgroup's rows (loads and stores)
     if (ldc > ldbig) ldbig = ldc;
@@ -652,14 +648,13 @@ int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, vo
     WsArgs p{(const h16_t*)A, (const h16_t*)W, C, bias, colscale, (h16_t*)pre, res, (const h16_t*)aux, colsum,
              lda, ldw, ldc, ldp, ldr, ldaux, (int)M, (int)N, act, (int)tpw, (int)nchunk};
     dim3 grid((unsigned)(ncg * nchunk));
-    static const bool no_pipe = getenv("SVOL_WS_NO_PIPE") != nullptr;
-    void (*kp)(WsArgs) = nullptr;
-    if (!no_pipe && mode == 0) {
+    void (*kp)(WsArgs) = nullptr;   // the pipelined kernels, where one exists for the mode and epilogue
+    if (mode == 0) {
         if (act == SVOL_ACT_NONE && !pre) kp = colscale ? gemm_wsp_bf16_none_scale : gemm_wsp_bf16_none;
         else if (act == SVOL_ACT_GELU && !colscale) kp = pre ? gemm_wsp_bf16_gelu_pre : gemm_wsp_bf16_gelu;
         else if (act == SVOL_ACT_GELU_D && !colscale) kp = gemm_wsp_bf16_gelu_dpre;
         else if (act == SVOL_ACT_RELU && !pre && !colscale) kp = gemm_wsp_bf16_relu;
-    } else if (!no_pipe && mode == 2) {
+    } else if (mode == 2) {
         kp = act == SVOL_ACT_RELU ? gemm_wsp_bf16_drelu : (act == SVOL_ACT_GELU_D ? gemm_wsp_bf16_dmul : gemm_wsp_bf16_dgelu);
     }
     if (kp) hipLaunchKernelGGL(kp, grid, dim3(256), 0, s, p);

@@ -324,11 +324,8 @@ __global__ void weighted_total_bwd_kernel(const float* __restrict__ w, const flo
     if (i < n) dx[i] = w[i] * dout[0];
 }
 
-// 8 waves when the layer has at least 8 chunks of 32 columns (D >= 256); SVOL_HEADS_WAVES=4: round 6's first form (A/B)
-inline unsigned heads_threads(int64_t D) {
-    static const int w = getenv("SVOL_HEADS_WAVES") ? atoi(getenv("SVOL_HEADS_WAVES")) : 8;
-    return (w >= 8 && D >= 256) ? 512u : 256u;
-}
+// 8 waves when the layer has at least 8 chunks of 32 columns (D >= 256)
+inline unsigned heads_threads(int64_t D) { return D >= 256 ? 512u : 256u; }
 
 }  // namespace
 
