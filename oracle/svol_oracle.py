@@ -123,9 +123,9 @@ def _mha_p(sd, p):
     return (sd[p + '.in_proj_weight'], sd[p + '.in_proj_bias'], sd[p + '.out_proj.weight'], sd[p + '.out_proj.bias'])
 
 
-def cross_modal_layer(sd, p: str, h: int, src_vid, src_skch, out, vid_pad_mask, vid_pos, query_pos):
-    """CrossModalTransformerLayer.forward, cross_modal_transformer.py:105-160
-    (batch-first).  Returns (mem, out)."""
+def video_half(sd, p: str, h: int, src_vid, src_skch, vid_pos):
+    """The video half of CrossModalTransformerLayer.forward, cross_modal_transformer.py:122-143 (batch-first): gate + LN1,
+    video self-attention + LN2, MLP1 + LN3.  src_skch [B,1,d].  Returns mem."""
     # gate (:122-127): only the head-mean weights of sketch->video attention are used
     _, att1 = mha(src_skch, src_vid + vid_pos, src_vid + vid_pos, *_mha_p(sd, p + 'sketch_video_cross_attn'), h,
                   need_output=False)  # [B,1,L]
@@ -136,18 +136,33 @@ def cross_modal_layer(sd, p: str, h: int, src_vid, src_skch, out, vid_pad_mask, 
     o, _ = mha(qk, qk, mem, *_mha_p(sd, p + 'content_self_attn'), h)
     mem = _ln(o + mem, sd, p + 'norm2')
     # MLP1 (:142-143)
-    mem = _ln(mem + mlp_block(mem, sd, p + 'mlp1'), sd, p + 'norm3')
-    # query self-attention (:145-149)
+    return _ln(mem + mlp_block(mem, sd, p + 'mlp1'), sd, p + 'norm3')
+
+
+def query_self(sd, p: str, h: int, out, query_pos):
+    """Query self-attention + LN4, cross_modal_transformer.py:145-147.  Returns out."""
     qk = out + query_pos
     o, _ = mha(qk, qk, out, *_mha_p(sd, p + 'token_self_attn'), h)
-    out = _ln(o + out, sd, p + 'norm4')
+    return _ln(o + out, sd, p + 'norm4')
+
+
+def query_cross(sd, p: str, h: int, out, mem, vid_pad_mask, vid_pos, query_pos):
+    """Query -> video cross-attention + LN5, MLP2 + LN6, cross_modal_transformer.py:149-158; vid_pad_mask is True on pads.
+    Returns out."""
     # query -> video cross-attention (:151-156), key_padding_mask=True on pads
     o, _ = mha(out + query_pos, mem + vid_pos, mem, *_mha_p(sd, p + 'content_token_cross_attn'), h,
                key_padding_mask=vid_pad_mask)
     out = _ln(out + o, sd, p + 'norm5')
     # MLP2 (:157-158)
-    out = _ln(out + mlp_block(out, sd, p + 'mlp2'), sd, p + 'norm6')
-    return mem, out
+    return _ln(out + mlp_block(out, sd, p + 'mlp2'), sd, p + 'norm6')
+
+
+def cross_modal_layer(sd, p: str, h: int, src_vid, src_skch, out, vid_pad_mask, vid_pos, query_pos):
+    """CrossModalTransformerLayer.forward, cross_modal_transformer.py:105-160
+    (batch-first).  Returns (mem, out)."""
+    mem = video_half(sd, p, h, src_vid, src_skch, vid_pos)
+    out = query_self(sd, p, h, out, query_pos)
+    return mem, query_cross(sd, p, h, out, mem, vid_pad_mask, vid_pos, query_pos)
 
 
 def svanet_forward(sd: Dict[str, torch.Tensor], args, src_sketch, src_sketch_mask, src_video, src_video_mask,
