@@ -94,6 +94,29 @@ int svol_adamw_flat_scaled(float* p, const float* g, float* m, float* v, int64_t
                            float weight_decay, float grad_mul, const float* scaler_state, void* stream);
 int svol_loss_scaler_update(float* scaler_state, float growth_factor, float backoff_factor, int64_t growth_interval, float min_scale,
                             float max_scale, void* stream);
+/* The reference's other two --optimizer choices (train.py:94-97) over the same kind of flat, 16-byte aligned fp32 ranges; new symbols
+ * only, the ABI version is unchanged.  All return SVOL_E_INVALID on a null pointer, n < 0 or (where a step is passed) step <= 0,
+ * SVOL_OK on n == 0, SVOL_E_UNSUPPORTED on a misaligned range; no allocation, no synchronisation.
+ * torch.optim.SGD(lr, momentum, weight_decay), dampening 0, nesterov / maximize off (train.py:94-95):
+ *   d = g * grad_scale + wd * p;  buf = momentum * buf + d;  p -= lr * buf.
+ * A zero-initialised buf makes the first step torch's buf = clone(d); momentum == 0 is plain SGD.  20 bytes per parameter.
+ * _zero: the gradient range is zeroed behind its read, as svol_adamw_flat_zero does.
+ * _scaled: the contract of svol_adamw_flat_scaled (a no-op when scaler_state[1] is set; g' = g * grad_mul / scaler_state[0]). */
+int svol_sgd_flat(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
+                  void* stream);
+int svol_sgd_flat_zero(float* p, float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
+                       void* stream);
+int svol_sgd_flat_scaled(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_mul,
+                         const float* scaler_state, void* stream);
+/* torch.optim.Adam(lr, weight_decay) with its coupled L2, amsgrad / maximize off (train.py:96-97):
+ *   g' = g * grad_scale + wd * p;  then the moment and step arithmetic of svol_adamw_flat without its p *= 1 - lr*wd.
+ * step counts from 1; _scaled takes it from scaler_state[3] + 1. */
+int svol_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, int64_t step, float grad_scale, void* stream);
+int svol_adam_flat_zero(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int64_t step, float grad_scale, void* stream);
+int svol_adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_mul, const float* scaler_state, void* stream);
 
 /* ---- GEMMs (nn.Linear and its backward) --------------------------------- */
 /* C[M,N] = act((A[M,K] * B[N,K]^T + bias[N]) * colscale[N]) + residual[M,N]

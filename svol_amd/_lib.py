@@ -53,6 +53,12 @@ SIGNATURES = {
     'svol_grad_finite': [_p, _i64, _p, _p],
     'svol_adamw_flat_scaled': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _p, _p],
     'svol_loss_scaler_update': [_p, _f32, _f32, _i64, _f32, _f32, _p],
+    'svol_sgd_flat': [_p, _p, _p, _i64, _f32, _f32, _f32, _f32, _p],
+    'svol_sgd_flat_zero': [_p, _p, _p, _i64, _f32, _f32, _f32, _f32, _p],
+    'svol_sgd_flat_scaled': [_p, _p, _p, _i64, _f32, _f32, _f32, _f32, _p, _p],
+    'svol_adam_flat': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _p],
+    'svol_adam_flat_zero': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _p],
+    'svol_adam_flat_scaled': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _p, _p],
     'svol_conv_nhwc': [_p, _p, _i64, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_im2col': [_p, _i64, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_maxpool_nhwc': [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],

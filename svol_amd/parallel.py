@@ -358,7 +358,7 @@ class BucketedGradAllReduce:
 
 class DynamicLossScaler:
     """apex-amp style dynamic loss scaling for fp16 operands (the reference's fp16 mode: configs.py:52-61, ``amp.scale_loss`` at
-    train.py:231-232) kept entirely on the device: ``scale(loss)`` multiplies by the scale tensor, ``FlatAdamW.step()`` checks the
+    train.py:231-232) kept entirely on the device: ``scale(loss)`` multiplies by the scale tensor, ``FlatAdamW.step()`` (FlatAdam, FlatSGD alike) checks the
     flat gradient buckets for inf / NaN, SKIPS the whole update when one is found (parameters, moments and the bias-correction step
     count keep their values), and halves / grows the scale — no host synchronisation, no ``.item()``.  ``state_dict()`` speaks the
     ``amp`` entry of the reference's checkpoints (``{'loss_scaler0': {'loss_scale', 'unskipped'}}``)."""
@@ -382,31 +382,18 @@ class DynamicLossScaler:
         self.state[2] = float(e.get('unskipped', 0))
 
 
-class FlatAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW (decoupled weight decay, amsgrad off; the reference's optimizer, train.py:98-99) over the reducer's
-    flat buckets: the parameters of a bucket are re-homed into ONE flat fp32 buffer (``param.data`` becomes a view, like
-    ``param.grad`` already is), the moments are flat too, and a step is one streaming kernel per bucket (``svol_adamw_flat``:
-    28 bytes per parameter) instead of torch's multi-tensor launches over ~150 separate tensors (0.44 ms -> 0.15 ms at the
-    benchmark size).  Parameters the reducer skips (they never receive a gradient) are not touched, as in torch.
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FlatAdamW, FlatAdam and FlatSGD share: the parameters of every reducer bucket re-homed into one flat fp32 buffer
+    (``param.data`` becomes a view, like ``param.grad`` already is) with flat state buffers beside it, one update kernel per bucket,
+    the gradient mean's ``1 / world`` and the loss scale riding that kernel, ``zero_grads`` / ``step_in_backward``, the dynamic loss
+    scaler, and checkpoints in the schema of the torch optimizer of the same name.  A subclass names its state buffers (``_STATE``),
+    the hyper-parameters a checkpoint carries (``_HYPER``), and launches its kernels (``_launch_bucket``, ``_launch_scaled``)."""
 
-    It IS a ``torch.optim.Optimizer``: one ``param_groups`` entry whose ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` the step
-    reads (so ``StepLR`` / ``MultiStepLR`` of the reference loop, train.py:127-130, wrap it), and ``state_dict()`` /
-    ``load_state_dict()`` speak torch AdamW's schema — ``{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups':
-    [...]}`` with ``i`` indexing ``params`` — so a checkpoint written by the reference (train.py:267-284) resumes here and vice
-    versa.  ``params``: the optimizer's parameter list in the REFERENCE's order (train.py:72: every trainable parameter in
-    ``named_parameters()`` order, including the ones that never get a gradient and therefore have no state entry); defaults
-    to the reducer's own parameters in bucket order."""
+    _STATE = ()        # (key in self.flat[i], key in torch's per-parameter state) per flat state buffer
+    _HYPER = ()        # hyper-parameter keys of the param group that load_state_dict() takes from a checkpoint
+    _HAS_STEP = True   # torch's per-parameter state carries 'step'
 
-    def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
-        """zero_grads: the update kernel zeroes each gradient bucket behind its read (``svol_adamw_flat_zero``) and the reducer's next
-        ``zero_grad()`` skips its fill — the reference loop's ``optimizer.zero_grad()`` (train.py:222) folded into ``step()``; for a
-        loop that reads no ``param.grad`` between ``step()`` and ``zero_grad()``.
-        step_in_backward: a bucket's update is issued as soon as its gradients are final (behind its all-reduce at world size > 1),
-        on the reducer's communication stream, instead of all of them in ``step()`` behind the whole backward; ``step()`` then only
-        updates what is left (the last bucket) and closes the step.  Same arithmetic on the same values: the reference has no
-        gradient clipping or any other cross-bucket dependency between backward and the update (train.py:229-234).  NOT for a loop
-        that may skip ``step()`` after ``backward()``; ignored while a loss scaler is attached (its overflow check spans all buckets)."""
+    def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool):
         owned = [p for b in reducer.buckets for p in b['params']]
         plist = list(params) if params is not None else owned
         self._params_given = params is not None
@@ -414,9 +401,6 @@ class FlatAdamW(torch.optim.Optimizer):
         missing = [p for p in owned if id(p) not in known]
         if missing:
             raise ValueError(f'{len(missing)} parameter(s) of the gradient buckets are not in `params`')
-        defaults = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
-                        weight_decay=float(weight_decay), amsgrad=False, maximize=False, foreach=None, capturable=False,
-                        differentiable=False, fused=None)
         super().__init__(plist, defaults)
         self.reducer = reducer
         self.t = 0
@@ -424,7 +408,7 @@ class FlatAdamW(torch.optim.Optimizer):
         # inside the update kernel
         self.loss_scale = 1.0
         self._scaler: Optional[DynamicLossScaler] = None   # set for fp16 training: overflow check + skip + dynamic scale (see step())
-        self.flat = []      # per bucket: flat parameters / first / second moments
+        self.flat = []      # per bucket: flat parameters and flat state buffers
         self._slot = {}     # id(param) -> (bucket index, offset, numel)
         for bi, b in enumerate(reducer.buckets):
             flat_g = b['flat']
@@ -434,17 +418,20 @@ class FlatAdamW(torch.optim.Optimizer):
                 flat_p[off:off + n].copy_(p.data.reshape(-1))
                 p.data = flat_p[off:off + n].view_as(p)  # same layout as the gradient views of the bucket
                 self._slot[id(p)] = (bi, off, n)
-            self.flat.append({'p': flat_p, 'm': torch.zeros_like(flat_p), 'v': torch.zeros_like(flat_p)})
+            st = {'p': flat_p}
+            for k, _ in self._STATE:
+                st[k] = torch.zeros_like(flat_p)
+            self.flat.append(st)
         self.zero_grads = bool(zero_grads)
         self.step_in_backward = bool(step_in_backward)
         self._stepped = [False] * len(self.flat)
         if self.step_in_backward:
             reducer.on_bucket_reduced = self._step_bucket_early
 
-    # With a scaler attached the bias-correction step count is the DEVICE count of updates really taken (scaler.state[3]: an
-    # overflow-skipped step does not advance it, as apex + torch AdamW do not advance 'step').  It is what checkpoints carry
-    # (a resume used to restart it at 1 under warm moments), so attaching a scaler or loading a state dict keeps the
-    # two in step: whichever happens second pushes the loaded count to the device.
+    # With a scaler attached the count of updates really taken lives on the DEVICE (scaler.state[3]: an overflow-skipped step does
+    # not advance it, as apex + torch do not advance 'step'); it is the bias-correction step of the Adam family and what checkpoints
+    # carry (a resume used to restart it at 1 under warm moments), so attaching a scaler or loading a state dict keeps
+    # the two in step: whichever happens second pushes the loaded count to the device.
     @property
     def scaler(self) -> Optional['DynamicLossScaler']:
         return self._scaler
@@ -467,9 +454,15 @@ class FlatAdamW(torch.optim.Optimizer):
 
     # the hyper-parameters live in param_groups[0] (what torch's schedulers edit); attribute access kept for callers
     lr = property(lambda self: self.param_groups[0]['lr'], lambda self, v: self.param_groups[0].__setitem__('lr', float(v)))
-    betas = property(lambda self: self.param_groups[0]['betas'])
-    eps = property(lambda self: self.param_groups[0]['eps'])
     weight_decay = property(lambda self: self.param_groups[0]['weight_decay'])
+
+    def _launch_bucket(self, b, st, g, t, gscale, stream):
+        """one bucket's update with step count ``t`` and gradient factor ``gscale`` on ``stream`` (the zeroing kernel under zero_grads)"""
+        raise NotImplementedError
+
+    def _launch_scaled(self, b, st, g, gmul, sc, stream):
+        """the same under the loss scaler ``sc``: a no-op on an overflowed step, the gradient factor is gmul / scale"""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -478,19 +471,17 @@ class FlatAdamW(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
         if self.scaler is not None:
-            # dynamic loss scaling (a static scale with no overflow check lets one inf gradient poison p, m and v for good):
-            # the buckets are checked first, every update kernel is a no-op on an overflowed step, then the scale moves
+            # dynamic loss scaling (a static scale with no overflow check lets one inf gradient poison the parameters and the
+            # optimizer state for good): the buckets are checked first, every update kernel is a no-op on an overflowed step, then the
+            # scale moves
             sc = self.scaler
             gmul = float(self.reducer.pending_scale)
             self.reducer.pending_scale = 1.0
-            self.t += 1    # (host-side count of step() calls; the bias corrections use the DEVICE count of steps really taken)
+            self.t += 1    # (host-side count of step() calls; the DEVICE counts the steps really taken)
             for b in self.reducer.buckets:
                 _lib.check(_lib.lib().svol_grad_finite(_ptr(b['flat']), b['flat'].numel(), _ptr(sc.state), _stream()), 'svol_grad_finite')
             for b, st in zip(self.reducer.buckets, self.flat):
-                rc = _lib.lib().svol_adamw_flat_scaled(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(),
-                                                       float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']),
-                                                       float(g['weight_decay']), gmul, _ptr(sc.state), _stream())
-                _lib.check(rc, 'svol_adamw_flat_scaled')
+                self._launch_scaled(b, st, g, gmul, sc, _stream())
             _lib.check(_lib.lib().svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval,
                                                           sc.min_scale, sc.max_scale, _stream()), 'svol_loss_scaler_update')
             return loss
@@ -503,16 +494,6 @@ class FlatAdamW(torch.optim.Optimizer):
                 continue
             self._launch_bucket(b, st, g, self.t, gscale, _stream())
         return loss
-
-    def _launch_bucket(self, b, st, g, t, gscale, stream):
-        from . import _lib
-        from .ops import _ptr
-        fn = _lib.lib().svol_adamw_flat_zero if self.zero_grads else _lib.lib().svol_adamw_flat
-        rc = fn(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(), float(g['lr']), float(g['betas'][0]),
-                float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), t, gscale, stream)
-        _lib.check(rc, 'svol_adamw_flat_zero' if self.zero_grads else 'svol_adamw_flat')
-        if self.zero_grads:
-            b['clean'] = True
 
     @torch.no_grad()
     def _step_bucket_early(self, bi, stream):
@@ -532,22 +513,151 @@ class FlatAdamW(torch.optim.Optimizer):
     def _views(self, p):
         bi, off, n = self._slot[id(p)]
         st = self.flat[bi]
-        return st['m'][off:off + n].view_as(p), st['v'][off:off + n].view_as(p)
+        return tuple(st[k][off:off + n].view_as(p) for k, _ in self._STATE)
+
+    def _has_state(self) -> bool:
+        """torch would hold per-parameter state by now"""
+        return self.steps_taken() > 0   # (not the count of step() calls: overflow-skipped steps are not steps)
 
     def state_dict(self):
-        """torch.optim.AdamW's schema.  A parameter has a state entry iff it has a slot in a gradient bucket and at least
-        one step was taken (torch creates the entry at the first step of a parameter that has a gradient)."""
+        """The schema of the torch optimizer of the same name.  A parameter has a state entry iff it has a slot in a gradient
+        bucket and at least one step was taken (torch creates the entry at the first step of a parameter that has a gradient)."""
         plist = self.param_groups[0]['params']
         state = {}
-        taken = self.steps_taken()   # (not the count of step() calls: overflow-skipped steps are not steps)
-        if taken > 0:
+        if self._has_state():
+            taken = self.steps_taken()
             for i, p in enumerate(plist):
                 if id(p) in self._slot:
-                    m, v = self._views(p)
-                    state[i] = {'step': torch.tensor(float(taken)), 'exp_avg': m.clone(), 'exp_avg_sq': v.clone()}
+                    ent = {'step': torch.tensor(float(taken))} if self._HAS_STEP else {}
+                    for (_, name), view in zip(self._STATE, self._views(p)):
+                        ent[name] = view.clone()
+                    state[i] = ent
         group = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
         group['params'] = list(range(len(plist)))
         return {'state': state, 'param_groups': [group]}
+
+    def _check_group(self, g0):
+        """refuse a checkpoint written with options this optimizer does not implement"""
+        if g0.get('amsgrad') or g0.get('maximize'):
+            raise ValueError('amsgrad / maximize are not supported')
+
+    def _entry_is_empty(self, ent) -> bool:
+        """a per-parameter entry of a checkpoint that stands for "no state yet" and is passed over on load"""
+        return False
+
+    def load_state_dict(self, sd):
+        name = type(self).__name__
+        if not self._params_given:
+            # torch's schema maps state to parameters BY POSITION in the optimizer's list (train.py:72: named_parameters() order);
+            # this optimizer was built in bucket (arrival) order, so the state of the many equal-shaped d x d weights would be
+            # silently permuted (ADVICE r2)
+            raise ValueError(f'{name}.load_state_dict: build the optimizer with params=<the parameter list in the order the checkpoint '
+                             'was written with (the reference: every trainable parameter in named_parameters() order)>')
+        groups = sd['param_groups']
+        plist = self.param_groups[0]['params']
+        ids = [i for g in groups for i in g['params']]
+        if len(ids) != len(plist):
+            raise ValueError(f'loaded state dict holds {len(ids)} parameters, the optimizer {len(plist)}')
+        g0 = groups[0]
+        for g in groups[1:]:
+            if any(g.get(k) != g0.get(k) for k in self._HYPER):
+                raise ValueError(f'{name} keeps one parameter group: the loaded groups differ in their hyper-parameters')
+        self._check_group(g0)
+        steps = set()
+        todo = []
+        for pos, i in enumerate(ids):
+            ent = sd['state'].get(i)
+            p = plist[pos]
+            if ent is None or self._entry_is_empty(ent):
+                continue
+            lacking = [k for _, k in self._STATE if ent.get(k) is None] + (['step'] if self._HAS_STEP and 'step' not in ent else [])
+            if lacking:
+                raise ValueError(f'parameter {pos}: the state entry lacks {lacking}')
+            if id(p) not in self._slot:
+                raise ValueError(f'parameter {pos} has optimizer state but no gradient bucket here')
+            for _, k in self._STATE:
+                if ent[k].numel() != p.numel():
+                    raise ValueError(f'parameter {pos}: {k} of {ent[k].numel()} elements for {p.numel()} weights')
+            if self._HAS_STEP:
+                steps.add(int(float(ent['step'])))
+            todo.append((p, ent))
+        if len(steps) > 1:
+            raise ValueError(f'per-parameter step counts differ ({sorted(steps)}); {name} keeps one')
+        for st in self.flat:
+            for k, _ in self._STATE:
+                st[k].zero_()
+        for p, ent in todo:
+            for (_, k), view in zip(self._STATE, self._views(p)):
+                view.copy_(ent[k].reshape(p.shape))
+        # (a schema without 'step' does not say how many updates were taken; one is enough to know that state exists)
+        self.t = (steps.pop() if steps else 0) if self._HAS_STEP else int(bool(todo))
+        if self._scaler is not None:
+            self._scaler.state[3] = float(self.t)
+        grp = self.param_groups[0]
+        for k in self._HYPER + ('initial_lr',):
+            if k in g0:
+                grp[k] = (float(g0[k][0]), float(g0[k][1])) if k == 'betas' else float(g0[k])
+
+
+class FlatAdamW(_FlatOptimizer):
+    """torch.optim.AdamW (decoupled weight decay, amsgrad off; the reference's optimizer, train.py:98-99) over the reducer's
+    flat buckets: the parameters of a bucket are re-homed into ONE flat fp32 buffer (``param.data`` becomes a view, like
+    ``param.grad`` already is), the moments are flat too, and a step is one streaming kernel per bucket (``svol_adamw_flat``:
+    28 bytes per parameter) instead of torch's multi-tensor launches over ~150 separate tensors (0.44 ms -> 0.15 ms at the
+    benchmark size).  Parameters the reducer skips (they never receive a gradient) are not touched, as in torch.
+
+    It IS a ``torch.optim.Optimizer``: one ``param_groups`` entry whose ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` the step
+    reads (so ``StepLR`` / ``MultiStepLR`` of the reference loop, train.py:127-130, wrap it), and ``state_dict()`` /
+    ``load_state_dict()`` speak torch AdamW's schema — ``{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups':
+    [...]}`` with ``i`` indexing ``params`` — so a checkpoint written by the reference (train.py:267-284) resumes here and vice
+    versa.  ``params``: the optimizer's parameter list in the REFERENCE's order (train.py:72: every trainable parameter in
+    ``named_parameters()`` order, including the ones that never get a gradient and therefore have no state entry); defaults
+    to the reducer's own parameters in bucket order."""
+
+    _STATE = (('m', 'exp_avg'), ('v', 'exp_avg_sq'))
+    _HYPER = ('lr', 'betas', 'eps', 'weight_decay')
+    _KERNEL = 'svol_adamw_flat'   # + '_zero' (zero_grads) / '_scaled' (loss scaler): the three entries share their argument lists
+
+    def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
+        """zero_grads: the update kernel zeroes each gradient bucket behind its read (``svol_adamw_flat_zero``) and the reducer's next
+        ``zero_grad()`` skips its fill — the reference loop's ``optimizer.zero_grad()`` (train.py:222) folded into ``step()``; for a
+        loop that reads no ``param.grad`` between ``step()`` and ``zero_grad()``.
+        step_in_backward: a bucket's update is issued as soon as its gradients are final (behind its all-reduce at world size > 1),
+        on the reducer's communication stream, instead of all of them in ``step()`` behind the whole backward; ``step()`` then only
+        updates what is left (the last bucket) and closes the step.  Same arithmetic on the same values: the reference has no
+        gradient clipping or any other cross-bucket dependency between backward and the update (train.py:229-234).  NOT for a loop
+        that may skip ``step()`` after ``backward()``; ignored while a loss scaler is attached (its overflow check spans all buckets)."""
+        super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward)
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                    weight_decay=float(weight_decay), amsgrad=False, maximize=False, foreach=None, capturable=False,
+                    differentiable=False, fused=None)
+
+    betas = property(lambda self: self.param_groups[0]['betas'])
+    eps = property(lambda self: self.param_groups[0]['eps'])
+
+    def _launch_bucket(self, b, st, g, t, gscale, stream):
+        from . import _lib
+        from .ops import _ptr
+        name = self._KERNEL + ('_zero' if self.zero_grads else '')
+        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(), float(g['lr']),
+                                       float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), t, gscale,
+                                       stream)
+        _lib.check(rc, name)
+        if self.zero_grads:
+            b['clean'] = True
+
+    def _launch_scaled(self, b, st, g, gmul, sc, stream):
+        from . import _lib
+        from .ops import _ptr
+        name = self._KERNEL + '_scaled'
+        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(), float(g['lr']),
+                                       float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), gmul,
+                                       _ptr(sc.state), stream)
+        _lib.check(rc, name)
 
     def load_state_dict(self, sd):
         if 't' in sd and 'm' in sd:   # round-1 files of this build: flat moments per bucket, layout-dependent
@@ -560,54 +670,93 @@ class FlatAdamW(torch.optim.Optimizer):
             if self._scaler is not None:
                 self._scaler.state[3] = float(self.t)
             return
-        if not self._params_given:
-            # torch's schema maps state to parameters BY POSITION in the optimizer's list (train.py:72: named_parameters() order);
-            # this optimizer was built in bucket (arrival) order, so the moments of the many equal-shaped d x d weights would be
-            # silently permuted
-            raise ValueError('FlatAdamW.load_state_dict: build the optimizer with params=<the parameter list in the order the checkpoint '
-                             'was written with (the reference: every trainable parameter in named_parameters() order)>')
-        groups = sd['param_groups']
-        plist = self.param_groups[0]['params']
-        ids = [i for g in groups for i in g['params']]
-        if len(ids) != len(plist):
-            raise ValueError(f'loaded state dict holds {len(ids)} parameters, the optimizer {len(plist)}')
-        g0 = groups[0]
-        for g in groups[1:]:
-            if any(g.get(k) != g0.get(k) for k in ('lr', 'betas', 'eps', 'weight_decay')):
-                raise ValueError('FlatAdamW keeps one parameter group: the loaded groups differ in their hyper-parameters')
-        if g0.get('amsgrad') or g0.get('maximize'):
-            raise ValueError('amsgrad / maximize are not supported')
-        steps = set()
-        todo = []
-        for pos, i in enumerate(ids):
-            ent = sd['state'].get(i)
-            p = plist[pos]
-            if ent is None:
-                continue
-            if id(p) not in self._slot:
-                raise ValueError(f'parameter {pos} has optimizer state but no gradient bucket here')
-            if ent['exp_avg'].numel() != p.numel() or ent['exp_avg_sq'].numel() != p.numel():
-                raise ValueError(f'parameter {pos}: state of {ent["exp_avg"].numel()} elements for {p.numel()} weights')
-            steps.add(int(float(ent['step'])))
-            todo.append((p, ent))
-        if len(steps) > 1:
-            raise ValueError(f'per-parameter step counts differ ({sorted(steps)}); FlatAdamW keeps one')
-        for st in self.flat:
-            st['m'].zero_()
-            st['v'].zero_()
-        for p, ent in todo:
-            m, v = self._views(p)
-            m.copy_(ent['exp_avg'].reshape(p.shape))
-            v.copy_(ent['exp_avg_sq'].reshape(p.shape))
-        self.t = steps.pop() if steps else 0
-        if self._scaler is not None:
-            self._scaler.state[3] = float(self.t)
-        grp = self.param_groups[0]
-        for k in ('lr', 'eps', 'weight_decay', 'initial_lr'):
-            if k in g0:
-                grp[k] = float(g0[k])
-        if 'betas' in g0:
-            grp['betas'] = (float(g0['betas'][0]), float(g0['betas'][1]))
+        super().load_state_dict(sd)
+
+
+class FlatAdam(FlatAdamW):
+    """torch.optim.Adam (``--optimizer adam``, train.py:96-97: weight decay as coupled L2 — ``wd * p`` joins the gradient before the
+    moments —, amsgrad off) with everything FlatAdamW has: the same flat layout and constructor surface, one ``svol_adam_flat``
+    kernel per bucket (28 bytes per parameter), and torch Adam's checkpoint schema ``{'step', 'exp_avg', 'exp_avg_sq'}``."""
+
+    _KERNEL = 'svol_adam_flat'
+
+    def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
+        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward)
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return dict(FlatAdamW._defaults(lr, betas, eps, weight_decay), decoupled_weight_decay=False)
+
+    def _check_group(self, g0):
+        super()._check_group(g0)
+        if g0.get('decoupled_weight_decay'):
+            raise ValueError('decoupled_weight_decay is AdamW: load this checkpoint into FlatAdamW')
+
+    def load_state_dict(self, sd):
+        _FlatOptimizer.load_state_dict(self, sd)   # (no round-1 flat format: that predates this class)
+
+
+class FlatSGD(_FlatOptimizer):
+    """torch.optim.SGD with momentum (``--optimizer sgd``, train.py:94-95: momentum 0.9, coupled weight decay, dampening 0, nesterov
+    off) over the reducer's flat buckets, with the constructor surface and behaviour of FlatAdamW: one ``svol_sgd_flat`` kernel
+    per bucket (20 bytes per parameter: p, g and the momentum buffer in, p and the buffer out).  The flat momentum buffer starts
+    at zero, which makes the first update torch's ``buf = clone(d)``; ``momentum=0`` is plain SGD.  Checkpoints speak torch SGD's
+    schema: ``{'momentum_buffer'}`` per parameter and no 'step', written once an update has been taken (never at momentum 0, where
+    torch keeps no buffer either)."""
+
+    _STATE = (('buf', 'momentum_buffer'),)
+    _HYPER = ('lr', 'momentum', 'weight_decay')
+    _HAS_STEP = False
+
+    def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, momentum=0.9, weight_decay=0.0,
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
+        """zero_grads, step_in_backward: see FlatAdamW."""
+        defaults = dict(lr=float(lr), momentum=float(momentum), dampening=0, weight_decay=float(weight_decay), nesterov=False,
+                        maximize=False, foreach=None, differentiable=False, fused=None)
+        super().__init__(reducer, defaults, params, zero_grads, step_in_backward)
+
+    momentum = property(lambda self: self.param_groups[0]['momentum'])
+
+    def _launch_bucket(self, b, st, g, t, gscale, stream):
+        from . import _lib
+        from .ops import _ptr
+        name = 'svol_sgd_flat_zero' if self.zero_grads else 'svol_sgd_flat'
+        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['buf']), st['p'].numel(), float(g['lr']),
+                                       float(g['momentum']), float(g['weight_decay']), gscale, stream)
+        _lib.check(rc, name)
+        if self.zero_grads:
+            b['clean'] = True
+
+    def _launch_scaled(self, b, st, g, gmul, sc, stream):
+        from . import _lib
+        from .ops import _ptr
+        rc = _lib.lib().svol_sgd_flat_scaled(_ptr(st['p']), _ptr(b['flat']), _ptr(st['buf']), st['p'].numel(), float(g['lr']),
+                                             float(g['momentum']), float(g['weight_decay']), gmul, _ptr(sc.state), stream)
+        _lib.check(rc, 'svol_sgd_flat_scaled')
+
+    def _has_state(self) -> bool:
+        return self.param_groups[0]['momentum'] != 0 and super()._has_state()
+
+    def _entry_is_empty(self, ent) -> bool:
+        return ent.get('momentum_buffer') is None   # (torch SGD keeps momentum_buffer None before a first update and at momentum 0)
+
+    def _check_group(self, g0):
+        if g0.get('nesterov') or g0.get('maximize') or g0.get('dampening', 0) != 0:
+            raise ValueError('nesterov / dampening / maximize are not supported')
+
+
+def build_optimizer(args, reducer: 'BucketedGradAllReduce', params: Optional[Iterable[torch.nn.Parameter]] = None, **kw):
+    """The optimizer ``args.optimizer`` names, as the reference's train_setup builds it (train.py:94-99: SGD with momentum 0.9, Adam,
+    AdamW, each with ``lr=args.lr, weight_decay=args.wd``), over ``reducer``'s flat buckets.  ``params``: the reference's parameter
+    list (see FlatAdamW); ``kw``: zero_grads / step_in_backward."""
+    if args.optimizer == 'sgd':
+        return FlatSGD(reducer, lr=args.lr, momentum=0.9, weight_decay=args.wd, params=params, **kw)
+    if args.optimizer == 'adam':
+        return FlatAdam(reducer, lr=args.lr, weight_decay=args.wd, params=params, **kw)
+    if args.optimizer == 'adamw':
+        return FlatAdamW(reducer, lr=args.lr, weight_decay=args.wd, params=params, **kw)
+    raise ValueError(f"--optimizer {args.optimizer!r}: choose one of 'sgd', 'adam', 'adamw'")
 
 
 class StepFence:

@@ -1,0 +1,138 @@
+"""Time of one optimizer step on the parameter list of the benchmark model (bench.py's configs[1] head: d = 256, 6 layers, the
+reducer's 16 MiB buckets in arrival order), in ONE process with device events:
+
+    flat AdamW   parallel.FlatAdamW   svol_adamw_flat   28 B / parameter   (the yardstick: the kernel bench.py times)
+    flat Adam    parallel.FlatAdam    svol_adam_flat    28 B / parameter
+    flat SGD     parallel.FlatSGD     svol_sgd_flat     20 B / parameter
+    torch Adam   torch.optim.Adam at its defaults (multi-tensor)
+    torch SGD    torch.optim.SGD(momentum=0.9) otherwise at its defaults
+
+All five read the SAME gradient buffers: the three flat optimizers share one reducer (each keeps flat parameters and state of
+its own; the gradient buckets are the reducer's), the torch optimizers step the same parameters, whose .grad are views into those
+buckets.  Per optimizer: warm-up, then blocks of --block steps between two events, the five taking turns (alternating blocks,
+so that a clock or temperature drift hits all alike), --blocks blocks each = blocks * block timed steps; the whole sequence --reps
+times for the spread.  Achieved bytes/s = bytes per parameter * flat length / time per step, also as a share of the HBM peak
+(MI355X: 8.0 TB/s spec; 6.29 TB/s is what a float4 copy reaches).  After the timed sequence each flat optimizer runs once more,
+untimed, beside bench.py's clock probe: the shader clock the chip held under it.
+
+    python tools/micro/optim_step_bench.py [--block 100] [--blocks 5] [--reps 3] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+HBM_PEAK = 8.0e12       # bytes/s, spec
+HBM_COPY = 6.29e12      # bytes/s, measured float4 copy
+
+
+def shader_clock(dev, opt, steps):
+    """The shader clock the chip holds under `steps` more (untimed) steps of `opt`: bench.py's probe (csrc/clock_probe.hip), one wave on
+    a stream of its own sampling shader-clock ticks against the constant wall counter in 200 us windows."""
+    import ctypes
+    from svol_amd import _lib
+    cap = 8192
+    samples = torch.zeros(2 * cap, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    stop = torch.zeros(1, dtype=torch.int32, device=dev)
+    khz = ctypes.c_int32(0)
+    ps = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().svol_clock_probe(samples.data_ptr(), count.data_ptr(), cap, stop.data_ptr(), 200, 20000, ctypes.byref(khz),
+                                           ps.cuda_stream), 'svol_clock_probe')
+    try:
+        for _ in range(steps):
+            opt.step()
+    finally:
+        stop.fill_(1)            # stream-ordered behind the steps: the probe leaves at its next window
+        torch.cuda.synchronize()
+    n = int(count.item())
+    if n < 8:
+        return None
+    w = samples[:2 * n].view(n, 2).cpu().double()
+    ghz = (w[:, 0] / w[:, 1] * (khz.value / 1e6)).sort().values
+    pick = lambda q: round(float(ghz[min(n - 1, int(q * n))]), 3)
+    return {'p10': pick(0.1), 'median': pick(0.5), 'p90': pick(0.9), 'windows': n, 'window_us': 200}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--block', type=int, default=100)
+    ap.add_argument('--blocks', type=int, default=5)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    assert a.block * a.blocks >= 500, 'at least 500 timed steps per optimizer'
+    from svol_amd import parallel
+    from svol_amd import synthetic as syn
+    from svol_amd.modeling.svanet import build_svanet
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    args = syn.cfg2_args('video_matcher')
+    args.compute_dtype = 'bf16'
+    torch.manual_seed(1)
+    model = build_svanet(args).to(dev).train()
+    params = [p for p in model.parameters() if p.requires_grad]
+    reducer = parallel.BucketedGradAllReduce(parallel.arrival_order(model), skip=parallel.unused_parameters(model), ordered=True)
+    kw = dict(lr=1e-4, weight_decay=1e-4, params=params)
+    opts = {'flat AdamW': parallel.FlatAdamW(reducer, **kw), 'flat Adam': parallel.FlatAdam(reducer, **kw),
+            'flat SGD': parallel.FlatSGD(reducer, momentum=0.9, **kw)}
+    live = [p for b in reducer.buckets for p in b['params']]     # (the torch optimizers skip a parameter without .grad anyway)
+    opts['torch Adam'] = torch.optim.Adam(live, lr=1e-4, weight_decay=1e-4)
+    opts['torch SGD'] = torch.optim.SGD(live, lr=1e-4, momentum=0.9, weight_decay=1e-4)
+    bytes_per = {'flat AdamW': 28, 'flat Adam': 28, 'flat SGD': 20, 'torch Adam': 28, 'torch SGD': 20}   # (torch: the same minimum)
+    n_flat = sum(b['flat'].numel() for b in reducer.buckets)
+    gen = torch.Generator(device=dev).manual_seed(7)
+    for b in reducer.buckets:
+        b['flat'].copy_(torch.randn(b['flat'].numel(), device=dev, generator=gen) * 1e-3)
+    for o in opts.values():
+        for _ in range(a.warmup):
+            o.step()
+    torch.cuda.synchronize()
+    reps = []
+    for _ in range(a.reps):
+        spans = {k: [] for k in opts}
+        for _ in range(a.blocks):
+            for name, o in opts.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.block):
+                    o.step()
+                e1.record()
+                spans[name].append((e0, e1))
+        torch.cuda.synchronize()
+        reps.append({k: sum(e0.elapsed_time(e1) for e0, e1 in v) / (a.block * a.blocks) for k, v in spans.items()})
+    sclk = {k: shader_clock(dev, opts[k], a.block * a.blocks) for k in ('flat AdamW', 'flat Adam', 'flat SGD')}
+    assert all(bool(torch.isfinite(st['p']).all()) for o in list(opts.values())[:3] for st in o.flat)
+    res = {'device': torch.cuda.get_device_name(dev), 'torch': torch.__version__, 'parameters': sum(p.numel() for p in live),
+           'flat_floats': n_flat, 'buckets': len(reducer.buckets), 'steps_per_rep': a.block * a.blocks, 'reps': a.reps,
+           'argv': ' '.join(sys.argv[1:]), 'sclk_ghz': sclk, 'rows': {}}
+    print(f'{res["device"]}: {res["parameters"]} parameters in {res["buckets"]} buckets ({n_flat * 4 / 2 ** 20:.1f} MiB flat), '
+          f'{a.reps} x {a.block * a.blocks} steps each')
+    print(f'{"":12s} {"ms/step (reps)":28s} {"median":>8s} {"spread":>8s} {"B/param":>8s} {"TB/s":>7s} {"of 8.0":>7s} {"of 6.29":>8s}')
+    for k in opts:
+        ms = [r[k] for r in reps]
+        med = statistics.median(ms)
+        bw = bytes_per[k] * n_flat / (med * 1e-3)
+        res['rows'][k] = {'ms_per_step': ms, 'median_ms': med, 'spread_ms': max(ms) - min(ms), 'bytes_per_param': bytes_per[k],
+                          'bytes_per_s': bw, 'share_of_hbm_peak': bw / HBM_PEAK, 'share_of_hbm_copy': bw / HBM_COPY}
+        print(f'{k:12s} {" ".join(f"{x:.4f}" for x in ms):28s} {med:8.4f} {max(ms) - min(ms):8.4f} {bytes_per[k]:8d} {bw / 1e12:7.2f} '
+              f'{bw / HBM_PEAK:7.1%} {bw / HBM_COPY:8.1%}')
+    for k, c in sclk.items():
+        print(f'shader clock under {k}: ' + (f'{c["median"]:.3f} GHz median (p10 {c["p10"]:.3f}, p90 {c["p90"]:.3f}, {c["windows"]} windows '
+                                             f'of {c["window_us"]} us)' if c else 'not sampled'))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
