@@ -117,6 +117,38 @@ int svol_adam_flat_zero(float* p, float* g, float* m, float* v, int64_t n, float
                         float weight_decay, int64_t step, float grad_scale, void* stream);
 int svol_adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, float grad_mul, const float* scaler_state, void* stream);
+/* Global gradient-norm clipping inside the flat optimizers' step: these two entries stand in for torch.nn.utils.clip_grad_norm_
+ * (2-norm, error_if_nonfinite=False) where a DETR-style loop calls it, between backward and optimizer.step() — the place of
+ * train.py:231-234 in the reference's loop, which itself does not clip.  New symbols only, the ABI version is unchanged.  No
+ * allocation, no synchronisation, no floating-point atomics: a fixed grid and a fixed reduction order, so the result for a given
+ * (g, n) is bit-identical from run to run, with and without SVOL_DETERMINISTIC.
+ *
+ * svol_grad_sqnorm: *out = sum of g[i]^2 over one flat fp32 range, 16-byte aligned, read once with 16-byte loads (at most 2048
+ * workgroups, a grid-stride loop above that).  Two launches on `stream`: block partials into ws, then one block that adds them in
+ * index order in double.  The longest chain of fp32 additions is ceil(n / 2^21) + 12 (28 at n = 2^25), so sqrt(*out) is within
+ * 1e-5 relative of the exact norm up to n = 2^27 without further argument.  n == 0 writes 0.  A non-finite element makes the sum
+ * non-finite, and so does a FINITE gradient whose square sum leaves fp32's range (|g| >~ 1e19): torch's norm is inf there too.
+ * ws: svol_grad_sqnorm_ws_bytes(n) bytes, 16-byte aligned, caller-owned, not shared by launches that may run concurrently; it
+ * needs no initialisation.  SVOL_E_INVALID on a null pointer or n < 0, SVOL_E_UNSUPPORTED on a misaligned g or ws.
+ *
+ * svol_grad_clip_state (one thread): from the nb per-range sums sq[0..nb),
+ *   total = sqrt(sum_b sq[b]) * grad_mul / scale        the norm of the TRUE gradient: grad_mul is the pending 1 / world of summed
+ *                                                        buckets, scale the loss scale (scaler_state[0], or loss_scale when
+ *                                                        scaler_state is NULL)
+ *   coef  = min(1, max_norm / (total + 1e-6))            torch's formula; max_norm = inf measures without clipping
+ * and writes state_out, EIGHT floats whose first four have the layout of the scaler state, so that svol_adamw_flat_scaled,
+ * svol_adam_flat_scaled and svol_sgd_flat_scaled take it in place of scaler_state unchanged:
+ *   [0] scale / coef   [1] overflow flag   [2] 0   [3] updates taken so far (scaler_state[3], or steps_taken)
+ *   [4] total, before clipping   [5] coef   [6], [7] 0.
+ * With scaler_state: a non-finite total also sets scaler_state[1], so that the scaled update kernels skip the step and
+ * svol_loss_scaler_update backs the scale off — this replaces the svol_grad_finite pass.  Without: nothing is skipped and a
+ * non-finite total behaves as in torch (total = inf: coef = 0, finite gradients become 0 and infinite ones NaN; total = NaN:
+ * every gradient becomes NaN).  SVOL_E_INVALID on a null sq / state_out, nb < 1, steps_taken < 0, max_norm not > 0, or
+ * loss_scale not > 0 without scaler_state. */
+int64_t svol_grad_sqnorm_ws_bytes(int64_t n);
+int svol_grad_sqnorm(const float* g, int64_t n, float* ws, float* out, void* stream);
+int svol_grad_clip_state(const float* sq, int32_t nb, float grad_mul, float max_norm, float loss_scale, int64_t steps_taken,
+                         float* scaler_state, float* state_out, void* stream);
 
 /* ---- GEMMs (nn.Linear and its backward) --------------------------------- */
 /* C[M,N] = act((A[M,K] * B[N,K]^T + bias[N]) * colscale[N]) + residual[M,N]

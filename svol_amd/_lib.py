@@ -59,6 +59,9 @@ SIGNATURES = {
     'svol_adam_flat': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _p],
     'svol_adam_flat_zero': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _p],
     'svol_adam_flat_scaled': [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _p, _p],
+    'svol_grad_sqnorm_ws_bytes': [_i64],
+    'svol_grad_sqnorm': [_p, _i64, _p, _p, _p],
+    'svol_grad_clip_state': [_p, _i32, _f32, _f32, _f32, _i64, _p, _p, _p],
     'svol_conv_nhwc': [_p, _p, _i64, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_im2col': [_p, _i64, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_maxpool_nhwc': [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
@@ -155,6 +158,7 @@ def lib():
             f.argtypes = at
         L.svol_attn_ws_bytes.restype = _i64
         L.svol_attn_bwd_sp_image_bytes.restype = _i64
+        L.svol_grad_sqnorm_ws_bytes.restype = _i64
         L.svol_block_slot_names.restype = ctypes.c_char_p
         L.svol_block_slot_names.argtypes = [_int]
         _LIB = L

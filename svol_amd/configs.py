@@ -16,7 +16,9 @@ reference command line parses unchanged.  Differences, all additive:
   backbone, train.py:72), with the reference's dead ``--freeze_backbone`` honoured as the opt-out; ``--sync_bn`` is honoured
   by the trainable extractors (global-batch BatchNorm statistics across ranks, train.py:65-68).
   With ``--backbone vit`` only an explicit ``--train_backbone 1`` trains the ViT extractors (the reference's ViT path cannot
-  run as shipped); ``--finetune_layers K`` restricts that to the last K layers and the final LayerNorm.
+  run as shipped); ``--finetune_layers K`` restricts that to the last K layers and the final LayerNorm;
+* ``--clip_max_norm X`` (DETR's name; default 0.0 = off): ``parallel.build_optimizer`` clips the global gradient 2-norm to X inside
+  the flat optimizers' step (the reference's loop does not clip).
 """
 from __future__ import annotations
 
@@ -129,6 +131,8 @@ _EXTRA = [
     (('--finetune_layers',), dict(type=int, default=None,
                                   help='with --backbone vit --train_backbone 1: train only the last K ViT layers and the final '
                                        'LayerNorm (preprocess/sketch_vit_finetune.py); default: every parameter')),
+    (('--clip_max_norm',), dict(type=float, default=0.0,
+                                help='clip the global gradient 2-norm inside the optimizer step (parallel.build_optimizer); 0 = off')),
 ]
 
 

@@ -283,7 +283,9 @@ class BucketedGradAllReduce:
         """Wait for every in-flight bucket and turn sums into means.  Call after backward() — MANDATORY before anything reads
         ``param.grad`` (a gradient-norm log, clipping, a torch optimizer), also at world size 1: the block programs write the gradient
         buckets from the query-half and weight-gradient streams without autograd edges to the parameters, so ``backward()``
-        returning does not order those streams against the caller's; this call does.
+        returning does not order those streams against the caller's; this call does.  (For clipping and the norm with a flat
+        optimizer use its ``max_grad_norm`` / ``grad_norm``: ``clip_grad_norm_`` over ``param.grad`` sees sums over ranks after
+        ``mean=False`` and loss-scaled gradients under a loss scale.)
         mean=False: leave the SUMS in the buckets and remember the factor (``pending_scale`` = 1 / world) for ``FlatAdamW.step()``,
         which applies it inside its one pass over the gradients (no multiply launch per bucket)."""
         if self.on_gpu:
@@ -393,7 +395,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     _HYPER = ()        # hyper-parameter keys of the param group that load_state_dict() takes from a checkpoint
     _HAS_STEP = True   # torch's per-parameter state carries 'step'
 
-    def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool):
+    def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool,
+                 max_grad_norm: Optional[float] = None):
         owned = [p for b in reducer.buckets for p in b['params']]
         plist = list(params) if params is not None else owned
         self._params_given = params is not None
@@ -427,6 +430,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._stepped = [False] * len(self.flat)
         if self.step_in_backward:
             reducer.on_bucket_reduced = self._step_bucket_early
+        self._max_grad_norm: Optional[float] = None
+        self._clip = None   # device buffers of the clipped step, made when clipping is first turned on (_clip_buffers)
+        self.max_grad_norm = max_grad_norm
 
     # With a scaler attached the count of updates really taken lives on the DEVICE (scaler.state[3]: an overflow-skipped step does
     # not advance it, as apex + torch do not advance 'step'); it is the bias-correction step of the Adam family and what checkpoints
@@ -448,6 +454,40 @@ class _FlatOptimizer(torch.optim.Optimizer):
         else:
             self.t = taken
 
+    # Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm, between backward and step: DETR's --clip_max_norm) inside
+    # step(): a setting of the LOOP, as torch's call is — it is not in param_groups and not in checkpoints.  clip_grad_norm_ itself over
+    # the gradient views sees what the buckets HOLD: sums over ranks after finish(mean=False), gradients times the loss scale under
+    # loss_scale / a DynamicLossScaler; the clipped step takes both factors out of the norm on the device.
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        """None: no clipping.  May be set between steps; None or 0 turns clipping off, float('inf') measures the norm (``grad_norm``)
+        without clipping, torch's idiom."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v: Optional[float]):
+        v = None if v is None or float(v) == 0.0 else float(v)
+        if v is not None and not v > 0.0:
+            raise ValueError(f'max_grad_norm must be positive, None or 0 (off), got {v}')
+        self._max_grad_norm = v
+        if v is not None and self._clip is None:
+            self._clip = self._clip_buffers()
+
+    def _clip_buffers(self):
+        from . import _lib
+        dev = self.reducer.buckets[0]['flat'].device
+        ws = [torch.empty(int(_lib.lib().svol_grad_sqnorm_ws_bytes(b['flat'].numel())) // 4, dtype=torch.float32, device=dev)
+              for b in self.reducer.buckets]
+        return {'state': torch.zeros(8, dtype=torch.float32, device=dev),     # include/svol_hip.h, svol_grad_clip_state
+                'sq': torch.zeros(len(ws), dtype=torch.float32, device=dev), 'ws': ws}
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """While clipping is on: a 0-dim fp32 DEVICE tensor (a view of the clip state, no host read) holding the last step's total
+        2-norm of the TRUE gradient — mean over ranks, loss scale divided out, before clipping; inf / NaN on an overflowed step.
+        None while clipping is off."""
+        return self._clip['state'][4] if self._max_grad_norm is not None else None
+
     def steps_taken(self) -> int:
         """Updates really applied (what torch calls 'step'); a host read of the device count when a scaler is attached."""
         return int(self._scaler.state[3].item()) if self._scaler is not None else self.t
@@ -461,8 +501,35 @@ class _FlatOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     def _launch_scaled(self, b, st, g, gmul, sc, stream):
-        """the same under the loss scaler ``sc``: a no-op on an overflowed step, the gradient factor is gmul / scale"""
+        """the same under the loss scaler ``sc`` (anything with a scaler-layout ``state`` tensor: the clipped step passes its clip
+        state): a no-op on an overflowed step, the gradient factor is gmul / state[0]"""
         raise NotImplementedError
+
+    class _State:   # what _launch_scaled reads of a DynamicLossScaler
+        def __init__(self, state):
+            self.state = state
+
+    def _step_clipped(self, g):
+        """step() with max_grad_norm set: one sum-of-squares launch per bucket, one launch that turns the sums into a state vector
+        of the scaler's layout ([0] = scale / coef), then the *_scaled update kernels reading it.  Under a loss scaler the sums double
+        as the overflow check (a non-finite norm), and the step ends with the scaler's update as it does without clipping."""
+        from . import _lib
+        from .ops import _ptr, _stream
+        L, sc, c = _lib.lib(), self._scaler, self._clip
+        gmul = float(self.reducer.pending_scale)
+        self.reducer.pending_scale = 1.0
+        self.t += 1
+        for bi, b in enumerate(self.reducer.buckets):
+            _lib.check(L.svol_grad_sqnorm(_ptr(b['flat']), b['flat'].numel(), _ptr(c['ws'][bi]), c['sq'].data_ptr() + 4 * bi, _stream()),
+                       'svol_grad_sqnorm')
+        _lib.check(L.svol_grad_clip_state(_ptr(c['sq']), len(self.flat), gmul, self._max_grad_norm, float(self.loss_scale), self.t - 1,
+                                          _ptr(sc.state) if sc is not None else None, _ptr(c['state']), _stream()), 'svol_grad_clip_state')
+        view = self._State(c['state'])
+        for b, st in zip(self.reducer.buckets, self.flat):
+            self._launch_scaled(b, st, g, gmul, view, _stream())
+        if sc is not None:
+            _lib.check(L.svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
+                                                 sc.max_scale, _stream()), 'svol_loss_scaler_update')
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -470,6 +537,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         from .ops import _ptr, _stream
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
+        if self._max_grad_norm is not None:
+            self._step_clipped(g)
+            return loss
         if self.scaler is not None:
             # dynamic loss scaling (a static scale with no overflow check lets one inf gradient poison the parameters and the
             # optimizer state for good): the buckets are checked first, every update kernel is a no-op on an overflowed step, then the
@@ -499,8 +569,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _step_bucket_early(self, bi, stream):
         """reducer callback (step_in_backward): bucket ``bi``'s gradients are final and ``stream`` is ordered behind every kernel
         that wrote them or read its parameters in this step."""
-        if self._scaler is not None or self._stepped[bi]:
-            return
+        if self._scaler is not None or self._max_grad_norm is not None or self._stepped[bi]:
+            return   # (the overflow check and the gradient norm span all buckets)
         g = self.param_groups[0]
         world = self.reducer.world
         gscale = (1.0 / world if world > 1 else 1.0) / float(self.loss_scale)
@@ -619,16 +689,25 @@ class FlatAdamW(_FlatOptimizer):
     _KERNEL = 'svol_adamw_flat'   # + '_zero' (zero_grads) / '_scaled' (loss scaler): the three entries share their argument lists
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
+                 max_grad_norm: Optional[float] = None):
         """zero_grads: the update kernel zeroes each gradient bucket behind its read (``svol_adamw_flat_zero``) and the reducer's next
         ``zero_grad()`` skips its fill — the reference loop's ``optimizer.zero_grad()`` (train.py:222) folded into ``step()``; for a
         loop that reads no ``param.grad`` between ``step()`` and ``zero_grad()``.
         step_in_backward: a bucket's update is issued as soon as its gradients are final (behind its all-reduce at world size > 1),
         on the reducer's communication stream, instead of all of them in ``step()`` behind the whole backward; ``step()`` then only
-        updates what is left (the last bucket) and closes the step.  Same arithmetic on the same values: the reference has no
-        gradient clipping or any other cross-bucket dependency between backward and the update (train.py:229-234).  NOT for a loop
-        that may skip ``step()`` after ``backward()``; ignored while a loss scaler is attached (its overflow check spans all buckets)."""
-        super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward)
+        updates what is left (the last bucket) and closes the step.  Same arithmetic on the same values: the reference's loop has no
+        cross-bucket dependency between backward and the update (train.py:229-234).  NOT for a loop that may skip ``step()`` after
+        ``backward()``; ignored while a loss scaler is attached (its overflow check spans all buckets) and while ``max_grad_norm``
+        is set (so does the gradient norm).
+        max_grad_norm: clip the global 2-norm of the gradient inside ``step()`` — ``torch.nn.utils.clip_grad_norm_(params, max_norm)``
+        followed by the update, as a DETR-style loop does (``--clip_max_norm``) — on the norm of the TRUE gradient: the pending
+        ``1 / world`` of ``finish(mean=False)`` and the loss scale are taken out on the device, which a ``clip_grad_norm_`` call over
+        ``param.grad`` cannot do.  One streaming reduction per bucket and a one-thread kernel, no host synchronisation; under a
+        loss scaler the reduction replaces the overflow check.  ``zero_grads`` then behaves as under a scaler: the reducer's own
+        fill runs.  Without a scaler a non-finite norm skips nothing and behaves as in torch (``error_if_nonfinite=False``).  The
+        norm of the last step is ``grad_norm`` (a device tensor).  See the ``max_grad_norm`` property; not part of ``state_dict()``."""
+        super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward, max_grad_norm)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -681,8 +760,9 @@ class FlatAdam(FlatAdamW):
     _KERNEL = 'svol_adam_flat'
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
-        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward)
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
+                 max_grad_norm: Optional[float] = None):
+        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward, max_grad_norm)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -710,11 +790,12 @@ class FlatSGD(_FlatOptimizer):
     _HAS_STEP = False
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, momentum=0.9, weight_decay=0.0,
-                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False):
-        """zero_grads, step_in_backward: see FlatAdamW."""
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
+                 max_grad_norm: Optional[float] = None):
+        """zero_grads, step_in_backward, max_grad_norm: see FlatAdamW."""
         defaults = dict(lr=float(lr), momentum=float(momentum), dampening=0, weight_decay=float(weight_decay), nesterov=False,
                         maximize=False, foreach=None, differentiable=False, fused=None)
-        super().__init__(reducer, defaults, params, zero_grads, step_in_backward)
+        super().__init__(reducer, defaults, params, zero_grads, step_in_backward, max_grad_norm)
 
     momentum = property(lambda self: self.param_groups[0]['momentum'])
 
@@ -749,7 +830,10 @@ class FlatSGD(_FlatOptimizer):
 def build_optimizer(args, reducer: 'BucketedGradAllReduce', params: Optional[Iterable[torch.nn.Parameter]] = None, **kw):
     """The optimizer ``args.optimizer`` names, as the reference's train_setup builds it (train.py:94-99: SGD with momentum 0.9, Adam,
     AdamW, each with ``lr=args.lr, weight_decay=args.wd``), over ``reducer``'s flat buckets.  ``params``: the reference's parameter
-    list (see FlatAdamW); ``kw``: zero_grads / step_in_backward."""
+    list (see FlatAdamW); ``kw``: zero_grads / step_in_backward / max_grad_norm.  ``args.clip_max_norm`` > 0 (DETR's option, configs.py)
+    becomes ``max_grad_norm`` unless ``kw`` names one."""
+    if 'max_grad_norm' not in kw and (getattr(args, 'clip_max_norm', 0) or 0) > 0:
+        kw['max_grad_norm'] = float(args.clip_max_norm)
     if args.optimizer == 'sgd':
         return FlatSGD(reducer, lr=args.lr, momentum=0.9, weight_decay=args.wd, params=params, **kw)
     if args.optimizer == 'adam':

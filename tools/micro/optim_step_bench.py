@@ -16,6 +16,15 @@ times for the spread.  Achieved bytes/s = bytes per parameter * flat length / ti
 untimed, beside bench.py's clock probe: the shader clock the chip held under it.
 
     python tools/micro/optim_step_bench.py [--block 100] [--blocks 5] [--reps 3] [--out FILE.json]
+
+--clip times the clipped step instead (max_grad_norm, parallel.py), same protocol, five other rows on the same gradient buffers:
+
+    (a) flat AdamW                       the row above
+    (b) flat AdamW + scaler              svol_grad_finite per bucket + svol_adamw_flat_scaled + svol_loss_scaler_update: the launch
+                                         structure of the clipped step, 32 B / parameter
+    (c) clipped AdamW                    svol_grad_sqnorm per bucket + svol_grad_clip_state + svol_adamw_flat_scaled
+    (d) clipped AdamW + scaler           (c) + svol_loss_scaler_update
+    (e) clip_grad_norm_ + flat AdamW     torch.nn.utils.clip_grad_norm_ over the gradient views, then (a)
 """
 import argparse
 import json
@@ -67,6 +76,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--clip', action='store_true', help='time the clipped step: rows (a) to (e) of the module docstring')
     a = ap.parse_args()
     assert a.block * a.blocks >= 500, 'at least 500 timed steps per optimizer'
     from svol_amd import parallel
@@ -81,12 +91,35 @@ def main():
     params = [p for p in model.parameters() if p.requires_grad]
     reducer = parallel.BucketedGradAllReduce(parallel.arrival_order(model), skip=parallel.unused_parameters(model), ordered=True)
     kw = dict(lr=1e-4, weight_decay=1e-4, params=params)
-    opts = {'flat AdamW': parallel.FlatAdamW(reducer, **kw), 'flat Adam': parallel.FlatAdam(reducer, **kw),
-            'flat SGD': parallel.FlatSGD(reducer, momentum=0.9, **kw)}
     live = [p for b in reducer.buckets for p in b['params']]     # (the torch optimizers skip a parameter without .grad anyway)
-    opts['torch Adam'] = torch.optim.Adam(live, lr=1e-4, weight_decay=1e-4)
-    opts['torch SGD'] = torch.optim.SGD(live, lr=1e-4, momentum=0.9, weight_decay=1e-4)
-    bytes_per = {'flat AdamW': 28, 'flat Adam': 28, 'flat SGD': 20, 'torch Adam': 28, 'torch SGD': 20}   # (torch: the same minimum)
+    if a.clip:
+        # the gradients below have norm 1e-3 * sqrt(19.1e6) = 4.4: max_grad_norm 1 clips every step.  The scalers never grow
+        # (growth_interval past the run), so (b) and (d) do the same work every step.
+        scaler = lambda: parallel.DynamicLossScaler(dev, init_scale=1.0, growth_interval=10 ** 9)
+        opts = {'(a) flat AdamW': parallel.FlatAdamW(reducer, **kw), '(b) flat AdamW + scaler': parallel.FlatAdamW(reducer, **kw),
+                '(c) clipped AdamW': parallel.FlatAdamW(reducer, max_grad_norm=1.0, **kw),
+                '(d) clipped AdamW + scaler': parallel.FlatAdamW(reducer, max_grad_norm=1.0, **kw)}
+        opts['(b) flat AdamW + scaler'].scaler = scaler()
+        opts['(d) clipped AdamW + scaler'].scaler = scaler()
+
+        class ClipThenStep:     # what INTEGRATION.md used to advise: ~150 gradient views through torch's multi-tensor norm and scale
+            def __init__(self, opt):
+                self.flat = opt.flat
+                self.opt = opt
+
+            def step(self):
+                torch.nn.utils.clip_grad_norm_(live, 1.0)
+                self.opt.step()
+        opts['(e) clip_grad_norm_ + flat AdamW'] = ClipThenStep(parallel.FlatAdamW(reducer, **kw))
+        bytes_per = {k: 28 if k.startswith('(a)') else 32 for k in opts}   # one more read of the gradient ((e): the same minimum)
+        probed = list(opts)[:4]
+    else:
+        opts = {'flat AdamW': parallel.FlatAdamW(reducer, **kw), 'flat Adam': parallel.FlatAdam(reducer, **kw),
+                'flat SGD': parallel.FlatSGD(reducer, momentum=0.9, **kw)}
+        opts['torch Adam'] = torch.optim.Adam(live, lr=1e-4, weight_decay=1e-4)
+        opts['torch SGD'] = torch.optim.SGD(live, lr=1e-4, momentum=0.9, weight_decay=1e-4)
+        bytes_per = {'flat AdamW': 28, 'flat Adam': 28, 'flat SGD': 20, 'torch Adam': 28, 'torch SGD': 20}   # (torch: the same minimum)
+        probed = ['flat AdamW', 'flat Adam', 'flat SGD']
     n_flat = sum(b['flat'].numel() for b in reducer.buckets)
     gen = torch.Generator(device=dev).manual_seed(7)
     for b in reducer.buckets:
@@ -108,21 +141,25 @@ def main():
                 spans[name].append((e0, e1))
         torch.cuda.synchronize()
         reps.append({k: sum(e0.elapsed_time(e1) for e0, e1 in v) / (a.block * a.blocks) for k, v in spans.items()})
-    sclk = {k: shader_clock(dev, opts[k], a.block * a.blocks) for k in ('flat AdamW', 'flat Adam', 'flat SGD')}
-    assert all(bool(torch.isfinite(st['p']).all()) for o in list(opts.values())[:3] for st in o.flat)
+    sclk = {k: shader_clock(dev, opts[k], a.block * a.blocks) for k in probed}
+    assert all(bool(torch.isfinite(st['p']).all()) for o in opts.values() if hasattr(o, 'flat') for st in o.flat)
+    if a.clip:
+        norms = {k: float(o.grad_norm) for k, o in opts.items() if getattr(o, 'grad_norm', None) is not None}
+        print('grad_norm after the run:', norms)
     res = {'device': torch.cuda.get_device_name(dev), 'torch': torch.__version__, 'parameters': sum(p.numel() for p in live),
            'flat_floats': n_flat, 'buckets': len(reducer.buckets), 'steps_per_rep': a.block * a.blocks, 'reps': a.reps,
            'argv': ' '.join(sys.argv[1:]), 'sclk_ghz': sclk, 'rows': {}}
     print(f'{res["device"]}: {res["parameters"]} parameters in {res["buckets"]} buckets ({n_flat * 4 / 2 ** 20:.1f} MiB flat), '
           f'{a.reps} x {a.block * a.blocks} steps each')
-    print(f'{"":12s} {"ms/step (reps)":28s} {"median":>8s} {"spread":>8s} {"B/param":>8s} {"TB/s":>7s} {"of 8.0":>7s} {"of 6.29":>8s}')
+    wid = max(12, max(len(k) for k in opts))
+    print(f'{"":{wid}s} {"ms/step (reps)":28s} {"median":>8s} {"spread":>8s} {"B/param":>8s} {"TB/s":>7s} {"of 8.0":>7s} {"of 6.29":>8s}')
     for k in opts:
         ms = [r[k] for r in reps]
         med = statistics.median(ms)
         bw = bytes_per[k] * n_flat / (med * 1e-3)
         res['rows'][k] = {'ms_per_step': ms, 'median_ms': med, 'spread_ms': max(ms) - min(ms), 'bytes_per_param': bytes_per[k],
                           'bytes_per_s': bw, 'share_of_hbm_peak': bw / HBM_PEAK, 'share_of_hbm_copy': bw / HBM_COPY}
-        print(f'{k:12s} {" ".join(f"{x:.4f}" for x in ms):28s} {med:8.4f} {max(ms) - min(ms):8.4f} {bytes_per[k]:8d} {bw / 1e12:7.2f} '
+        print(f'{k:{wid}s} {" ".join(f"{x:.4f}" for x in ms):28s} {med:8.4f} {max(ms) - min(ms):8.4f} {bytes_per[k]:8d} {bw / 1e12:7.2f} '
               f'{bw / HBM_PEAK:7.1%} {bw / HBM_COPY:8.1%}')
     for k, c in sclk.items():
         print(f'shader clock under {k}: ' + (f'{c["median"]:.3f} GHz median (p10 {c["p10"]:.3f}, p90 {c["p90"]:.3f}, {c["windows"]} windows '
