@@ -71,7 +71,8 @@ int svol_cast_transpose_multi(const void* descs, int32_t n_desc, int64_t total_t
  * LayerNorm do not average it out, profiles/round2_bf16_output_error.md), so those products use both halves. */
 int svol_cast_split(const float* src, int64_t ld_src, void* dst_hilo, int64_t R, int64_t C, void* stream);
 
-/* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, amsgrad / maximize off — the reference's optimizer,
+/* The flat optimizers and the loss scaler (csrc/optim.hip; gradient-norm clipping: csrc/gradnorm.hip).
+ * One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, amsgrad / maximize off — the reference's optimizer,
  * train.py:98-99) over a FLAT fp32 range of parameters p with gradients g and moment buffers m, v, all 16-byte aligned:
  *   g' = g * grad_scale;  p *= 1 - lr*wd;  m += (g' - m)(1 - b1);  v = b2*v + (1 - b2) g'^2;
  *   p -= lr/(1 - b1^step) * m / (sqrt(v)/sqrt(1 - b2^step) + eps).          step counts from 1. */

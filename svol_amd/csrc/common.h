@@ -103,6 +103,7 @@ template <> struct H16<f16_t> {
     } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+__device__ __forceinline__ bool nonfinite(float x) { return !(fabsf(x) <= 3.0e38f); }   // inf or NaN
 
 // SVOL_DETERMINISTIC=1 (read once): every reduction that normally meets its partial sums through floating-point atomics in ARRIVAL
 // order takes a form with ONE adder per output element instead — the row-loop kernels (LayerNorm / gate backward, column sums) store

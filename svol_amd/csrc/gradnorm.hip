@@ -1,6 +1,6 @@
 // Global gradient-norm clipping for the flat optimizers (stands in for torch.nn.utils.clip_grad_norm_ between backward() and step(),
 // the place of train.py:231-234 in the reference's loop): the sum of squares of one flat fp32 gradient range, and the one-thread
-// kernel that turns the per-bucket sums into the state vector the *_flat_scaled update kernels read (norm.hip, optim.hip).
+// kernel that turns the per-bucket sums into the state vector the *_flat_scaled update kernels read (optim.hip).
 // No floating-point atomics anywhere: a fixed grid, a fixed reduction order, the same bits in every run.
 #include "common.h"
 
@@ -66,7 +66,7 @@ __global__ void grad_clip_state_kernel(const float* __restrict__ sq, int nb, flo
     const float coef = c > 1.f ? 1.f : c;             // torch's clamp(max=1): a NaN stays a NaN
     float flag = 0.f;
     if (scaler_state) {
-        if (!(fabsf(total) <= 3.0e38f)) scaler_state[1] = 1.f;   // inf or NaN: svol_loss_scaler_update backs the scale off
+        if (nonfinite(total)) scaler_state[1] = 1.f;   // svol_loss_scaler_update backs the scale off
         flag = scaler_state[1];
     }
     state_out[0] = scale / coef;

@@ -1,14 +1,26 @@
-// SGD with momentum and Adam with coupled L2 over a flat fp32 range: the reference's other two --optimizer choices
-// (train.py:94-97: torch.optim.SGD(lr, momentum=0.9, weight_decay=wd), torch.optim.Adam(lr, weight_decay=wd)); AdamW is in norm.hip.
-// HBM-bound streaming passes shaped like adamw_flat_kernel: 4 parameters per thread (16-byte accesses), thread n/4 takes the n % 4
-// tail, every array read once and written once.  SGD moves 20 bytes per parameter (p, g, buf in; p, buf out), Adam 28; ZERO adds 4.
+// The flat optimizers' update kernels and the dynamic loss scaler (parallel._FlatOptimizer, parallel.DynamicLossScaler): the
+// reference's three --optimizer choices (train.py:94-99: torch.optim.SGD(lr, momentum=0.9, weight_decay=wd), torch.optim.Adam and
+// torch.optim.AdamW(lr, weight_decay=wd)) over a flat, 16-byte aligned fp32 range of parameters p with gradients g and one (SGD: the
+// momentum buffer) or two (Adam, AdamW: exp_avg, exp_avg_sq) state arrays.  Each rule's per-element arithmetic is written once
+// (sgd_update, adam_update<DECOUPLED>: AdamW is Adam with decoupled weight decay), and each family has one kernel, an HBM-bound
+// streaming pass: 4 parameters per thread (16-byte accesses), thread n / 4 takes the n % 4 tail, every array read once and written
+// once.  SGD moves 20 bytes per parameter, Adam and AdamW 28; ZERO adds 4.
+//   ZERO:   the gradient range is zeroed behind its read (optimizer.zero_grad() of the next iteration, train.py:222, folded into the
+//           step: the step boundary loses the caller's fill launches).
+//   SCALED: the update reads a state vector of four floats on the device: [0] loss scale, [1] overflow flag of the current step
+//           (0 / 1), [2] clean steps since the last change of the scale, [3] optimizer steps really taken.  Nothing is written when
+//           [1] is set (an overflowed step is skipped whole: parameters and state keep their values), the gradient is multiplied by
+//           gscale / [0], and Adam's bias-correction step is [3] + 1.  The vector is a DynamicLossScaler's state (svol_grad_finite
+//           sets [1], svol_loss_scaler_update moves [0], [2], [3] and clears [1]: no host synchronisation anywhere) or the clip state
+//           of svol_grad_clip_state (gradnorm.hip), whose first four floats have this layout.
+// Where a constant is computed decides its bits: the plain entries take Adam's step_size and 1 / sqrt(bc2) from the host in double
+// and AdamW's decay = 1 - lr * wd in host float, the SCALED ones compute all three on the device in float.
+// The two kernels stay separate functions with scalar parameters on purpose: which product of a sum the compiler contracts into an
+// fma depends on how the body reaches the kernel, and a body shared through a rule type or a further inlined function made
+// another choice in the SGD and Adam updates (other result bits).
 #include "common.h"
 
 namespace {
-
-// ZERO:   the gradient range is zeroed behind its read (optimizer.zero_grad() of the next iteration folded into the step).
-// SCALED: dynamic loss scaling, the contract of adamw_flat_scaled_kernel (norm.hip) — nothing is written when state[1] is set,
-//         the gradient is multiplied by gscale / state[0], Adam's bias-correction step is state[3] + 1.
 
 __device__ __forceinline__ void sgd_update(float& p, float g, float& buf, float lr, float mom, float wd, float gscale) {
     const float d = g * gscale + wd * p;   // grad.add(param, alpha=weight_decay)
@@ -47,23 +59,33 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, fl
     }
 }
 
-__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float wd, float b1, float b2, float step_size,
+// DECOUPLED: AdamW's param.mul_(1 - lr * weight_decay) in place of Adam's grad.add(param, alpha=weight_decay).  A compile-time choice,
+// not a zero coefficient: 0 * inf must not enter either rule's gradient.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float wd, float decay, float b1, float b2, float step_size,
                                             float inv_bc2_sqrt, float eps, float gscale) {
-    const float gr = g * gscale + wd * p;            // grad.add(param, alpha=weight_decay): coupled L2, no p *= 1 - lr*wd
+    float gr;
+    if constexpr (DECOUPLED) {
+        gr = g * gscale;
+        p *= decay;
+    } else {
+        gr = g * gscale + wd * p;
+    }
     m = m + (gr - m) * (1.f - b1);                   // exp_avg.lerp_(grad, 1 - beta1)
     v = v * b2 + (1.f - b2) * gr * gr;               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     p -= step_size * (m / (sqrtf(v) * inv_bc2_sqrt + eps));
 }
 
-template <bool ZERO, bool SCALED>
+template <bool DECOUPLED, bool ZERO, bool SCALED>
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, int64_t n4, int64_t n, float lr, float wd, float b1, float b2,
                                                         float step_size, float inv_bc2_sqrt, float eps, float gscale,
-                                                        const float* __restrict__ state) {
+                                                        const float* __restrict__ state, float decay) {
     if constexpr (SCALED) {
         if (state[1] != 0.f) return;
         gscale = gscale / state[0];
         const float step = state[3] + 1.f;
+        if constexpr (DECOUPLED) decay = 1.f - lr * wd;
         step_size = lr / (1.f - powf(b1, step));
         inv_bc2_sqrt = 1.f / sqrtf(1.f - powf(b2, step));
     }
@@ -74,7 +96,7 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, f
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float pe = pp[e], me = mm[e], ve = vv[e];
-            adam_update(pe, gg[e], me, ve, wd, b1, b2, step_size, inv_bc2_sqrt, eps, gscale);
+            adam_update<DECOUPLED>(pe, gg[e], me, ve, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, gscale);
             pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
@@ -84,51 +106,82 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, f
     } else if (i == n4) {
         for (int64_t j = 4 * n4; j < n; ++j) {
             float pj = p[j], mj = m[j], vj = v[j];
-            adam_update(pj, g[j], mj, vj, wd, b1, b2, step_size, inv_bc2_sqrt, eps, gscale);
+            adam_update<DECOUPLED>(pj, g[j], mj, vj, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, gscale);
             p[j] = pj; m[j] = mj; v[j] = vj;
             if constexpr (ZERO) g[j] = 0.f;
         }
     }
 }
 
-// one thread per 4 parameters plus the tail thread; 0 when the grid would not fit
-inline unsigned flat_blocks(int64_t n) {
-    const int64_t blocks = (n / 4 + 1 + 255) / 256;
-    return blocks >= (1ll << 31) ? 0u : (unsigned)blocks;
+// What every launch checks first: SVOL_E_INVALID on a null array, n < 0 or !args_ok, SVOL_E_UNSUPPORTED on an array off a 16-byte
+// boundary or a grid that would not fit; blocks: one thread per 4 parameters plus the tail thread, 0 (with SVOL_OK) when n == 0.
+template <class... P>
+int flat_grid(int64_t n, bool args_ok, unsigned& blocks, const P*... arrays) {
+    blocks = 0;
+    if ((... || !arrays) || n < 0 || !args_ok) return SVOL_E_INVALID;
+    if (n == 0) return SVOL_OK;
+    if ((... || !aligned16(arrays))) return SVOL_E_UNSUPPORTED;
+    const int64_t b = (n / 4 + 1 + 255) / 256;
+    if (b >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
+    blocks = (unsigned)b;
+    return SVOL_OK;
 }
 
+// (g: only the ZERO kernels write it, and their entries take it non-const)
 template <bool ZERO, bool SCALED>
-int sgd_flat_launch(float* p, float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
+int sgd_flat_launch(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
                     const float* state, void* stream) {
-    if (!p || !g || !buf || n < 0 || (SCALED && !state)) return SVOL_E_INVALID;
-    if (n == 0) return SVOL_OK;
-    if (!aligned16(p) || !aligned16(g) || !aligned16(buf)) return SVOL_E_UNSUPPORTED;
-    const unsigned blocks = flat_blocks(n);
-    if (!blocks) return SVOL_E_UNSUPPORTED;
-    hipLaunchKernelGGL((sgd_flat_kernel<ZERO, SCALED>), dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, buf, n / 4, n,
-                       lr, momentum, weight_decay, grad_scale, state);
+    unsigned blocks;
+    const int rc = flat_grid(n, !SCALED || state, blocks, p, g, buf);
+    if (!blocks) return rc;
+    hipLaunchKernelGGL((sgd_flat_kernel<ZERO, SCALED>), dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+                       const_cast<float*>(g), buf, n / 4, n, lr, momentum, weight_decay, grad_scale, state);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
 
-template <bool ZERO, bool SCALED>
-int adam_flat_launch(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int64_t step, float grad_scale, const float* state, void* stream) {
-    if (!p || !g || !m || !v || n < 0 || (SCALED ? !state : step <= 0)) return SVOL_E_INVALID;
-    if (n == 0) return SVOL_OK;
-    if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return SVOL_E_UNSUPPORTED;
-    const unsigned blocks = flat_blocks(n);
-    if (!blocks) return SVOL_E_UNSUPPORTED;
+template <bool DECOUPLED, bool ZERO, bool SCALED>
+int adam_flat_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t step, float grad_scale, const float* state, void* stream) {
+    unsigned blocks;
+    const int rc = flat_grid(n, SCALED ? state != nullptr : step > 0, blocks, p, g, m, v);
+    if (!blocks) return rc;
     float step_size = 0.f, inv_bc2_sqrt = 0.f;
-    if (!SCALED) {   // bias corrections in double on the host, as adamw_flat_launch computes them
+    if (!SCALED) {   // the plain entries' constants: bias corrections in double; decay in float, below
         const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
         step_size = (float)((double)lr / bc1);
         inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
     }
-    hipLaunchKernelGGL((adam_flat_kernel<ZERO, SCALED>), dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n / 4, n,
-                       lr, weight_decay, beta1, beta2, step_size, inv_bc2_sqrt, eps, grad_scale, state);
+    hipLaunchKernelGGL((adam_flat_kernel<DECOUPLED, ZERO, SCALED>), dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+                       const_cast<float*>(g), m, v, n / 4, n, lr, weight_decay, beta1, beta2, step_size, inv_bc2_sqrt, eps, grad_scale, state,
+                       1.f - lr * weight_decay);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
+}
+
+__global__ __launch_bounds__(256) void grad_finite_kernel(const float* __restrict__ g, int64_t n4, int64_t n, float* __restrict__ state) {
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(g + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bad |= nonfinite(v[e]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t j = 4 * n4; j < n; ++j) bad |= nonfinite(g[j]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) state[1] = 1.f;   // (benign race: every writer stores the same value)
+}
+
+__global__ void loss_scaler_update_kernel(float* state, float growth, float backoff, float interval, float min_scale, float max_scale) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (state[1] != 0.f) {
+        state[0] = fmaxf(state[0] * backoff, min_scale);
+        state[2] = 0.f;
+    } else {
+        state[3] += 1.f;
+        state[2] += 1.f;
+        if (state[2] >= interval) { state[0] = fminf(state[0] * growth, max_scale); state[2] = 0.f; }
+    }
+    state[1] = 0.f;
 }
 
 }  // namespace
@@ -137,7 +190,7 @@ extern "C" {
 
 int svol_sgd_flat(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
                   void* stream) {
-    return sgd_flat_launch<false, false>(p, const_cast<float*>(g), buf, n, lr, momentum, weight_decay, grad_scale, nullptr, stream);
+    return sgd_flat_launch<false, false>(p, g, buf, n, lr, momentum, weight_decay, grad_scale, nullptr, stream);
 }
 int svol_sgd_flat_zero(float* p, float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
                        void* stream) {
@@ -145,22 +198,54 @@ int svol_sgd_flat_zero(float* p, float* g, float* buf, int64_t n, float lr, floa
 }
 int svol_sgd_flat_scaled(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_mul,
                          const float* scaler_state, void* stream) {
-    return sgd_flat_launch<false, true>(p, const_cast<float*>(g), buf, n, lr, momentum, weight_decay, grad_mul, scaler_state, stream);
+    return sgd_flat_launch<false, true>(p, g, buf, n, lr, momentum, weight_decay, grad_mul, scaler_state, stream);
 }
 
 int svol_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t step, float grad_scale, void* stream) {
-    return adam_flat_launch<false, false>(p, const_cast<float*>(g), m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr,
-                                          stream);
+    return adam_flat_launch<false, false, false>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
 }
 int svol_adam_flat_zero(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int64_t step, float grad_scale, void* stream) {
-    return adam_flat_launch<true, false>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
+    return adam_flat_launch<false, true, false>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
 }
 int svol_adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, float grad_mul, const float* scaler_state, void* stream) {
-    return adam_flat_launch<false, true>(p, const_cast<float*>(g), m, v, n, lr, beta1, beta2, eps, weight_decay, 1, grad_mul, scaler_state,
-                                         stream);
+    return adam_flat_launch<false, false, true>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 0, grad_mul, scaler_state, stream);
+}
+
+int svol_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int64_t step, float grad_scale, void* stream) {
+    return adam_flat_launch<true, false, false>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
+}
+int svol_adamw_flat_zero(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int64_t step, float grad_scale, void* stream) {
+    return adam_flat_launch<true, true, false>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
+}
+int svol_adamw_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, float grad_mul, const float* scaler_state, void* stream) {
+    return adam_flat_launch<true, false, true>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 0, grad_mul, scaler_state, stream);
+}
+
+int svol_grad_finite(const float* g, int64_t n, float* scaler_state, void* stream) {
+    if (!g || !scaler_state || n < 0) return SVOL_E_INVALID;
+    if (n == 0) return SVOL_OK;
+    if (!aligned16(g)) return SVOL_E_UNSUPPORTED;
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(grad_finite_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, n4, n, scaler_state);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+int svol_loss_scaler_update(float* scaler_state, float growth_factor, float backoff_factor, int64_t growth_interval, float min_scale,
+                            float max_scale, void* stream) {
+    if (!scaler_state || growth_factor < 1.f || backoff_factor <= 0.f || backoff_factor > 1.f || growth_interval < 1) return SVOL_E_INVALID;
+    hipLaunchKernelGGL(loss_scaler_update_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scaler_state, growth_factor,
+                       backoff_factor, (float)growth_interval, min_scale, max_scale);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
 }
 
 }  // extern "C"

@@ -28,6 +28,9 @@ from typing import Iterable, List, Optional
 import torch
 import torch.distributed as dist
 
+from . import _lib, ops   # (neither loads the kernel library at import)
+from .ops import _ptr, _stream
+
 _LATE = ('query_embed', 'input_', 'backbone', 'pos_embed', 'position_embedding')   # first used in forward = last in backward
 _GATE = ('sketch_video_cross_attn',)   # the gate-vector algebra of every layer runs ahead of the layer loop (cross_modal_transformer.py):
                                        # its backward is the last thing the transformer does, just before the input projections'
@@ -121,13 +124,12 @@ class BucketedGradAllReduce:
         # the stream the caller computes on (the video half of the model, the criterion, the optimizer); re-read
         # at every zero_grad() on the caller's thread — hooks run on the autograd thread under the NODE's stream
         self.main_stream = torch.cuda.current_stream(self.device) if self.on_gpu else None
-        from .ops import GradSink
         for bi, b in enumerate(self.buckets):
             for p in b['params']:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(bi)))
                 # the svol kernels accumulate weight / bias / LayerNorm gradients straight into the bucket view
                 # (svol_amd.ops "gradient sinks"); the hook above still fires for them
-                p._svol_sink = GradSink(p.grad, self, bi)
+                p._svol_sink = ops.GradSink(p.grad, self, bi)
 
     def _make_bucket(self, params):
         # every tensor starts on a 16-byte boundary (the kernels take 16-byte vector accesses on gradients and — FlatAdamW —
@@ -140,7 +142,8 @@ class BucketedGradAllReduce:
         for p, off in zip(params, offs):
             assert p.dtype == torch.float32, 'master parameters are fp32'
             p.grad = flat[off:off + p.numel()].view_as(p)  # autograd accumulates in place into the view
-        self.buckets.append({'params': params, 'offsets': offs, 'flat': flat, 'pending': len(params), 'n': len(params)})
+        self.buckets.append({'index': len(self.buckets), 'params': params, 'offsets': offs, 'flat': flat, 'pending': len(params),
+                             'n': len(params)})
 
     def _make_hook(self, bi):
         def hook(_p):
@@ -170,7 +173,6 @@ class BucketedGradAllReduce:
         """every stream a gradient of a bucket can have been written on: the caller's compute stream (video half,
         heads, input projections), the model's side stream (query half: gradient-sink kernels and AccumulateGrad nodes
         created under ``torch.cuda.stream(side)``), and the stream of the node whose hook is running."""
-        from . import ops
         from .modeling import cross_modal_transformer as cmt
         ss = ([self.main_stream, torch.cuda.current_stream(self.device)] + list(cmt.side_streams(self.device)) +
               list(ops.wgrad_streams(self.device)))   # weight-gradient GEMMs run on a stream of their own (ops.gemm_tn_sink)
@@ -194,7 +196,6 @@ class BucketedGradAllReduce:
             # By the time the last hook of a bucket fires every producing kernel of the bucket has been ENQUEUED on
             # its stream (autograd issues nodes in order on the host), so waiting on all producer streams here is
             # sufficient.
-            from . import ops
             ops.flush_wgrad()   # weight-gradient GEMMs still queued on the host (ops.gemm_tn_sink) may belong to this bucket
             for s in self._producer_streams():
                 self.comm_stream.wait_stream(s)
@@ -209,11 +210,11 @@ class BucketedGradAllReduce:
                 if self.record_spans:
                     h.wait()       # (stream-side wait: orders the communication stream behind the collective, does not block the host)
                     e1.record(self.comm_stream)
-                    self.spans.append((next(i for i, x in enumerate(self.buckets) if x is b), e0, e1))
+                    self.spans.append((b['index'], e0, e1))
                 if early:          # the bucket's optimizer update right behind its exchange, on the communication stream
                     h.wait()
                     self._early_any = True
-                    self.on_bucket_reduced(next(i for i, x in enumerate(self.buckets) if x is b), self.comm_stream.cuda_stream)
+                    self.on_bucket_reduced(b['index'], self.comm_stream.cuda_stream)
         else:
             h = dist.all_reduce(b['flat'], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         self._handles.append((h, b))
@@ -223,14 +224,11 @@ class BucketedGradAllReduce:
         stream behind every producer stream's work so far.  Weight-gradient launches still QUEUED on the host (ops: deferred to
         the next large attention backward) belong in front of it: the update joins that queue behind them, so the deferral keeps its
         schedule and the update lands beside the attention backward — an issue-bound launch that leaves the memory side idle."""
-        from . import ops
-        bi = next(i for i, x in enumerate(self.buckets) if x is b)
-
         def issue():
             for s in self._producer_streams():
                 self.comm_stream.wait_stream(s)
             self._early_any = True
-            self.on_bucket_reduced(bi, self.comm_stream.cuda_stream)
+            self.on_bucket_reduced(b['index'], self.comm_stream.cuda_stream)
 
         if ops._WGRAD_PENDING:
             ops._WGRAD_PENDING.append(issue)
@@ -262,7 +260,6 @@ class BucketedGradAllReduce:
         """Zero the flat buckets (replaces optimizer.zero_grad(); keeps the grad views alive)."""
         if self.on_gpu:
             self.main_stream = torch.cuda.current_stream(self.device)
-            from . import ops
             ops.drop_pending_wgrad()   # weight-gradient launches a failed backward left queued must not land in the zeroed buckets
         self.fire_order = []
         self.spans = []
@@ -291,7 +288,6 @@ class BucketedGradAllReduce:
         if self.on_gpu:
             # kernels that accumulate straight into the buckets (gradient sinks) may have run on the model's side
             # stream (query-stream / video-stream overlap): join it before anyone reads the buckets
-            from . import ops
             from .modeling import cross_modal_transformer as cmt
             ops.flush_wgrad()
             for s in list(cmt.side_streams(self.device)) + list(ops.wgrad_streams(self.device)):
@@ -388,12 +384,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
     """What FlatAdamW, FlatAdam and FlatSGD share: the parameters of every reducer bucket re-homed into one flat fp32 buffer
     (``param.data`` becomes a view, like ``param.grad`` already is) with flat state buffers beside it, one update kernel per bucket,
     the gradient mean's ``1 / world`` and the loss scale riding that kernel, ``zero_grads`` / ``step_in_backward``, the dynamic loss
-    scaler, and checkpoints in the schema of the torch optimizer of the same name.  A subclass names its state buffers (``_STATE``),
-    the hyper-parameters a checkpoint carries (``_HYPER``), and launches its kernels (``_launch_bucket``, ``_launch_scaled``)."""
+    scaler, and checkpoints in the schema of the torch optimizer of the same name.  A subclass names its kernels (``_KERNEL``), its
+    state buffers (``_STATE``), the hyper-parameters a checkpoint carries (``_HYPER``) and the ones its kernels take (``_hyper``)."""
 
-    _STATE = ()        # (key in self.flat[i], key in torch's per-parameter state) per flat state buffer
+    _KERNEL = ''       # the plain C entry; + '_zero' (zero_grads) / '_scaled' (state vector): the three share their leading arguments
+    _STATE = ()        # (key in self.flat[i], key in torch's per-parameter state) per flat state buffer, in the entries' order
     _HYPER = ()        # hyper-parameter keys of the param group that load_state_dict() takes from a checkpoint
-    _HAS_STEP = True   # torch's per-parameter state carries 'step'
+    _HAS_STEP = True   # torch's per-parameter state carries 'step', and the plain entries take a step count
+
+    @staticmethod
+    def _hyper(g) -> tuple:
+        """the hyper-parameters of param group ``g`` in the order the C entries take them"""
+        raise NotImplementedError
 
     def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool,
                  max_grad_norm: Optional[float] = None):
@@ -474,7 +476,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._clip = self._clip_buffers()
 
     def _clip_buffers(self):
-        from . import _lib
         dev = self.reducer.buckets[0]['flat'].device
         ws = [torch.empty(int(_lib.lib().svol_grad_sqnorm_ws_bytes(b['flat'].numel())) // 4, dtype=torch.float32, device=dev)
               for b in self.reducer.buckets]
@@ -496,73 +497,61 @@ class _FlatOptimizer(torch.optim.Optimizer):
     lr = property(lambda self: self.param_groups[0]['lr'], lambda self, v: self.param_groups[0].__setitem__('lr', float(v)))
     weight_decay = property(lambda self: self.param_groups[0]['weight_decay'])
 
-    def _launch_bucket(self, b, st, g, t, gscale, stream):
-        """one bucket's update with step count ``t`` and gradient factor ``gscale`` on ``stream`` (the zeroing kernel under zero_grads)"""
-        raise NotImplementedError
+    def _launch(self, bi, stream, gscale, t=None, state=None):
+        """Bucket ``bi``'s update on ``stream``.  ``state`` None: the plain entry (the zeroing one under zero_grads) with step count
+        ``t`` and gradient factor ``gscale``.  ``state`` a device vector of the scaler's layout (a DynamicLossScaler's, or the clip
+        state): the _scaled entry, a no-op on an overflowed step, whose gradient factor is gscale / state[0]."""
+        b, st = self.reducer.buckets[bi], self.flat[bi]
+        zero = state is None and self.zero_grads
+        name = self._KERNEL + ('_scaled' if state is not None else '_zero' if zero else '')
+        tail = (gscale, _ptr(state)) if state is not None else ((t,) if self._HAS_STEP else ()) + (gscale,)
+        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), *(_ptr(st[k]) for k, _ in self._STATE), st['p'].numel(),
+                                       *self._hyper(self.param_groups[0]), *tail, stream)
+        _lib.check(rc, name)
+        if zero:
+            b['clean'] = True
 
-    def _launch_scaled(self, b, st, g, gmul, sc, stream):
-        """the same under the loss scaler ``sc`` (anything with a scaler-layout ``state`` tensor: the clipped step passes its clip
-        state): a no-op on an overflowed step, the gradient factor is gmul / state[0]"""
-        raise NotImplementedError
-
-    class _State:   # what _launch_scaled reads of a DynamicLossScaler
-        def __init__(self, state):
-            self.state = state
-
-    def _step_clipped(self, g):
-        """step() with max_grad_norm set: one sum-of-squares launch per bucket, one launch that turns the sums into a state vector
-        of the scaler's layout ([0] = scale / coef), then the *_scaled update kernels reading it.  Under a loss scaler the sums double
-        as the overflow check (a non-finite norm), and the step ends with the scaler's update as it does without clipping."""
-        from . import _lib
-        from .ops import _ptr, _stream
+    def _clip_state(self, gmul, stream):
+        """max_grad_norm set: one sum-of-squares launch per bucket, then one launch that turns the sums into a state vector of the
+        scaler's layout ([0] = scale / coef) for the *_scaled update kernels.  Under a loss scaler the sums double as the overflow
+        check (a non-finite norm)."""
         L, sc, c = _lib.lib(), self._scaler, self._clip
-        gmul = float(self.reducer.pending_scale)
-        self.reducer.pending_scale = 1.0
-        self.t += 1
         for bi, b in enumerate(self.reducer.buckets):
-            _lib.check(L.svol_grad_sqnorm(_ptr(b['flat']), b['flat'].numel(), _ptr(c['ws'][bi]), c['sq'].data_ptr() + 4 * bi, _stream()),
+            _lib.check(L.svol_grad_sqnorm(_ptr(b['flat']), b['flat'].numel(), _ptr(c['ws'][bi]), c['sq'].data_ptr() + 4 * bi, stream),
                        'svol_grad_sqnorm')
         _lib.check(L.svol_grad_clip_state(_ptr(c['sq']), len(self.flat), gmul, self._max_grad_norm, float(self.loss_scale), self.t - 1,
-                                          _ptr(sc.state) if sc is not None else None, _ptr(c['state']), _stream()), 'svol_grad_clip_state')
-        view = self._State(c['state'])
-        for b, st in zip(self.reducer.buckets, self.flat):
-            self._launch_scaled(b, st, g, gmul, view, _stream())
-        if sc is not None:
-            _lib.check(L.svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
-                                                 sc.max_scale, _stream()), 'svol_loss_scaler_update')
+                                          _ptr(sc.state) if sc is not None else None, _ptr(c['state']), stream), 'svol_grad_clip_state')
+        return c['state']
 
     @torch.no_grad()
     def step(self, closure=None):
-        from . import _lib
-        from .ops import _ptr, _stream
         loss = closure() if closure is not None else None
-        g = self.param_groups[0]
-        if self._max_grad_norm is not None:
-            self._step_clipped(g)
+        L, sc, stream, buckets = _lib.lib(), self._scaler, _stream(), range(len(self.flat))
+        gmul = float(self.reducer.pending_scale)
+        self.reducer.pending_scale = 1.0
+        self.t += 1    # (host-side count of step() calls; under a scaler the DEVICE counts the steps really taken)
+        if self._max_grad_norm is None and sc is None:
+            gscale = gmul / float(self.loss_scale)
+            for bi in buckets:
+                if self._stepped[bi]:      # updated during backward (_step_bucket_early), with this step's count
+                    self._stepped[bi] = False
+                else:
+                    self._launch(bi, stream, gscale, t=self.t)
             return loss
-        if self.scaler is not None:
+        if self._max_grad_norm is not None:
+            state = self._clip_state(gmul, stream)
+        else:
             # dynamic loss scaling (ADVICE r3: a static scale with no overflow check lets one inf gradient poison the parameters and the
             # optimizer state for good): the buckets are checked first, every update kernel is a no-op on an overflowed step, then the
             # scale moves
-            sc = self.scaler
-            gmul = float(self.reducer.pending_scale)
-            self.reducer.pending_scale = 1.0
-            self.t += 1    # (host-side count of step() calls; the DEVICE counts the steps really taken)
             for b in self.reducer.buckets:
-                _lib.check(_lib.lib().svol_grad_finite(_ptr(b['flat']), b['flat'].numel(), _ptr(sc.state), _stream()), 'svol_grad_finite')
-            for b, st in zip(self.reducer.buckets, self.flat):
-                self._launch_scaled(b, st, g, gmul, sc, _stream())
-            _lib.check(_lib.lib().svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval,
-                                                          sc.min_scale, sc.max_scale, _stream()), 'svol_loss_scaler_update')
-            return loss
-        self.t += 1
-        gscale = float(self.reducer.pending_scale) / float(self.loss_scale)
-        self.reducer.pending_scale = 1.0
-        for bi, (b, st) in enumerate(zip(self.reducer.buckets, self.flat)):
-            if self._stepped[bi]:      # updated during backward (_step_bucket_early), with this step's count
-                self._stepped[bi] = False
-                continue
-            self._launch_bucket(b, st, g, self.t, gscale, _stream())
+                _lib.check(L.svol_grad_finite(_ptr(b['flat']), b['flat'].numel(), _ptr(sc.state), stream), 'svol_grad_finite')
+            state = sc.state
+        for bi in buckets:
+            self._launch(bi, stream, gmul, state=state)
+        if sc is not None:
+            _lib.check(L.svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
+                                                 sc.max_scale, stream), 'svol_loss_scaler_update')
         return loss
 
     @torch.no_grad()
@@ -571,10 +560,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         that wrote them or read its parameters in this step."""
         if self._scaler is not None or self._max_grad_norm is not None or self._stepped[bi]:
             return   # (the overflow check and the gradient norm span all buckets)
-        g = self.param_groups[0]
         world = self.reducer.world
-        gscale = (1.0 / world if world > 1 else 1.0) / float(self.loss_scale)
-        self._launch_bucket(self.reducer.buckets[bi], self.flat[bi], g, self.t + 1, gscale, stream)
+        self._launch(bi, stream, (1.0 / world if world > 1 else 1.0) / float(self.loss_scale), t=self.t + 1)
         self._stepped[bi] = True
 
     def zero_grad(self, set_to_none=False):
@@ -686,7 +673,7 @@ class FlatAdamW(_FlatOptimizer):
 
     _STATE = (('m', 'exp_avg'), ('v', 'exp_avg_sq'))
     _HYPER = ('lr', 'betas', 'eps', 'weight_decay')
-    _KERNEL = 'svol_adamw_flat'   # + '_zero' (zero_grads) / '_scaled' (loss scaler): the three entries share their argument lists
+    _KERNEL = 'svol_adamw_flat'
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
@@ -718,25 +705,9 @@ class FlatAdamW(_FlatOptimizer):
     betas = property(lambda self: self.param_groups[0]['betas'])
     eps = property(lambda self: self.param_groups[0]['eps'])
 
-    def _launch_bucket(self, b, st, g, t, gscale, stream):
-        from . import _lib
-        from .ops import _ptr
-        name = self._KERNEL + ('_zero' if self.zero_grads else '')
-        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(), float(g['lr']),
-                                       float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), t, gscale,
-                                       stream)
-        _lib.check(rc, name)
-        if self.zero_grads:
-            b['clean'] = True
-
-    def _launch_scaled(self, b, st, g, gmul, sc, stream):
-        from . import _lib
-        from .ops import _ptr
-        name = self._KERNEL + '_scaled'
-        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['m']), _ptr(st['v']), st['p'].numel(), float(g['lr']),
-                                       float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), gmul,
-                                       _ptr(sc.state), stream)
-        _lib.check(rc, name)
+    @staticmethod
+    def _hyper(g):
+        return float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay'])
 
     def load_state_dict(self, sd):
         if 't' in sd and 'm' in sd:   # round-1 files of this build: flat moments per bucket, layout-dependent
@@ -786,6 +757,7 @@ class FlatSGD(_FlatOptimizer):
     torch keeps no buffer either)."""
 
     _STATE = (('buf', 'momentum_buffer'),)
+    _KERNEL = 'svol_sgd_flat'
     _HYPER = ('lr', 'momentum', 'weight_decay')
     _HAS_STEP = False
 
@@ -799,22 +771,9 @@ class FlatSGD(_FlatOptimizer):
 
     momentum = property(lambda self: self.param_groups[0]['momentum'])
 
-    def _launch_bucket(self, b, st, g, t, gscale, stream):
-        from . import _lib
-        from .ops import _ptr
-        name = 'svol_sgd_flat_zero' if self.zero_grads else 'svol_sgd_flat'
-        rc = getattr(_lib.lib(), name)(_ptr(st['p']), _ptr(b['flat']), _ptr(st['buf']), st['p'].numel(), float(g['lr']),
-                                       float(g['momentum']), float(g['weight_decay']), gscale, stream)
-        _lib.check(rc, name)
-        if self.zero_grads:
-            b['clean'] = True
-
-    def _launch_scaled(self, b, st, g, gmul, sc, stream):
-        from . import _lib
-        from .ops import _ptr
-        rc = _lib.lib().svol_sgd_flat_scaled(_ptr(st['p']), _ptr(b['flat']), _ptr(st['buf']), st['p'].numel(), float(g['lr']),
-                                             float(g['momentum']), float(g['weight_decay']), gmul, _ptr(sc.state), stream)
-        _lib.check(rc, 'svol_sgd_flat_scaled')
+    @staticmethod
+    def _hyper(g):
+        return float(g['lr']), float(g['momentum']), float(g['weight_decay'])
 
     def _has_state(self) -> bool:
         return self.param_groups[0]['momentum'] != 0 and super()._has_state()

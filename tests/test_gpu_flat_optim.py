@@ -193,7 +193,7 @@ def test_update_kernels_stay_inside_their_ranges(n):
         ar.check(f'{name} n={n}')
         return t
 
-    for base in ('svol_sgd_flat', 'svol_adam_flat'):
+    for base in ('svol_sgd_flat', 'svol_adam_flat', 'svol_adamw_flat'):
         plain, zero, scaled, skipped = run(base), run(base + '_zero'), run(base + '_scaled'), run(base + '_scaled', overflow=True)
         keys = ('p', 'a') if 'sgd' in base else ('p', 'a', 'b')
         assert all(torch.equal(plain[k], zero[k]) for k in keys)
@@ -204,6 +204,8 @@ def test_update_kernels_stay_inside_their_ranges(n):
             _close(scaled[k], plain[k], 2e-6, f'{base}_scaled {k}')
         p, g, a, b = (src[k].double() for k in ('p', 'g', 'a', 'b'))
         d = g + 0.05 * p
+        if 'adamw' in base:     # decoupled decay: the parameter shrinks, the bare gradient feeds the moments
+            p, d = p * (1 - 3e-3 * 0.05), g
         if 'sgd' in base:
             want = {'a': 0.9 * a + d}
             want['p'] = p - 3e-3 * want['a']
