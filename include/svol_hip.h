@@ -429,7 +429,11 @@ int svol_lsap_solve(const double* cost, int64_t nr, int64_t nc, int64_t* rows, i
  * HungarianMatcher.
  * status / box_status (the outputs of svol_lsap_batched / svol_match_cost, layer-major with problems_per_layer entries
  * per layer; either may be NULL): a layer with any non-zero flag gets NaN in its four losses — where the reference
- * raises (scipy ValueError, box_utils AssertionError) this build stays asynchronous but cannot pass for a healthy step. */
+ * raises (scipy ValueError, box_utils AssertionError) this build stays asynchronous but cannot pass for a healthy step;
+ * the flagged layer's unit gradients are NaN as well, the other layers are untouched.
+ * A layer WITHOUT a single match (no target boxes in the batch): the reference cannot express it (torch.stack([]) raises,
+ * loss.py:87); this build defines loss_bbox = loss_giou = class_error = 0 and g_bbox = g_giou = 0 for it, loss_label and
+ * g_label are the all-background cross-entropy (every row weighted eos_coef, mean over B*N). */
 int svol_set_loss(const float* logits, const float* boxes, const float* tgt_boxes, const int32_t* match,
                   float* losses, float* g_label, float* g_bbox, float* g_giou, int32_t n_layers,
                   int32_t rows_per_layer, float eos_coef, const int32_t* rebase_vid_off, int32_t rows_per_video,

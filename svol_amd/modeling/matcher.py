@@ -36,7 +36,9 @@ class PackedTargets:
                     boxes.append(inst['bbox'])
             per_video.append(cnt)
         assert len(targets) == B
-        tgt = torch.stack(boxes).to(torch.float32) if boxes else torch.zeros((0, 4))
+        # a batch without a single box: one unused row, so that the kernels still get a non-NULL pointer (every tgt_cnt is 0:
+        # no problem reads it, nothing is matched) instead of rejecting the launch
+        tgt = torch.stack(boxes).to(torch.float32) if boxes else torch.zeros((1, 4))
         self.per_video = per_video
         self.per_frame = per_frame
         self.matcher = matcher
@@ -157,8 +159,8 @@ class StaticPackedTargets:
         assert tmp.n_problems == self.n_problems and tmp.cost_numel <= self.cost_numel
         self._i32.copy_(torch.stack([tmp.pred_off, tmp.pred_cnt, tmp.tgt_off, tmp.tgt_cnt]), non_blocking=True)
         self.cost_off.copy_(tmp.cost_off, non_blocking=True)
-        nb = tmp.tgt_boxes.shape[0]
-        self.tgt_boxes[:nb].copy_(tmp.tgt_boxes, non_blocking=True)
+        nb = tmp.total_boxes
+        self.tgt_boxes[:nb].copy_(tmp.tgt_boxes[:nb], non_blocking=True)
         if self.rebase_vid_off is not None:
             self.rebase_vid_off.copy_(tmp.rebase_vid_off, non_blocking=True)
         self.vid_off = tmp.vid_off
