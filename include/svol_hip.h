@@ -150,6 +150,38 @@ int64_t svol_grad_sqnorm_ws_bytes(int64_t n);
 int svol_grad_sqnorm(const float* g, int64_t n, float* ws, float* out, void* stream);
 int svol_grad_clip_state(const float* sq, int32_t nb, float grad_mul, float max_norm, float loss_scale, int64_t steps_taken,
                          float* scaler_state, float* state_out, void* stream);
+/* Parameter groups and a capturable step: the three rules with every hyper-parameter and the step count read from DEVICE memory,
+ * per run of the range.  The reference carries the recipe these serve, commented out, at train.py:76-106: backbone parameters in
+ * group 0 at lr * 0.1 (train.py:76-90, 104-105), the rest in group 1 at lr (train.py:106); a launch that bakes no host value is
+ * also what a captured graph needs to follow a scheduler.  New symbols only, the ABI version is unchanged.
+ * One launch over a flat, 16-byte aligned fp32 range p, g, (buf | m, v) of n floats, n % 4 == 0 (every parameter of a gradient
+ * bucket starts on a 16-byte boundary and is padded to one; padding floats stay zero under all three rules).
+ *   seg_end    device int32[nseg], ascending, in units of four floats, the last equal to n / 4: where each RUN ends, a run being
+ *              a maximal stretch of adjacent parameters of one group
+ *   seg_group  device int32[nseg]: each run's group
+ *   hyper      device float[ngroups][8]: lr, beta1 (SGD: momentum), beta2, eps, weight_decay, three spare
+ *   state      device scale state or NULL, the layout the _scaled entries take: the gradient is divided by [0], nothing at all is
+ *              written when [1] is set; a DynamicLossScaler's vector or the clip state of svol_grad_clip_state (whose [3], a host
+ *              value baked at launch, is NOT read).  NULL: no division, never skipped
+ *   step_count device pointer to ONE float, the updates taken so far: Adam's bias-correction step is *step_count + 1.  With a
+ *              scaler &scaler_state[3], else a counter of the caller's that svol_flat_step_advance moves.  (No such argument for SGD.)
+ *   grad_mul   the pending 1 / world;   zero != 0: the gradient range is zeroed behind its read, as the _zero entries do
+ * Per element the arithmetic of the entries above, with step_size, 1 / sqrt(bc2) and AdamW's decay computed on the device in
+ * float as the _scaled entries do.  SVOL_E_INVALID on a null array or table (Adam: or step_count), n < 0, nseg < 1 or
+ * ngroups < 1; SVOL_OK on n == 0; SVOL_E_UNSUPPORTED on a misaligned array, n % 4 != 0 or n >= 2^33.  No allocation, no
+ * synchronisation: capture-safe.  The tables' CONTENTS are the caller's contract; whatever they hold, run and group lookups are
+ * clamped into the tables and no thread touches an array at or beyond n.
+ * svol_flat_step_advance (one thread): if (!state || state[1] == 0) *step_count += 1 — for a caller without a scaler (with one,
+ * svol_loss_scaler_update advances scaler_state[3]). */
+int svol_sgd_flat_grouped(float* p, float* g, float* buf, int64_t n, const int32_t* seg_end, const int32_t* seg_group, int32_t nseg,
+                          const float* hyper, int32_t ngroups, const float* state, float grad_mul, int zero, void* stream);
+int svol_adam_flat_grouped(float* p, float* g, float* m, float* v, int64_t n, const int32_t* seg_end, const int32_t* seg_group,
+                           int32_t nseg, const float* hyper, int32_t ngroups, const float* state, const float* step_count,
+                           float grad_mul, int zero, void* stream);
+int svol_adamw_flat_grouped(float* p, float* g, float* m, float* v, int64_t n, const int32_t* seg_end, const int32_t* seg_group,
+                            int32_t nseg, const float* hyper, int32_t ngroups, const float* state, const float* step_count,
+                            float grad_mul, int zero, void* stream);
+int svol_flat_step_advance(float* step_count, const float* state, void* stream);
 
 /* ---- GEMMs (nn.Linear and its backward) --------------------------------- */
 /* C[M,N] = act((A[M,K] * B[N,K]^T + bias[N]) * colscale[N]) + residual[M,N]

@@ -62,6 +62,10 @@ SIGNATURES = {
     'svol_grad_sqnorm_ws_bytes': [_i64],
     'svol_grad_sqnorm': [_p, _i64, _p, _p, _p],
     'svol_grad_clip_state': [_p, _i32, _f32, _f32, _f32, _i64, _p, _p, _p],
+    'svol_sgd_flat_grouped': [_p, _p, _p, _i64, _p, _p, _i32, _p, _i32, _p, _f32, _int, _p],
+    'svol_adam_flat_grouped': [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _i32, _p, _p, _f32, _int, _p],
+    'svol_adamw_flat_grouped': [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _i32, _p, _p, _f32, _int, _p],
+    'svol_flat_step_advance': [_p, _p, _p],
     'svol_conv_nhwc': [_p, _p, _i64, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_im2col': [_p, _i64, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_maxpool_nhwc': [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],

@@ -22,7 +22,9 @@ from .modeling.matcher import StaticPackedTargets
 class GraphedTrainStep:
     def __init__(self, model, criterion, optimizer, reducer, inputs: dict, targets, max_boxes_per_video: int = 128,
                  warmup: int = 3):
-        """model: SVANet head (training mode), criterion: SetCriterion, optimizer: a CAPTURABLE torch optimizer
+        """model: SVANet head (training mode), criterion: SetCriterion, optimizer: a CAPTURABLE optimizer — a flat optimizer of
+        svol_amd.parallel built with ``capturable=True`` (its step count and hyper-parameters live on the device; a scheduler's
+        edits of ``param_groups`` reach the replays through its ``push_hyper()``, called here before every replay) or a torch one
         (e.g. AdamW(fused=True, capturable=True)), reducer: BucketedGradAllReduce (world size 1)."""
         if reducer.world != 1:
             raise NotImplementedError('graph capture is used for single-process steps; multi-GPU runs stay eager so '
@@ -84,5 +86,7 @@ class GraphedTrainStep:
                 self.static_in[k].copy_(v, non_blocking=True)
         if targets is not None:
             self.packed.load(targets)
+        if hasattr(self.optimizer, 'push_hyper'):
+            self.optimizer.push_hyper()
         self.graph.replay()
         return self.static_loss, self.static_losses

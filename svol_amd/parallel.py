@@ -397,16 +397,34 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """the hyper-parameters of param group ``g`` in the order the C entries take them"""
         raise NotImplementedError
 
+    @staticmethod
+    def _hyper_row(g) -> tuple:
+        """the first five floats of ``g``'s row of the grouped entries' hyper table: lr, beta1 | momentum, beta2, eps, weight_decay"""
+        raise NotImplementedError
+
     def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, capturable: bool = False):
         owned = [p for b in reducer.buckets for p in b['params']]
         plist = list(params) if params is not None else owned
         self._params_given = params is not None
-        known = {id(p) for p in plist}
+        as_dicts = bool(plist) and isinstance(plist[0], dict)
+        if as_dicts:
+            plist = [dict(g, params=list(g['params'])) for g in plist]
+        in_groups = [p for g in plist for p in g['params']] if as_dicts else plist
+        known = {id(p) for p in in_groups}
         missing = [p for p in owned if id(p) not in known]
         if missing:
             raise ValueError(f'{len(missing)} parameter(s) of the gradient buckets are not in `params`')
-        super().__init__(plist, defaults)
+        if as_dicts and len(known) != len(in_groups):
+            raise ValueError('a parameter appears twice in the groups of `params`')
+        super().__init__(plist, defaults)   # (torch's list-of-dicts form too: a group's missing keys are filled from `defaults`)
+        # The grouped path (_step_grouped): more than one param group, or a step that a graph capture may record.  The ..._grouped
+        # entries read every hyper-parameter and the step count from device memory; one group and capturable=False is the plain path.
+        self.capturable = bool(capturable)
+        self._grouped = len(self.param_groups) > 1 or self.capturable
+        if self._grouped and step_in_backward:
+            raise ValueError('step_in_backward launches a bucket\'s update with a host step count: not with several param groups or '
+                             'capturable=True')
         self.reducer = reducer
         self.t = 0
         # the loss was multiplied by this before backward (fp16 operands: gradients of ~1e-6 underflow otherwise); divided back out
@@ -435,6 +453,67 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._max_grad_norm: Optional[float] = None
         self._clip = None   # device buffers of the clipped step, made when clipping is first turned on (_clip_buffers)
         self.max_grad_norm = max_grad_norm
+        if self._grouped:
+            self._build_grouped()
+
+    def _build_grouped(self):
+        """The grouped path's tables, built once.  Per bucket the RUNS of its layout — maximal stretches of adjacent parameters of
+        one group; the reducer laid the buckets out in arrival order before this optimizer existed, so groups alternate as they
+        come — as (ends in units of four floats, group per run): ``seg_tables`` on the host, int32 tensors on the device.  One
+        hyper table, a row of eight floats per group (``_hyper_row``), with a pinned host mirror that ``push_hyper`` uploads from;
+        and the count of updates taken as one device float, which the kernels read unless a scaler owns the count."""
+        dev = self.reducer.buckets[0]['flat'].device
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g['params']}
+        self.seg_tables = []
+        for b in self.reducer.buckets:
+            ends, groups = [], []
+            for p, off in zip(b['params'], b['offsets']):
+                gi, end = group_of[id(p)], (off + (p.numel() + 3) // 4 * 4) // 4
+                if groups and groups[-1] == gi:
+                    ends[-1] = end
+                else:
+                    ends.append(end)
+                    groups.append(gi)
+            assert ends[-1] * 4 == b['flat'].numel()
+            self.seg_tables.append((ends, groups))
+        self._seg_dev = [(torch.tensor(e, dtype=torch.int32, device=dev), torch.tensor(g, dtype=torch.int32, device=dev))
+                         for e, g in self.seg_tables]
+        self._hyper_rows = self._rows()
+        self._hyper_host = torch.tensor(self._hyper_rows, dtype=torch.float32)
+        if dev.type == 'cuda':
+            self._hyper_host = self._hyper_host.pin_memory()
+        self._hyper_dev = self._hyper_host.to(dev)
+        self._hyper_sent = None     # event behind the last upload: the mirror is not rewritten while a copy may still read it
+        self._step_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def _rows(self):
+        return [list(self._hyper_row(g)) + [0.0] * 3 for g in self.param_groups]
+
+    def push_hyper(self):
+        """Grouped path: re-read ``param_groups`` (what a scheduler edits) and, when a value changed, upload the hyper table — an
+        asynchronous copy from the pinned mirror on the current stream, so kernels already enqueued keep the old values.  ``step()``
+        calls it, except while its stream is capturing; around a captured step the caller does (``GraphedTrainStep`` before every
+        replay).  A no-op on the plain path, whose launches take ``param_groups[0]`` as arguments."""
+        if not self._grouped:
+            return
+        rows = self._rows()
+        if rows == self._hyper_rows:
+            return
+        if self._hyper_sent is not None:
+            self._hyper_sent.synchronize()
+        self._hyper_host.copy_(torch.tensor(rows, dtype=torch.float32))
+        self._hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        if self._hyper_dev.is_cuda:
+            self._hyper_sent = torch.cuda.Event()
+            self._hyper_sent.record()
+        self._hyper_rows = rows
+
+    def _sync_count(self):
+        """push the host's count of updates (``self.t``, just loaded or taken over) to where the kernels read it"""
+        if self._scaler is not None:
+            self._scaler.state[3] = float(self.t)
+        elif self._grouped:
+            self._step_dev.fill_(float(self.t))
 
     # With a scaler attached the count of updates really taken lives on the DEVICE (scaler.state[3]: an overflow-skipped step does
     # not advance it, as apex + torch do not advance 'step'); it is the bias-correction step of the Adam family and what checkpoints
@@ -455,6 +534,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             sc.state[3] = float(taken)
         else:
             self.t = taken
+            self._sync_count()
 
     # Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm, between backward and step: DETR's --clip_max_norm) inside
     # step(): a setting of the LOOP, as torch's call is — it is not in param_groups and not in checkpoints.  clip_grad_norm_ itself over
@@ -490,8 +570,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return self._clip['state'][4] if self._max_grad_norm is not None else None
 
     def steps_taken(self) -> int:
-        """Updates really applied (what torch calls 'step'); a host read of the device count when a scaler is attached."""
-        return int(self._scaler.state[3].item()) if self._scaler is not None else self.t
+        """Updates really applied (what torch calls 'step'); a host read of the device count when a scaler is attached and on the
+        grouped path."""
+        if self._scaler is not None:
+            return int(self._scaler.state[3].item())
+        return int(self._step_dev.item()) if self._grouped else self.t
 
     # the hyper-parameters live in param_groups[0] (what torch's schedulers edit); attribute access kept for callers
     lr = property(lambda self: self.param_groups[0]['lr'], lambda self, v: self.param_groups[0].__setitem__('lr', float(v)))
@@ -526,6 +609,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._grouped:
+            self._step_grouped()
+            return loss
         L, sc, stream, buckets = _lib.lib(), self._scaler, _stream(), range(len(self.flat))
         gmul = float(self.reducer.pending_scale)
         self.reducer.pending_scale = 1.0
@@ -554,6 +640,42 @@ class _FlatOptimizer(torch.optim.Optimizer):
                                                  sc.max_scale, stream), 'svol_loss_scaler_update')
         return loss
 
+    def _step_grouped(self):
+        """step() with several param groups or capturable=True: one ..._grouped launch per bucket, which reads its hyper-parameters per
+        run from the device table and Adam's step from the device count, then the count moves (the scaler's update, or
+        svol_flat_step_advance).  Nothing of the launches depends on a host value that changes from step to step, so a captured
+        step replays right: the count advances on the device, and an ``lr`` a scheduler edits arrives through ``push_hyper``."""
+        L, sc, stream = _lib.lib(), self._scaler, _stream()
+        gmul = float(self.reducer.pending_scale)
+        self.reducer.pending_scale = 1.0
+        self.t += 1
+        if not (self._hyper_dev.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self.push_hyper()
+        state = None
+        if self._max_grad_norm is not None:
+            state = self._clip_state(gmul, stream)     # ([3], a host value, is not read by the grouped kernels)
+        elif sc is not None:
+            for b in self.reducer.buckets:
+                _lib.check(L.svol_grad_finite(_ptr(b['flat']), b['flat'].numel(), _ptr(sc.state), stream), 'svol_grad_finite')
+            state = sc.state
+        else:
+            gmul /= float(self.loss_scale)
+        count = sc.state.data_ptr() + 12 if sc is not None else _ptr(self._step_dev)
+        zero = state is None and self.zero_grads   # (a skipped step zeroes nothing: under a state vector the reducer's own fill runs)
+        name = self._KERNEL + '_grouped'
+        for b, st, (ends, groups) in zip(self.reducer.buckets, self.flat, self._seg_dev):
+            rc = getattr(L, name)(_ptr(st['p']), _ptr(b['flat']), *(_ptr(st[k]) for k, _ in self._STATE), st['p'].numel(), _ptr(ends),
+                                  _ptr(groups), ends.numel(), _ptr(self._hyper_dev), len(self.param_groups),
+                                  _ptr(state), *((count,) if self._HAS_STEP else ()), gmul, int(zero), stream)
+            _lib.check(rc, name)
+            if zero:
+                b['clean'] = True
+        if sc is not None:
+            _lib.check(L.svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
+                                                 sc.max_scale, stream), 'svol_loss_scaler_update')
+        else:
+            _lib.check(L.svol_flat_step_advance(_ptr(self._step_dev), _ptr(state), stream), 'svol_flat_step_advance')
+
     @torch.no_grad()
     def _step_bucket_early(self, bi, stream):
         """reducer callback (step_in_backward): bucket ``bi``'s gradients are final and ``stream`` is ordered behind every kernel
@@ -572,26 +694,27 @@ class _FlatOptimizer(torch.optim.Optimizer):
         st = self.flat[bi]
         return tuple(st[k][off:off + n].view_as(p) for k, _ in self._STATE)
 
-    def _has_state(self) -> bool:
-        """torch would hold per-parameter state by now"""
-        return self.steps_taken() > 0   # (not the count of step() calls: overflow-skipped steps are not steps)
-
     def state_dict(self):
         """The schema of the torch optimizer of the same name.  A parameter has a state entry iff it has a slot in a gradient
         bucket and at least one step was taken (torch creates the entry at the first step of a parameter that has a gradient)."""
-        plist = self.param_groups[0]['params']
-        state = {}
-        if self._has_state():
-            taken = self.steps_taken()
-            for i, p in enumerate(plist):
-                if id(p) in self._slot:
+        state, groups, i = {}, [], 0
+        taken = self.steps_taken()   # (not the count of step() calls: overflow-skipped steps are not steps)
+        for g in self.param_groups:   # torch's numbering: positions in the groups' parameter lists, one after the other
+            for j, p in enumerate(g['params']):
+                if taken > 0 and id(p) in self._slot and self._group_keeps_state(g):
                     ent = {'step': torch.tensor(float(taken))} if self._HAS_STEP else {}
                     for (_, name), view in zip(self._STATE, self._views(p)):
                         ent[name] = view.clone()
-                    state[i] = ent
-        group = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
-        group['params'] = list(range(len(plist)))
-        return {'state': state, 'param_groups': [group]}
+                    state[i + j] = ent
+            group = {k: v for k, v in g.items() if k != 'params'}
+            group['params'] = list(range(i, i + len(g['params'])))
+            groups.append(group)
+            i += len(g['params'])
+        return {'state': state, 'param_groups': groups}
+
+    def _group_keeps_state(self, g) -> bool:
+        """torch keeps per-parameter state for the parameters of a group with these hyper-parameters"""
+        return True
 
     def _check_group(self, g0):
         """refuse a checkpoint written with options this optimizer does not implement"""
@@ -611,15 +734,25 @@ class _FlatOptimizer(torch.optim.Optimizer):
             raise ValueError(f'{name}.load_state_dict: build the optimizer with params=<the parameter list in the order the checkpoint '
                              'was written with (the reference: every trainable parameter in named_parameters() order)>')
         groups = sd['param_groups']
-        plist = self.param_groups[0]['params']
+        plist = [p for g in self.param_groups for p in g['params']]
         ids = [i for g in groups for i in g['params']]
         if len(ids) != len(plist):
             raise ValueError(f'loaded state dict holds {len(ids)} parameters, the optimizer {len(plist)}')
-        g0 = groups[0]
-        for g in groups[1:]:
-            if any(g.get(k) != g0.get(k) for k in self._HYPER):
-                raise ValueError(f'{name} keeps one parameter group: the loaded groups differ in their hyper-parameters')
-        self._check_group(g0)
+        if len(self.param_groups) == 1:
+            # built with one group: loaded groups that agree are one group, groups that differ need an optimizer built with them
+            g0 = groups[0]
+            for g in groups[1:]:
+                if any(g.get(k) != g0.get(k) for k in self._HYPER):
+                    raise ValueError(f'{name} was built with one parameter group: the loaded groups differ in their hyper-parameters')
+            loaded = [g0]
+        else:   # torch's rule: the same number of groups, of the same sizes; each group's hyper-parameters come from the file
+            if len(groups) != len(self.param_groups):
+                raise ValueError(f'loaded state dict has {len(groups)} parameter groups, the optimizer {len(self.param_groups)}')
+            if any(len(g['params']) != len(own['params']) for g, own in zip(groups, self.param_groups)):
+                raise ValueError('loaded state dict has parameter groups of other sizes than the optimizer\'s')
+            loaded = groups
+        for g in loaded:
+            self._check_group(g)
         steps = set()
         todo = []
         for pos, i in enumerate(ids):
@@ -648,12 +781,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 view.copy_(ent[k].reshape(p.shape))
         # (a schema without 'step' does not say how many updates were taken; one is enough to know that state exists)
         self.t = (steps.pop() if steps else 0) if self._HAS_STEP else int(bool(todo))
-        if self._scaler is not None:
-            self._scaler.state[3] = float(self.t)
-        grp = self.param_groups[0]
-        for k in self._HYPER + ('initial_lr',):
-            if k in g0:
-                grp[k] = (float(g0[k][0]), float(g0[k][1])) if k == 'betas' else float(g0[k])
+        self._sync_count()
+        for grp, g in zip(self.param_groups, loaded):
+            for k in self._HYPER + ('initial_lr',):
+                if k in g:
+                    grp[k] = (float(g[k][0]), float(g[k][1])) if k == 'betas' else float(g[k])
 
 
 class FlatAdamW(_FlatOptimizer):
@@ -677,7 +809,7 @@ class FlatAdamW(_FlatOptimizer):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, capturable: bool = False):
         """zero_grads: the update kernel zeroes each gradient bucket behind its read (``svol_adamw_flat_zero``) and the reducer's next
         ``zero_grad()`` skips its fill — the reference loop's ``optimizer.zero_grad()`` (train.py:222) folded into ``step()``; for a
         loop that reads no ``param.grad`` between ``step()`` and ``zero_grad()``.
@@ -693,8 +825,20 @@ class FlatAdamW(_FlatOptimizer):
         ``param.grad`` cannot do.  One streaming reduction per bucket and a one-thread kernel, no host synchronisation; under a
         loss scaler the reduction replaces the overflow check.  ``zero_grads`` then behaves as under a scaler: the reducer's own
         fill runs.  Without a scaler a non-finite norm skips nothing and behaves as in torch (``error_if_nonfinite=False``).  The
-        norm of the last step is ``grad_norm`` (a device tensor).  See the ``max_grad_norm`` property; not part of ``state_dict()``."""
-        super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward, max_grad_norm)
+        norm of the last step is ``grad_norm`` (a device tensor).  See the ``max_grad_norm`` property; not part of ``state_dict()``.
+        params as torch's list of dicts (``[{'params': [...], 'lr': ...}, {'params': [...]}]``; a missing key takes the constructor's
+        value, every bucket parameter belongs to exactly one group): several ``param_groups``, each with hyper-parameters of its own —
+        the backbone at a tenth of the head's ``lr`` (``reference_param_groups``), no weight decay on biases and norms — still one
+        launch per bucket: the ``..._grouped`` kernels look the group up per run of the bucket's layout.  Schedulers edit every
+        group; ``lr`` / ``weight_decay`` attribute access means group 0; checkpoints carry the groups in torch's schema and load
+        under torch's rule (the same group count and sizes).  Not with ``step_in_backward``.
+        capturable: the same device-side path with one group too, for a ``step()`` that a graph capture records
+        (``graph.GraphedTrainStep``): the step count lives on the device, and hyper-parameters reach the kernels through
+        ``push_hyper()``, which ``step()`` calls itself except while capturing.  (An attribute of this object, not of the param
+        groups: their ``capturable`` key stays torch's default, so that a checkpoint written here loads into a CPU torch optimizer.)
+        With one group and ``capturable=False`` the step is the plain path, launch for launch what it was."""
+        super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward, max_grad_norm,
+                         capturable)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -709,6 +853,8 @@ class FlatAdamW(_FlatOptimizer):
     def _hyper(g):
         return float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay'])
 
+    _hyper_row = _hyper   # (the table's row order is this family's argument order)
+
     def load_state_dict(self, sd):
         if 't' in sd and 'm' in sd:   # round-1 files of this build: flat moments per bucket, layout-dependent
             if len(sd['m']) != len(self.flat) or any(a.numel() != st['m'].numel() for a, st in zip(sd['m'], self.flat)):
@@ -717,8 +863,7 @@ class FlatAdamW(_FlatOptimizer):
             for st, m, v in zip(self.flat, sd['m'], sd['v']):
                 st['m'].copy_(m)
                 st['v'].copy_(v)
-            if self._scaler is not None:
-                self._scaler.state[3] = float(self.t)
+            self._sync_count()
             return
         super().load_state_dict(sd)
 
@@ -732,8 +877,8 @@ class FlatAdam(FlatAdamW):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None):
-        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward, max_grad_norm)
+                 max_grad_norm: Optional[float] = None, capturable: bool = False):
+        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward, max_grad_norm, capturable)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -763,11 +908,11 @@ class FlatSGD(_FlatOptimizer):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, momentum=0.9, weight_decay=0.0,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None):
-        """zero_grads, step_in_backward, max_grad_norm: see FlatAdamW."""
+                 max_grad_norm: Optional[float] = None, capturable: bool = False):
+        """zero_grads, step_in_backward, max_grad_norm, capturable and the list-of-dicts ``params``: see FlatAdamW."""
         defaults = dict(lr=float(lr), momentum=float(momentum), dampening=0, weight_decay=float(weight_decay), nesterov=False,
                         maximize=False, foreach=None, differentiable=False, fused=None)
-        super().__init__(reducer, defaults, params, zero_grads, step_in_backward, max_grad_norm)
+        super().__init__(reducer, defaults, params, zero_grads, step_in_backward, max_grad_norm, capturable)
 
     momentum = property(lambda self: self.param_groups[0]['momentum'])
 
@@ -775,8 +920,12 @@ class FlatSGD(_FlatOptimizer):
     def _hyper(g):
         return float(g['lr']), float(g['momentum']), float(g['weight_decay'])
 
-    def _has_state(self) -> bool:
-        return self.param_groups[0]['momentum'] != 0 and super()._has_state()
+    @staticmethod
+    def _hyper_row(g):
+        return float(g['lr']), float(g['momentum']), 0.0, 0.0, float(g['weight_decay'])
+
+    def _group_keeps_state(self, g) -> bool:
+        return g['momentum'] != 0
 
     def _entry_is_empty(self, ent) -> bool:
         return ent.get('momentum_buffer') is None   # (torch SGD keeps momentum_buffer None before a first update and at momentum 0)
@@ -786,11 +935,25 @@ class FlatSGD(_FlatOptimizer):
             raise ValueError('nesterov / dampening / maximize are not supported')
 
 
+def reference_param_groups(model: torch.nn.Module, args) -> List[dict]:
+    """The parameter groups of the recipe the reference carries commented out (train.py:76-90, 104-106): group 0 the trainable
+    parameters whose name contains 'backbone' at ``args.lr_backbone`` (the recipe's ``lr * 0.1``; DETR's ``--lr_backbone``), group 1
+    the other trainable parameters at ``args.lr``, each in ``named_parameters()`` order.  One group holding every trainable
+    parameter (train.py:72) when ``lr_backbone`` is None or no backbone parameter is trainable."""
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    lr_backbone = getattr(args, 'lr_backbone', None)
+    backbone = [p for n, p in named if 'backbone' in n]
+    if lr_backbone is None or not backbone:
+        return [{'params': [p for _, p in named]}]
+    return [{'params': backbone, 'lr': float(lr_backbone)}, {'params': [p for n, p in named if 'backbone' not in n], 'lr': float(args.lr)}]
+
+
 def build_optimizer(args, reducer: 'BucketedGradAllReduce', params: Optional[Iterable[torch.nn.Parameter]] = None, **kw):
     """The optimizer ``args.optimizer`` names, as the reference's train_setup builds it (train.py:94-99: SGD with momentum 0.9, Adam,
     AdamW, each with ``lr=args.lr, weight_decay=args.wd``), over ``reducer``'s flat buckets.  ``params``: the reference's parameter
-    list (see FlatAdamW); ``kw``: zero_grads / step_in_backward / max_grad_norm.  ``args.clip_max_norm`` > 0 (DETR's option, configs.py)
-    becomes ``max_grad_norm`` unless ``kw`` names one."""
+    list or torch's list of group dicts, e.g. ``reference_param_groups(model, args)`` (see FlatAdamW); ``kw``: zero_grads /
+    step_in_backward / max_grad_norm / capturable.  ``args.clip_max_norm`` > 0 (DETR's option, configs.py) becomes ``max_grad_norm``
+    unless ``kw`` names one."""
     if 'max_grad_norm' not in kw and (getattr(args, 'clip_max_norm', 0) or 0) > 0:
         kw['max_grad_norm'] = float(args.clip_max_norm)
     if args.optimizer == 'sgd':

@@ -25,6 +25,18 @@ untimed, beside bench.py's clock probe: the shader clock the chip held under it.
     (c) clipped AdamW                    svol_grad_sqnorm per bucket + svol_grad_clip_state + svol_adamw_flat_scaled
     (d) clipped AdamW + scaler           (c) + svol_loss_scaler_update
     (e) clip_grad_norm_ + flat AdamW     torch.nn.utils.clip_grad_norm_ over the gradient views, then (a)
+
+--groups times the grouped / capturable step (svol_adamw_flat_grouped + svol_flat_step_advance, parallel.py), same protocol:
+
+    (a) flat AdamW                       the row above
+    (b) grouped, one group               capturable=True: one run per bucket
+    (c) two groups, contiguous           split by name (what the forward uses first — input projections, embeddings, layer 0 —
+                                         against the rest): the groups are contiguous in the arrival-order buckets, a handful of runs
+    (d) two groups, alternating          weights against biases and norms: the groups alternate parameter by parameter, the
+                                         worst run count
+    (e) torch AdamW fused capturable     torch.optim.AdamW(fused=True, capturable=True): what a captured step uses today
+
+The run count per bucket of (b), (c), (d) is printed and stored with the result.
 """
 import argparse
 import json
@@ -77,7 +89,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--out', default=None)
     ap.add_argument('--clip', action='store_true', help='time the clipped step: rows (a) to (e) of the module docstring')
+    ap.add_argument('--groups', action='store_true', help='time the grouped / capturable step: rows (a) to (e) of the module docstring')
     a = ap.parse_args()
+    assert not (a.clip and a.groups), '--clip or --groups'
     assert a.block * a.blocks >= 500, 'at least 500 timed steps per optimizer'
     from svol_amd import parallel
     from svol_amd import synthetic as syn
@@ -112,6 +126,21 @@ def main():
                 self.opt.step()
         opts['(e) clip_grad_norm_ + flat AdamW'] = ClipThenStep(parallel.FlatAdamW(reducer, **kw))
         bytes_per = {k: 28 if k.startswith('(a)') else 32 for k in opts}   # one more read of the gradient ((e): the same minimum)
+        probed = list(opts)[:4]
+    elif a.groups:
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        late = lambda n: any(t in n for t in parallel._LATE + ('layers.0.',))   # (a boundary inside a bucket, not only between buckets)
+        split = {'(c) two groups, contiguous': [[p for n, p in named if late(n)], [p for n, p in named if not late(n)]],
+                 '(d) two groups, alternating': [[p for _, p in named if p.dim() >= 2], [p for _, p in named if p.dim() < 2]]}
+        assert all(len(g) > 0 for gs in split.values() for g in gs)
+        gkw = dict(lr=1e-4, weight_decay=1e-4)
+        opts = {'(a) flat AdamW': parallel.FlatAdamW(reducer, **kw),
+                '(b) grouped, one group': parallel.FlatAdamW(reducer, capturable=True, **kw)}
+        for k, (g0, g1) in split.items():     # group 1 at 10x the lr and without decay: the rows differ, the work does not
+            opts[k] = parallel.FlatAdamW(reducer, params=[{'params': g0}, {'params': g1, 'lr': 1e-3, 'weight_decay': 0.0}], **gkw)
+        runs = {k: [len(e) for e, _ in o.seg_tables] for k, o in opts.items() if getattr(o, '_grouped', False)}
+        opts['(e) torch AdamW fused capturable'] = torch.optim.AdamW(live, lr=1e-4, weight_decay=1e-4, fused=True, capturable=True)
+        bytes_per = {k: 28 for k in opts}
         probed = list(opts)[:4]
     else:
         opts = {'flat AdamW': parallel.FlatAdamW(reducer, **kw), 'flat Adam': parallel.FlatAdam(reducer, **kw),
@@ -149,6 +178,11 @@ def main():
     res = {'device': torch.cuda.get_device_name(dev), 'torch': torch.__version__, 'parameters': sum(p.numel() for p in live),
            'flat_floats': n_flat, 'buckets': len(reducer.buckets), 'steps_per_rep': a.block * a.blocks, 'reps': a.reps,
            'argv': ' '.join(sys.argv[1:]), 'sclk_ghz': sclk, 'rows': {}}
+    if a.groups:
+        res['runs_per_bucket'] = runs
+        assert all(o.steps_taken() == opts['(a) flat AdamW'].steps_taken() for k, o in opts.items() if k in runs)
+        for k, r in runs.items():
+            print(f'runs per bucket, {k}: {r}')
     print(f'{res["device"]}: {res["parameters"]} parameters in {res["buckets"]} buckets ({n_flat * 4 / 2 ** 20:.1f} MiB flat), '
           f'{a.reps} x {a.block * a.blocks} steps each')
     wid = max(12, max(len(k) for k in opts))
