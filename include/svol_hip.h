@@ -491,6 +491,30 @@ int svol_eval_ap(const double* pred_box, const double* pred_score, const int32_t
                  int32_t n_thresholds, int32_t* ws_order, unsigned char* ws_u8, double* ws_f64, double* ap, int64_t n_pred,
                  int64_t n_gt, int64_t n_groups, void* stream);
 
+/* ---- frame ingest: raw uint8 frames -> backbone inputs (the reference preprocesses on the model path: lib/modeling/backbone.py:31,49
+ * runs ViTFeatureExtractor(images=[frame]) inside ViTBackbone.forward — PIL bilinear resize to 224 x 224, x 1/255, mean / std 0.5 — and
+ * lib/dataset/svol_dataset.py:218-229 runs Resize((224,224)) + ToTensor() per frame for the ResNet path) ------------------------------
+ * Pillow's 8-bit bilinear resample, bit for bit, of n RGB images src[img, y, x, c] (BYTE strides s_n, s_h, s_w; channel stride 1;
+ * rows need no alignment), both passes in one launch, then a table look-up and a strided store:
+ *   t[y, x, c]  = clip8((2^21 + sum_i src[y, xs[x] + i, c] * kx_tab[x, i]) >> 22)     horizontal, rounded to uint8 as Pillow does
+ *   u[y', x, c] = clip8((2^21 + sum_j t[ys[y'] + j, x, c] * ky_tab[y', j]) >> 22)     vertical
+ *   out[img, c, y', flip[img] ? OW-1-x : x] = (out_dtype) lut[c][u[y', x, c]]         ELEMENT strides o_n, o_c, o_h, o_w
+ * xtab [OW, 2 + kx] / ytab [OH, 2 + ky] int32, one row per output index: first source index, tap count (<= k), then k non-negative
+ * taps with 22 fraction bits — Pillow's precompute_coeffs + normalize_coeffs_8bpc (svol_amd.ingest.resample_tables); an axis of
+ * unchanged size has the taps [2^22, 0] and is the identity.  lut [3, 256] fp32: the value written for channel c and byte v (the
+ * whole float stage — /255, mean, std — is this table, so it adds no rounding of its own); flip [n] bytes or NULL: nonzero mirrors that
+ * image's OUTPUT columns.  fp32 NCHW feeds svol_patchify and the fp32 stem; 16-bit NHWC is what svol_im2col takes through its strides
+ * and src_dtype.  Taps outside the image are never read, and nothing outside [src + img s_n + y s_h + 3 x .. + 3) is.
+ * Limits (SVOL_E_UNSUPPORTED outside): kx, ky <= 64 — Pillow's bilinear tables up to a 31-fold downscale per axis, which includes every
+ * OH, OW <= 512 at scales up to 18 (2160 x 3840 -> 224) —, OH, OW <= 16384, H, W <= 2^24, and tables whose windows grow as Pillow's do:
+ * t neighbouring outputs touch at most ceil((t-1) in/out) + k source indices (what the LDS tile is sized by; a table that asks for
+ * more loses taps, it never reads or writes out of bounds).  n == 0 -> SVOL_OK without a launch.  No atomics, no scratch, no
+ * allocation, no synchronisation: capture-safe.  A new symbol only: the ABI version is unchanged. */
+int svol_ingest_resize(const uint8_t* src, int64_t n, int64_t H, int64_t W, int64_t s_n, int64_t s_h, int64_t s_w,
+                       const int32_t* xtab, int64_t kx, const int32_t* ytab, int64_t ky, const float* lut, const uint8_t* flip,
+                       void* out, int64_t o_n, int64_t o_c, int64_t o_h, int64_t o_w, int64_t OH, int64_t OW, int out_dtype,
+                       void* stream);
+
 /* ---- ViT-B/16 feature extractor pieces (the Hugging Face ViTModel the reference's ViT backbone calls,
  * lib/modeling/backbone.py:30,48; inference only) ----------------------------------------------------------------
  * svol_patchify: pixel_values [n,C,H,W] fp32 -> out [n*(H/p)*(W/p), C*p*p] (dtype), the im2col of the stride-p patch

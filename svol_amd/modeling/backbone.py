@@ -41,6 +41,7 @@ import torch
 from torch import nn
 
 from .. import _lib, ops
+from ..ingest import FrameIngest, is_raw_frames
 from ..ops import _DT, _ptr, _stream
 
 
@@ -365,11 +366,18 @@ class ViTExtractor(nn.Module):
 
 
 class ViTBackbone(nn.Module):
-    """backbone.py:11-62 on device: (src_sketch [B,1,C,H,W], src_video [B,T,C,H,W]) -> ([B,1,d], [B,T*P,d])."""
+    """backbone.py:11-62 on device: (src_sketch [B,1,C,H,W], src_video [B,T,C,H,W]) -> ([B,1,d], [B,T*P,d]).
+
+    Raw frames — uint8 [B,T,H,W,3] (sketch [B,1,H,W,3]), or a list of B tensors [T,H_b,W_b,3] of any sizes — first go through the
+    FrameIngest this backbone owns: what ViTFeatureExtractor(images=[frame]) does inside the reference's forward (backbone.py:31,49:
+    PIL bilinear resize to 224 x 224, x 1/255, mean / std 0.5), bit for bit, into the fp32 NCHW pixel_values the extractor takes.
+    ``pixel_preset`` overrides 'vit'.  Float inputs take exactly the path they always took."""
 
     def __init__(self, video_backbone: ViTExtractor, sketch_backbone: ViTExtractor, use_sketch_cls_token: bool = True,
-                 frames_per_launch: int = 512):
+                 frames_per_launch: int = 512, pixel_preset=None):
         super().__init__()
+        s = video_backbone.cfg.image_size
+        self.ingest = FrameIngest((s, s), pixel_preset or 'vit', out='nchw_f32')
         self.video_backbone = video_backbone
         self.sketch_backbone = sketch_backbone
         self.use_sketch_cls_token = use_sketch_cls_token
@@ -378,7 +386,13 @@ class ViTBackbone(nn.Module):
     def forward(self, src_sketch, src_video):
         # gradients flow only where an extractor takes its autograd path (trainable, .train(), grad mode on)
         with torch.set_grad_enabled(self.sketch_backbone.uses_autograd() or self.video_backbone.uses_autograd()):
-            B, T = src_video.shape[:2]
+            B = len(src_video)
+            if is_raw_frames(src_sketch):
+                src_sketch = self.ingest(src_sketch)
+                src_sketch = src_sketch.view(B, -1, *src_sketch.shape[-3:])
+            if is_raw_frames(src_video):
+                src_video = self.ingest(src_video)
+                src_video = src_video.view(B, -1, *src_video.shape[-3:])
             sk = self.sketch_backbone(src_sketch.reshape(-1, *src_sketch.shape[2:]))
             sk = sk[:, :1] if self.use_sketch_cls_token else sk[:, 1:].mean(1, keepdim=True)  # backbone.py:35-38
             frames = src_video.reshape(-1, *src_video.shape[2:])

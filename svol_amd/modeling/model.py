@@ -2,7 +2,8 @@
 
 ``build_model(args)`` / ``SketchLocalizationModel.forward(src_sketch, src_video, src_sketch_mask,
 src_video_mask)`` keep the reference's signatures and the ``backbone.`` / ``head.`` state-dict
-prefixes.  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
+prefixes.  The online extractors also take RAW frames — uint8 ``[B,T,H,W,3]`` / ``[B,1,H,W,3]`` or lists of ``[T,H_b,W_b,3]`` — and
+resize and normalise them on the device (svol_amd/ingest.py; ``args.pixel_preset`` overrides the backbone's preset).  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
 ``--backbone vit`` runs the ViT-B/16 extractor of ``backbone.py`` on the device for every frame and the sketch
 (SURVEY.md §8 f1), frozen unless ``args.train_backbone`` is 1 (``--finetune_layers K``: only the last K layers and the final
 LayerNorm train, as preprocess/sketch_vit_finetune.py does).  Its default stays frozen, unlike the ResNet's: the reference's
@@ -23,6 +24,9 @@ class FeatureBackbone(nn.Module):
     are already features.  Returns (sketch [B,Ls,D], video [B,T*P,D]) like backbone.py:72-89."""
 
     def forward(self, src_sketch, src_video):
+        if isinstance(src_video, (list, tuple)) or src_video.dtype == torch.uint8 or getattr(src_sketch, 'dtype', None) == torch.uint8:
+            raise TypeError("--backbone features takes pre-extracted float features; raw uint8 frames need an online extractor "
+                            "(--backbone resnet / vit), whose FrameIngest resizes and normalises them on the device")
         if src_video.dim() == 4:
             src_video = src_video.flatten(1, 2)
         return src_sketch, src_video
@@ -44,7 +48,7 @@ def build_backbone(args):
         tb = bool(getattr(args, 'train_backbone', None) or False)
         tl = getattr(args, 'finetune_layers', None) if tb else None
         return ViTBackbone(ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl),
-                           ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl))
+                           ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl), pixel_preset=getattr(args, 'pixel_preset', None))
     if 'resnet' in args.backbone:  # backbone.py:133-152: ResNet-34 on the frames (7x7 tokens), ResNet-18 + avgpool on the sketch
         from .resnet import ResNetBackbone, resnet18, resnet34
         args.input_vid_dim = 512
@@ -60,7 +64,8 @@ def build_backbone(args):
         tb = (not bool(getattr(args, 'freeze_backbone', False))) if tb is None else bool(tb)
         sync = bool(getattr(args, 'sync_bn', False))   # train.py:65-68: apex convert_syncbn_model
         return ResNetBackbone(resnet34(compute_dtype=cd, trainable=tb, sync_bn=sync),
-                              resnet18(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync))
+                              resnet18(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync),
+                              pixel_preset=getattr(args, 'pixel_preset', None))
     raise NotImplementedError(f"backbone '{args.backbone}' is not part of the MI355X build (the reference has it commented out)")
 
 
@@ -71,7 +76,8 @@ class SketchLocalizationModel(nn.Module):
         self.head = head
 
     def forward(self, src_sketch, src_video, src_sketch_mask=None, src_video_mask=None):
-        T = src_video.shape[1]
+        # raw uint8 frames may come as a list of B tensors [T, H_b, W_b, 3] (svol_amd/ingest.py): T is then the first one's length
+        T = src_video[0].shape[0] if isinstance(src_video, (list, tuple)) else src_video.shape[1]
         src_sketch, src_video = self.backbone(src_sketch, src_video)
         # per-token masks: one sketch-mask entry per sketch token, one frame-mask entry per patch (model.py:21-22)
         src_sketch_mask = src_sketch_mask.repeat_interleave(src_sketch.shape[1], dim=1)

@@ -31,6 +31,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..ingest import FrameIngest, is_raw_frames
 
 _DTYPES = {'bf16': torch.bfloat16, 'fp32': torch.float32, torch.bfloat16: torch.bfloat16, torch.float32: torch.float32}
 
@@ -147,15 +148,25 @@ class _ConvBnFn(torch.autograd.Function):
         return dx, dW, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, did, None, None, None, None, None
 
 
+def _pixel_geom(pix, nhwc):
+    """(n, c, H, W, element strides (sn, sh, sw, sc)) of the stem's input: NCHW pixels, or the NHWC image FrameIngest writes"""
+    if nhwc:
+        n, H, W, c = pix.shape
+        return n, c, H, W, (H * W * c, W * c, c, 1)
+    n, c, H, W = pix.shape
+    return n, c, H, W, (c * H * W, W, 1, H * W)
+
+
 class _StemFn(torch.autograd.Function):
-    """pixels [n,3,H,W] fp32 -> relu(BatchNorm_train(conv7x7 s2 p3)) as NHWC [n*ho*wo, C]; no gradient for the pixels."""
+    """pixels [n,3,H,W] fp32 (nhwc: [n,H,W,3] in the compute dtype, what FrameIngest writes) -> relu(BatchNorm_train(conv7x7 s2 p3)) as
+    NHWC [n*ho*wo, C]; no gradient for the pixels."""
 
     @staticmethod
-    def forward(ctx, pix, weight, gamma, beta, bn, dt, sync=False):
-        n, c, H, W = pix.shape
+    def forward(ctx, pix, weight, gamma, beta, bn, dt, sync=False, nhwc=False):
+        n, c, H, W, strides = _pixel_geom(pix, nhwc)
         w16 = _w16(weight, dt)
         kh, kw = weight.shape[2], weight.shape[3]
-        cols, Ho, Wo = ops.im2col(pix, n, H, W, c, kh, kw, 2, 3, dt, strides=(c * H * W, W, 1, H * W), ldcols=w16.shape[1])
+        cols, Ho, Wo = ops.im2col(pix, n, H, W, c, kh, kw, 2, 3, dt, strides=strides, ldcols=w16.shape[1])
         z = ops.gemm_nt(cols, w16)
         y, mean, rstd = _bn_forward(z, bn, gamma, beta, None, True, sync)
         ctx.sync = sync
@@ -169,10 +180,10 @@ class _StemFn(torch.autograd.Function):
     def backward(ctx, dy):
         cols, weight, z, y, mean, rstd, gamma = ctx.saved_tensors
         if not any(ctx.needs_input_grad[1:4]):   # a frozen stem: the pixels take no gradient either, nothing to compute
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         dz, _, dgamma, dbeta = ops.bn_bwd(dy.contiguous(), y, z, mean, rstd, gamma, False, ctx.sync)
         dW = _weight_grad(dz, lambda: ops.gemm_tn(dz, cols), weight, ctx.sink, (cols, dz)) if ctx.needs_input_grad[1] else None
-        return None, dW, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, None, None, None
+        return None, dW, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, None, None, None, None
 
 
 class _MaxPoolFn(torch.autograd.Function):
@@ -243,30 +254,35 @@ class ResNetExtractor(nn.Module):
         self._folded = f
         return f
 
-    def forward(self, pixel_values):
+    def forward(self, pixel_values, nhwc=False):
         """pixel_values [n,3,H,W] fp32 (normalised as for torchvision's ImageNet weights) -> tokens [n, h*w, C] in the compute
-        dtype (row-major over (h, w): the order backbone.py:85-87 flattens to), or [n, C] fp32 with ``avgpool``."""
+        dtype (row-major over (h, w): the order backbone.py:85-87 flattens to), or [n, C] fp32 with ``avgpool``.
+        ``nhwc=True``: pixel_values is [n,H,W,3], contiguous, already in the compute dtype — what FrameIngest(out='nhwc_bf16') writes;
+        the stem reads it through svol_im2col's strides, and its im2col matrix has the bits of the fp32 route (one rounding to bf16
+        either way)."""
         if not pixel_values.is_cuda:
             raise RuntimeError('svol_amd ResNetExtractor runs on the MI355X HIP kernels only (no CPU path)')
+        if nhwc and (pixel_values.dtype != self.compute_dtype or not pixel_values.is_contiguous()):
+            raise ValueError(f'nhwc pixels must be contiguous {self.compute_dtype}, got {pixel_values.dtype}')
         if self.training and self.trainable:
-            return self._forward_train(pixel_values)
+            return self._forward_train(pixel_values, nhwc)
         if self.training and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError('parameters that require gradients need ResNetExtractor(trainable=True): the frozen path folds '
                                       'the running statistics into the weights and has no backward')
         with torch.no_grad():
-            return self._forward_frozen(pixel_values)
+            return self._forward_frozen(pixel_values, nhwc)
 
-    def _forward_train(self, pixel_values):
+    def _forward_train(self, pixel_values, nhwc=False):
         """batch-statistics BatchNorm, autograd through every unit (module docstring); folded weights are invalidated."""
         dt = self.compute_dtype
         if dt != torch.bfloat16:
             raise NotImplementedError('the training path of the ResNet extractor keeps its activations in bf16 (compute_dtype="bf16")')
         self._folded = None
-        x = pixel_values.float().contiguous()
-        n, c, H, W = x.shape
+        x = pixel_values if nhwc else pixel_values.float().contiguous()
+        n, c, H, W, _ = _pixel_geom(x, nhwc)
         conv0, bn0 = getattr(self, '0'), getattr(self, '1')
         sync = self.sync_bn
-        y = _StemFn.apply(x, conv0.weight, bn0.weight, bn0.bias, bn0, dt, sync)
+        y = _StemFn.apply(x, conv0.weight, bn0.weight, bn0.bias, bn0, dt, sync, nhwc)
         H, W, C = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1, conv0.out_channels
         y = _MaxPoolFn.apply(y, (n, H, W, C, 3, 2, 1))
         H, W = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
@@ -285,13 +301,13 @@ class ResNetExtractor(nn.Module):
             return _AvgPoolFn.apply(y, n, H * W, C)
         return y.view(n, H * W, C)
 
-    def _forward_frozen(self, pixel_values):
+    def _forward_frozen(self, pixel_values, nhwc=False):
         dt = self.compute_dtype
         f = self._folded or self.refold()
-        x = pixel_values.float().contiguous()
-        n, c, H, W = x.shape
+        x = pixel_values if nhwc else pixel_values.float().contiguous()
+        n, c, H, W, strides = _pixel_geom(x, nhwc)
         w0, b0 = f['stem']
-        cols, H, W = ops.im2col(x, n, H, W, c, 7, 7, 2, 3, dt, strides=(c * H * W, W, 1, H * W), ldcols=w0.shape[1])
+        cols, H, W = ops.im2col(x, n, H, W, c, 7, 7, 2, 3, dt, strides=strides, ldcols=w0.shape[1])
         y = ops.gemm_nt(cols, w0, b0, ops.ACT_RELU)
         del cols
         C = w0.shape[0]
@@ -315,15 +331,36 @@ def resnet34(avgpool=False, compute_dtype='bf16', trainable=False, sync_bn=False
 
 
 class ResNetBackbone(nn.Module):
-    """backbone.py:65-89: sketch [N,1,3,H,W] -> [N,1,C] (global average pooled), frames [N,T,3,H,W] -> [N, T*h*w, C]."""
+    """backbone.py:65-89: sketch [N,1,3,H,W] -> [N,1,C] (global average pooled), frames [N,T,3,H,W] -> [N, T*h*w, C].
 
-    def __init__(self, video_backbone, sketch_backbone):
+    Raw frames — uint8 [N,T,H,W,3] (sketch [N,1,H,W,3]), or a list of N tensors [T,H_b,W_b,3] of any sizes — go through the
+    FrameIngest this backbone owns (svol_dataset.py:218-229: Resize((224,224)) + ToTensor(); ``pixel_preset`` overrides
+    'totensor'): with bf16 extractors it writes the 16-bit NHWC image the stem's im2col reads directly.  Float inputs take exactly
+    the path they always took."""
+
+    def __init__(self, video_backbone, sketch_backbone, pixel_preset=None):
         super().__init__()
         self.video_backbone = video_backbone
         self.sketch_backbone = sketch_backbone
+        self.nhwc = video_backbone.compute_dtype == torch.bfloat16 and sketch_backbone.compute_dtype == torch.bfloat16
+        self.ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out='nhwc_bf16' if self.nhwc else 'nchw_f32')
 
     def forward(self, sketch_batch, video_batch):
+        if is_raw_frames(sketch_batch) or is_raw_frames(video_batch):
+            return self._forward_raw(sketch_batch, video_batch)
         N, T = video_batch.shape[:2]
         src_sketch = self.sketch_backbone(sketch_batch.flatten(0, 1)).view(N, -1, self.sketch_backbone.out_channels)
         tok = self.video_backbone(video_batch.flatten(0, 1))                  # [N*T, h*w, C]
         return src_sketch, tok.reshape(N, T * tok.shape[1], tok.shape[2])
+
+    def _forward_raw(self, sketch_batch, video_batch):
+        N = len(video_batch)
+
+        def run(extractor, x):
+            if is_raw_frames(x):
+                pix = self.ingest(x)
+                return extractor(pix.flatten(0, 1) if pix.dim() == 5 else pix, nhwc=self.nhwc)
+            return extractor(x.flatten(0, 1))
+        src_sketch = run(self.sketch_backbone, sketch_batch).view(N, -1, self.sketch_backbone.out_channels)
+        tok = run(self.video_backbone, video_batch)                             # [N*T, h*w, C]
+        return src_sketch, tok.reshape(N, -1, tok.shape[2])

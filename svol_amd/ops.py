@@ -519,6 +519,22 @@ def im2col(x, N, H, W, C, kh, kw, stride, pad, dtype, strides=None, ldcols=None)
     return cols, Ho, Wo
 
 
+def ingest_resize(src, xtab, kx, ytab, ky, lut, flip, out, out_strides, OH, OW):
+    """Pillow-exact bilinear resize + table look-up of uint8 frames src [n,H,W,3] (any strides, channel stride 1) into `out`,
+    addressed by the ELEMENT strides out_strides = (image, channel, row, column); xtab / ytab int32 [OW, 2+kx] / [OH, 2+ky]
+    (svol_amd.ingest.resample_tables), lut fp32 [3,256], flip uint8 [n] or None.  See svol_ingest_resize in include/svol_hip.h."""
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or (src.shape[0] and src.stride(3) != 1):
+        raise _lib.SvolHipError(f'ingest_resize takes uint8 [n,H,W,3] with channel stride 1, got {src.dtype} {tuple(src.shape)}')
+    n, H, W = src.shape[:3]
+    if n == 0:   # (an empty tensor has no data pointer to pass)
+        return out
+    o_n, o_c, o_h, o_w = out_strides
+    rc = _lib.lib().svol_ingest_resize(_ptr(src), n, H, W, src.stride(0), src.stride(1), src.stride(2), _ptr(xtab), kx, _ptr(ytab), ky,
+                                       _ptr(lut), _ptr(flip), _ptr(out), o_n, o_c, o_h, o_w, OH, OW, _dt(out), _stream())
+    _lib.check(rc, 'svol_ingest_resize')
+    return out
+
+
 def conv_nhwc(x, w, bias, act, N, H, W, C, kh, kw, stride, pad, residual=None):
     """convolution of an NHWC activation [N*H*W, C] with folded weights w [Cout, kh*kw*C (+pad)] -> (y [N*Ho*Wo, Cout], Ho, Wo).
     The implicit-GEMM kernel when the shape fits it (bf16, C % 32 == 0), else im2col + gemm_nt."""
