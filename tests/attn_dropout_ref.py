@@ -135,7 +135,12 @@ def rounder(dtype):
 
 def slice_errors(name, got, ref):
     """{tensor: SliceResult} of (o, dq, dk, dv) on the (batch, 128-row tile, head) slices: query tiles for o / dq, key tiles for dk / dv."""
-    B, H, Lq, Lk, dh, _ = CASES[name]
+    return slice_errors_dims(CASES[name][:5], got, ref)
+
+
+def slice_errors_dims(dims, got, ref):
+    """slice_errors for a launch given by its (B, H, Lq, Lk, dh)"""
+    B, H, Lq, Lk, dh = dims
     out = {}
     for tag, g, r, L in zip(('o', 'dq', 'dk', 'dv'), got, ref, (Lq, Lq, Lk, Lk)):
         out[tag] = S.compare(tag, g.reshape(B, L, H * dh), r.reshape(B, L, H * dh), 'act', heads=H)
