@@ -22,7 +22,7 @@
 // Element types: this file's generic template serves f32 (v_mfma_f32_32x32x2_f32, exact fp32 — the parity
 // mode); bf16 (v_mfma_f32_32x32x16_bf16) is dispatched to the tuned kernels of attention_bf16.hip.
 // Softmax runs in the log2 domain with fp32 statistics; exp via v_exp_f32.
-#include "common.h"
+#include "attn_call.h"
 
 namespace {
 
@@ -490,32 +490,26 @@ int check_common(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int d
 }
 bool ld_ok(int64_t ld, int dtype) { return ld % (svol_is16(dtype) ? 8 : 4) == 0; }
 
+// validates one call (a forward's four operands or a backward's eight) and stores the dims once they are known to fit
+int check_call(AttnCall& c, bool bwd, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int dtype) {
+    const void* ptr[8] = {c.q, c.k, c.v, bwd ? c.o : c.out_o, c.d_o, c.dq, c.dk, c.dv};
+    const int64_t ld[8] = {c.ldq, c.ldk, c.ldv, c.ldo, c.lddo, c.lddq, c.lddk, c.lddv};
+    bool null = !c.lse2 || (bwd && !c.delta), ld_bad = false, unaligned = false;
+    for (int i = 0; i < (bwd ? 8 : 4); ++i) {
+        null |= !ptr[i];
+        ld_bad |= !ld_ok(ld[i], dtype);
+        unaligned |= !aligned16(ptr[i]);
+    }
+    if (null || !(c.drop_p >= 0.f && c.drop_p < 1.f)) return SVOL_E_INVALID;
+    if (const int rc = check_common(B, H, Lq, Lk, dh, dtype)) return rc;
+    if (ld_bad) return SVOL_E_UNSUPPORTED;
+    if (unaligned) return SVOL_E_INVALID;
+    c.B = (int)B; c.H = (int)H; c.Lq = (int)Lq; c.Lk = (int)Lk; c.dh = (int)dh;
+    if (!aligned16(c.ws)) c.ws = nullptr;
+    return SVOL_OK;
+}
+
 }  // namespace
-
-// bf16 fast path (attention_bf16.hip)
-int svol_attn_fwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                              int64_t ldo, float* lse2, const float* kbias, int B, int H, int Lq, int Lk, int dh, float scale,
-                              float premul, float* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed, hipStream_t s);
-int svol_attn_bwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                              const void* o, int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta,
-                              const float* kbias, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int B,
-                              int H, int Lq, int Lk, int dh, float scale, float premul, float* ws, int64_t ws_bytes,
-                              float drop_p, uint64_t drop_seed, int flags, void* ev_prep, hipStream_t s);
-
-int64_t svol_attn_ws_floats_bf16(int B, int H, int Lq, int Lk, int dh);
-int64_t svol_attn_sp_image_bytes_bf16(int B, int H, int Lq, int Lk, int dh, int64_t ws_bytes);
-int svol_attn_sp_zero_bf16_launch(float* ws, int64_t ws_bytes, int B, int H, int Lq, int Lk, int dh, hipStream_t s);
-int64_t svol_attn_sp_image_bytes_f16(int B, int H, int Lq, int Lk, int dh, int64_t ws_bytes);
-int svol_attn_sp_zero_f16_launch(float* ws, int64_t ws_bytes, int B, int H, int Lq, int Lk, int dh, hipStream_t s);
-// the same kernels compiled with fp16 operands (attention_bf16.hip with -DSVOL_H16_FP16)
-int svol_attn_fwd_f16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                             int64_t ldo, float* lse2, const float* kbias, int B, int H, int Lq, int Lk, int dh, float scale,
-                             float premul, float* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed, hipStream_t s);
-int svol_attn_bwd_f16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                             const void* o, int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta,
-                             const float* kbias, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int B,
-                             int H, int Lq, int Lk, int dh, float scale, float premul, float* ws, int64_t ws_bytes,
-                             float drop_p, uint64_t drop_seed, int flags, void* ev_prep, hipStream_t s);
 
 extern "C" {
 
@@ -524,44 +518,29 @@ int64_t svol_attn_ws_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t
     return 4 * svol_attn_ws_floats_bf16((int)B, (int)H, (int)Lq, (int)Lk, (int)dh);
 }
 
-static int attn_fwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                         int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
-                         float scale, float q_premul, void* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed, int dtype,
-                         void* stream) {
-    if (!q || !k || !v || !o || !lse2) return SVOL_E_INVALID;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return SVOL_E_INVALID;
-    int rc = check_common(B, H, Lq, Lk, dh, dtype);
-    if (rc) return rc;
-    if (!ld_ok(ldq, dtype) || !ld_ok(ldk, dtype) || !ld_ok(ldv, dtype) || !ld_ok(ldo, dtype)) return SVOL_E_UNSUPPORTED;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o)) return SVOL_E_INVALID;
-    AttnArgs p{};
-    p.q = q; p.k = k; p.v = v; p.out_o = o; p.lse2 = lse2; p.kbias = kbias;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.B = (int)B; p.H = (int)H; p.Lq = (int)Lq; p.Lk = (int)Lk; p.dh = (int)dh; p.scale = scale; p.premul = q_premul;
-    p.drop_p = drop_p; p.drop_inv = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; p.drop_seed = drop_seed;
-    dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)H, (unsigned)B);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (svol_is16(dtype))
-        return (dtype == SVOL_BF16 ? svol_attn_fwd_bf16_launch : svol_attn_fwd_f16_launch)(
-            q, ldq, k, ldk, v, ldv, o, ldo, lse2, kbias, (int)B, (int)H, (int)Lq, (int)Lk, (int)dh, scale, q_premul,
-            aligned16(ws) ? (float*)ws : nullptr, ws_bytes, drop_p, drop_seed, s);
-    hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), 0, s, p);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
-}
-
-int svol_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                  int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
-                  float scale, float q_premul, void* ws, int64_t ws_bytes, int dtype, void* stream) {
-    return attn_fwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, lse2, kbias, B, H, Lq, Lk, dh, scale, q_premul, ws, ws_bytes, 0.f, 0, dtype,
-                         stream);
-}
 int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
                           int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
                           float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed, int dtype,
                           void* stream) {
-    return attn_fwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, lse2, kbias, B, H, Lq, Lk, dh, scale, q_premul, ws, ws_bytes, dropout_p, seed,
-                         dtype, stream);
+    AttnCall c{};
+    c.q = q; c.k = k; c.v = v; c.out_o = o; c.lse2 = lse2; c.kbias = kbias;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo;
+    c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
+    c.drop_p = dropout_p; c.drop_seed = seed; c.stream = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = check_call(c, false, B, H, Lq, Lk, dh, dtype)) return rc;
+    if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_fwd_bf16_launch : svol_attn_fwd_f16_launch)(c);
+    AttnArgs p{};
+    attn_fill(p, c);
+    dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)H, (unsigned)B);
+    hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), 0, c.stream, p);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+int svol_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                  int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
+                  float scale, float q_premul, void* ws, int64_t ws_bytes, int dtype, void* stream) {
+    return svol_attn_fwd_dropout(q, ldq, k, ldk, v, ldv, o, ldo, lse2, kbias, B, H, Lq, Lk, dh, scale, q_premul, ws, ws_bytes, 0.f, 0,
+                                 dtype, stream);
 }
 
 static int attn_bwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
@@ -569,35 +548,24 @@ static int attn_bwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk,
                          int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H, int64_t Lq, int64_t Lk,
                          int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed,
                          int dtype, void* stream, int flags = 0, void* ev_prep = nullptr) {
-    if (!q || !k || !v || !o || !d_o || !lse2 || !delta || !dq || !dk || !dv) return SVOL_E_INVALID;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return SVOL_E_INVALID;
-    int rc = check_common(B, H, Lq, Lk, dh, dtype);
-    if (rc) return rc;
-    if (!ld_ok(ldq, dtype) || !ld_ok(ldk, dtype) || !ld_ok(ldv, dtype) || !ld_ok(ldo, dtype) || !ld_ok(lddo, dtype) ||
-        !ld_ok(lddq, dtype) || !ld_ok(lddk, dtype) || !ld_ok(lddv, dtype))
-        return SVOL_E_UNSUPPORTED;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(d_o) || !aligned16(dq) ||
-        !aligned16(dk) || !aligned16(dv))
-        return SVOL_E_INVALID;
+    AttnCall c{};
+    c.q = q; c.k = k; c.v = v; c.o = o; c.d_o = d_o; c.lse2 = const_cast<float*>(lse2); c.delta = delta; c.kbias = kbias;
+    c.dq = dq; c.dk = dk; c.dv = dv;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo; c.lddo = lddo; c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
+    c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
+    c.drop_p = drop_p; c.drop_seed = drop_seed; c.flags = flags; c.ev_prep = ev_prep; c.stream = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = check_call(c, true, B, H, Lq, Lk, dh, dtype)) return rc;
+    if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_bwd_bf16_launch : svol_attn_bwd_f16_launch)(c);
     AttnArgs p{};
-    p.q = q; p.k = k; p.v = v; p.o = o; p.d_o = d_o; p.lse2 = const_cast<float*>(lse2); p.delta = delta; p.kbias = kbias;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-    p.B = (int)B; p.H = (int)H; p.Lq = (int)Lq; p.Lk = (int)Lk; p.dh = (int)dh; p.scale = scale; p.premul = q_premul;
-    p.drop_p = drop_p; p.drop_inv = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; p.drop_seed = drop_seed;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    attn_fill(p, c);
     const int64_t total = B * Lq * H;
     dim3 gd((unsigned)((total + 255) / 256));
     dim3 gq((unsigned)((Lq + 127) / 128), (unsigned)H, (unsigned)B);
     dim3 gk((unsigned)((Lk + 127) / 128), (unsigned)H, (unsigned)B);
-    if (svol_is16(dtype))
-        return (dtype == SVOL_BF16 ? svol_attn_bwd_bf16_launch : svol_attn_bwd_f16_launch)(
-            q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse2, delta, kbias, dq, lddq, dk, lddk, dv, lddv, (int)B, (int)H, (int)Lq,
-            (int)Lk, (int)dh, scale, q_premul, aligned16(ws) ? (float*)ws : nullptr, ws_bytes, drop_p, drop_seed, flags, ev_prep, s);
-    hipLaunchKernelGGL(attn_delta_kernel<float>, gd, dim3(256), 0, s, p);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, gq, dim3(256), 0, s, p);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<float>, gk, dim3(256), 0, s, p);
-    if (ev_prep) (void)hipEventRecord(static_cast<hipEvent_t>(ev_prep), s);
+    hipLaunchKernelGGL(attn_delta_kernel<float>, gd, dim3(256), 0, c.stream, p);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, gq, dim3(256), 0, c.stream, p);
+    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<float>, gk, dim3(256), 0, c.stream, p);
+    if (ev_prep) (void)hipEventRecord(static_cast<hipEvent_t>(ev_prep), c.stream);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }

@@ -18,7 +18,7 @@
 #include <cstdint>
 #include <cstdlib>
 
-#include "common.h"
+#include "attn_call.h"
 
 namespace {
 
@@ -2725,6 +2725,10 @@ static inline unsigned sp_grid(int B, int H, int Lk) { return (unsigned)(B * H *
 // workgroups a key-split launch aims for (these launches run on the query stream beside the video half: 256 -> 18.98 / 19.07 ms
 // per step, 512 -> 19.12, 1024 -> 19.28)
 constexpr int KSPLIT_WGS = 256;
+// floats of a key split's partials: [ks] unnormalised O | [ks] (m2, l) | the fp32 dQ image (make_args binds them)
+static int64_t ksplit_ws_floats(int ks, int B, int H, int Lq, int dh) {
+    return (int64_t)ks * B * Lq * H * dh + (int64_t)ks * B * H * Lq * 2 + (int64_t)B * Lq * H * dh;
+}
 static int plan_ksplit(int B, int H, int Lq, int Lk, int dh, int64_t ws_floats, int* tiles_per_split) {
     const int nt = (Lk + KT - 1) / KT;
     const int64_t wgs = (int64_t)((Lq + 127) / 128) * H * B;
@@ -2735,8 +2739,7 @@ static int plan_ksplit(int B, int H, int Lq, int Lk, int dh, int64_t ws_floats, 
     int tps = (nt + want - 1) / want;
     if (tps < 2) tps = 2;
     const int ks = (nt + tps - 1) / tps;
-    const int64_t need = (int64_t)ks * B * Lq * H * dh + (int64_t)ks * B * H * Lq * 2 + (int64_t)B * Lq * H * dh;
-    if (ks < 2 || need > ws_floats) return 1;
+    if (ks < 2 || ksplit_ws_floats(ks, B, H, Lq, dh) > ws_floats) return 1;
     *tiles_per_split = tps;
     return ks;
 }
@@ -2746,198 +2749,190 @@ constexpr int SP_MIN_LK = 2 * SP_KEYS;
 // SVOL_DETERMINISTIC=1: no floating-point atomics in the attention backward — the two-pass kernels (dQ by a query-stationary pass)
 // instead of the single pass, no key split for launches with few queries (their dQ partials meet through atomics).  Gradients are
 // then bit-identical from run to run (tests/test_gpu_ops.py::test_attention_backward_is_bit_reproducible_in_deterministic_mode).
-static bool attn_deterministic() {
-    static const bool det = getenv("SVOL_DETERMINISTIC") != nullptr;
-    return det;
+// The switch is svol_deterministic() (common.h), read once per process.
+// ---- the launch plan: every decision of the two launchers and of the scratch queries, made once ---------------------------------------
+// (tests/attn_range_cases.py plan() restates attn_plan under the same names; tests/test_abi.py holds the two together)
+enum class Fwd { fast2_redo, pre_all, pre_masked, general_m, general_u, ksplit_m, ksplit_u };   // fast2+redo, ...
+// 2pass_m / 2pass_u ("+ksplit": bwd_ksplit > 1); fq_m / fq_u go by the bias pointer, every other _m / _u by `masked`
+enum class Bwd { bwd_sp, bwd_rot_dma, bwd_rot, bwd_pre, bwd_pre_masked, fq_m, fq_u, two_pass_m, two_pass_u };
+// one launch grid and what its kernel is told about it: head_xcd != 0: 1-D, B*H*nxt workgroups with the heads dealt to the XCDs
+struct Grid { dim3 dim; int head_xcd, nxt, tail_last; };
+struct Plan {
+    bool masked, pre;   // a key bias or a ragged last key tile | the fast kernels (pre-multiplied q)
+    Fwd fwd; Bwd bwd;
+    int ntk, fwd_ksplit, fwd_tps, bwd_ksplit, bwd_tps;   // key tiles; key split (1 = none) and key tiles per split of each direction
+    Grid gf, gq, gk;                                     // forward | backward dQ | backward dK/dV
+    int fq_tps; dim3 fq_grid;                            // few-query pass: key tiles per workgroup, and its grid
+    // scratch each use needs, in 4-byte words (blind to dtype, premul and bias): key-tile classes of the masked fast kernels (one int
+    // per (batch, key tile)) | redo flags of the unmasked fast forward (one int per workgroup: (batch, head, 128-query tile)) |
+    // single-pass backward: fp32 dQ image + tail partials | key-split partials; `need`: what svol_attn_ws_bytes asks for
+    int64_t need_cls, need_redo, need_sp, need_ksplit, need;
+};
+static Plan attn_plan(int B, int H, int Lq, int Lk, int dh, bool premul, bool kbias, bool dropout, bool ws, int64_t ws_bytes,
+                      bool det = svol_deterministic()) {
+    static const bool no_fewq = getenv("SVOL_ATTN_NO_FEWQ") != nullptr;   // SVOL_ATTN_NO_FEWQ=1: the two-pass kernels
+    Plan pl{};
+    const int ntk = pl.ntk = pl.fwd_tps = (Lk + KT - 1) / KT, nq128 = (Lq + 127) / 128;
+    int tps;
+    const int ks_free = plan_ksplit(B, H, Lq, Lk, dh, INT64_MAX, &tps);   // the key split that unbounded scratch would allow
+    const bool sp_shape = !det && dh == 32 && H == 8 && (B * H) % 8 == 0 && Lq % KT == 0 && Lk % KT == 0 && Lk >= SP_MIN_LK;
+    pl.need_cls = (int64_t)B * ntk;
+    pl.need_redo = (int64_t)B * H * nq128;
+    pl.need_sp = sp_shape ? (int64_t)B * Lq * H * 32 + (int64_t)B * H * 4 * 2 * (Lk % SP_KEYS) * 32 : 0;
+    pl.need_ksplit = ks_free > 1 ? ksplit_ws_floats(ks_free, B, H, Lq, dh) : 0;
+    pl.need = ks_free > 1 ? pl.need_ksplit : max(max(pl.need_cls, pl.need_redo), pl.need_sp);   // (whichever is larger)
+    pl.masked = kbias || (Lk % KT) != 0;
+    // pre-multiplied q: the fast kernels (attention dropout lives in the general kernels only).  Masked / ragged launches take them
+    // when the key-split would not have been chosen anyway (enough query tiles to fill the chip): the encoder self-attention of the
+    // enc/dec Transformer, video lengths that are not a multiple of 128; masked launches with few queries keep the key-split path
+    pl.pre = premul && !dropout && (!pl.masked || (ks_free == 1 && ws && ws_bytes >= 4 * pl.need_cls));
+    pl.fwd_ksplit = (ws && !pl.pre) ? plan_ksplit(B, H, Lq, Lk, dh, ws_bytes / 4, &pl.fwd_tps) : 1;
+    pl.bwd_ksplit = det ? 1 : pl.fwd_ksplit;
+    pl.bwd_tps = det ? ntk : pl.fwd_tps;
+    // heads dealt to the XCDs (block_coords): the fast kernels, when the heads go round the 8 XCDs
+    const int hx = (pl.pre && (B * H) % 8 == 0) ? (((B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1) : 0;
+    auto grid = [&](int nx) {
+        return hx ? Grid{dim3((unsigned)(B * H * nx)), hx, nx, 0} : Grid{dim3((unsigned)nx, (unsigned)H, (unsigned)B), 0, 0, 0};
+    };
+    pl.gf = grid(nq128 * pl.fwd_ksplit);
+    pl.gq = pl.pre ? grid((Lq + 255) / 256) : grid(nq128 * pl.bwd_ksplit);   // (the fast dQ kernels: 256 queries per workgroup)
+    if (hx) pl.gq.tail_last = (Lq % 256 >= 1 && Lq % 256 <= 128 && pl.gq.nxt > 1) ? 1 : 0;
+    pl.gk = grid((Lk + 127) / 128);
+    if (pl.pre && pl.masked) pl.fwd = Fwd::pre_masked;
+    else if (pl.pre) pl.fwd = (hx && dh == 32 && ws && ws_bytes >= 4 * pl.need_redo) ? Fwd::fast2_redo : Fwd::pre_all;
+    else if (pl.fwd_ksplit > 1) pl.fwd = pl.masked ? Fwd::ksplit_m : Fwd::ksplit_u;
+    else pl.fwd = pl.masked ? Fwd::general_m : Fwd::general_u;
+    if (pl.pre && pl.masked) pl.bwd = Bwd::bwd_pre_masked;
+    else if (pl.pre && hx && sp_shape && ws && ws_bytes >= 4 * pl.need_sp) pl.bwd = Bwd::bwd_sp;
+    else if (pl.pre && dh == 32) pl.bwd = Lq % KT == 0 ? Bwd::bwd_rot_dma : Bwd::bwd_rot;
+    else if (pl.pre) pl.bwd = Bwd::bwd_pre;
+    // the single-pass few-query backward (attn_bwd_fq_bf16): <= 128 queries, the key-split path's fp32 dQ image bound (ksplit > 1: few
+    // query tiles, many key tiles, workspace large enough), head width 32, no attention dropout
+    else if (!no_fewq && !det && pl.bwd_ksplit > 1 && Lq <= KT && dh == 32 && !dropout) pl.bwd = kbias ? Bwd::fq_m : Bwd::fq_u;
+    else pl.bwd = pl.masked ? Bwd::two_pass_m : Bwd::two_pass_u;
+    const int chunks = min(ntk, max(1, 512 / (B * H)));   // ~512 workgroups
+    pl.fq_tps = (ntk + chunks - 1) / chunks;
+    pl.fq_grid = dim3((unsigned)((ntk + pl.fq_tps - 1) / pl.fq_tps), (unsigned)H, (unsigned)B);
+    return pl;
 }
-static bool sp_shape_ok(int B, int H, int Lq, int Lk, int dh) {
-    return !attn_deterministic() && dh == 32 && H == 8 && (B * H) % 8 == 0 && Lq % KT == 0 && Lk % KT == 0 && Lk >= SP_MIN_LK;
+static Plan attn_plan(const AttnCall& c) {
+    return attn_plan(c.B, c.H, c.Lq, c.Lk, c.dh, c.premul != 0.f, c.kbias != nullptr, c.drop_p > 0.f, c.ws != nullptr, c.ws_bytes);
 }
-// the single-pass few-query backward (attn_bwd_fq_bf16): <= 128 queries, the key-split path's fp32 dQ image bound (ksplit > 1: few
-// query tiles, many key tiles, workspace large enough), head width 32, no attention dropout; SVOL_ATTN_NO_FEWQ=1: the two-pass kernels
-static bool fewq_ok(const Args& p) {
-    static const bool off = getenv("SVOL_ATTN_NO_FEWQ") != nullptr;
-    return !off && !attn_deterministic() && p.ksplit > 1 && p.Lq <= KT && p.dh == 32 && p.drop_p == 0.f && p.ws_dq != nullptr;
+int64_t svol_attn_ws_floats_bf16(int B, int H, int Lq, int Lk, int dh) {
+    return attn_plan(B, H, Lq, Lk, dh, false, false, false, /*ws*/ false, 0).need;
 }
-static int64_t sp_ws_floats(int B, int H, int Lq, int Lk) { return (int64_t)B * Lq * H * 32 + (int64_t)B * H * 4 * 2 * (Lk % SP_KEYS) * 32; }
-// an unmasked, pre-multiplied, dropout-free launch of this shape with this workspace runs the single pass
-static bool sp_taken(int B, int H, int Lq, int Lk, int dh, const void* ws, int64_t ws_bytes) {
-    return sp_shape_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= 4 * sp_ws_floats(B, H, Lq, Lk);
+// whether an unmasked, pre-multiplied, dropout-free launch of this shape with this workspace runs the single pass
+static bool sp_planned(int B, int H, int Lq, int Lk, int dh, bool ws, int64_t ws_bytes) {
+    return attn_plan(B, H, Lq, Lk, dh, /*premul*/ true, /*kbias*/ false, /*dropout*/ false, ws, ws_bytes).bwd == Bwd::bwd_sp;
 }
 // bytes of the fp32 dQ image at the head of the workspace when the single pass serves the shape, else 0 (svol_attn_bwd_sp_image_bytes)
 int64_t svol_attn_sp_image_bytes_bf16(int B, int H, int Lq, int Lk, int dh, int64_t ws_bytes) {
-    return sp_taken(B, H, Lq, Lk, dh, reinterpret_cast<const void*>(16), ws_bytes) ? (int64_t)B * Lq * H * 32 * 4 : 0;
+    return sp_planned(B, H, Lq, Lk, dh, true, ws_bytes) ? (int64_t)B * Lq * H * 32 * 4 : 0;
 }
 // few workgroups: the launch runs BESIDE a single-pass kernel whose workgroups own their CUs' register files; a wide grid takes
 // dispatch slots from that kernel's first round (measured: 2048 workgroups cost it 30 us, more than the fill saves)
 constexpr int SP_ZERO_WGS = 64;
 int svol_attn_sp_zero_bf16_launch(float* ws, int64_t ws_bytes, int B, int H, int Lq, int Lk, int dh, hipStream_t s) {
-    if (!sp_taken(B, H, Lq, Lk, dh, ws, ws_bytes)) return SVOL_E_UNSUPPORTED;
+    if (!sp_planned(B, H, Lq, Lk, dh, ws != nullptr, ws_bytes)) return SVOL_E_UNSUPPORTED;
     const int64_t n4 = (int64_t)B * Lq * H * 32 / 4;
     const int64_t want = (n4 + 255) / 256;
     hipLaunchKernelGGL(attn_sp_zero_image, dim3((unsigned)(want < SP_ZERO_WGS ? want : SP_ZERO_WGS)), dim3(256), 0, s, ws, n4);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
-int64_t svol_attn_ws_floats_bf16(int B, int H, int Lq, int Lk, int dh) {
-    int tps;
-    const int ks = plan_ksplit(B, H, Lq, Lk, dh, INT64_MAX, &tps);
-    if (ks < 2) {
-        // key-tile classes of the masked fast kernels (one int per (batch, key tile)), or the redo flags of the unmasked fast
-        // forward (one int per workgroup: (batch, head, 128-query tile)) — whichever is larger
-        const int64_t cls = (int64_t)B * ((Lk + KT - 1) / KT), redo = (int64_t)B * H * ((Lq + 127) / 128);
-        const int64_t sp = sp_shape_ok(B, H, Lq, Lk, dh) ? sp_ws_floats(B, H, Lq, Lk) : 0;   // single-pass backward: fp32 dQ image + tail partials
-        const int64_t m = cls > redo ? cls : redo;
-        return m > sp ? m : sp;
+// the kernel arguments of one launch: the call's operands, a key split bound to the workspace, the grid's head deal
+static Args make_args(const AttnCall& c, int ksplit, int tiles_per_split, const Grid& g) {
+    Args p{};
+    attn_fill(p, c);
+    p.ksplit = ksplit; p.tiles_per_split = tiles_per_split;
+    if (ksplit > 1) {
+        p.ws_o = c.ws;
+        p.ws_ml = p.ws_o + (int64_t)p.ksplit * p.B * p.Lq * p.H * p.dh;
+        p.ws_dq = p.ws_ml + (int64_t)p.ksplit * p.B * p.H * p.Lq * 2;
     }
-    return (int64_t)ks * B * Lq * H * dh + (int64_t)ks * B * H * Lq * 2 + (int64_t)B * Lq * H * dh;
-}
-// masked / ragged launches take the fast kernels when the key-split would not have been chosen anyway (enough query tiles to
-// fill the chip): the encoder self-attention of the enc/dec Transformer, video lengths that are not a multiple of 128
-static bool pre_masked_ok(int B, int H, int Lq, int Lk, int dh) {
-    int tps;
-    return plan_ksplit(B, H, Lq, Lk, dh, INT64_MAX, &tps) == 1;
-}
-static void bind_ws(Args& p, float* ws) {
-    p.ws_o = ws;
-    p.ws_ml = p.ws_o + (int64_t)p.ksplit * p.B * p.Lq * p.H * p.dh;
-    p.ws_dq = p.ws_ml + (int64_t)p.ksplit * p.B * p.H * p.Lq * 2;
+    p.head_xcd = g.head_xcd; p.nxt = g.nxt; p.tail_last = g.tail_last;
+    return p;
 }
 
-int svol_attn_fwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                              int64_t ldo, float* lse2, const float* kbias, int B, int H, int Lq, int Lk, int dh, float scale,
-                              float premul, float* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed, hipStream_t s) {
-    Args p{};
-    p.drop_p = drop_p; p.drop_inv = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; p.drop_seed = drop_seed;
-    p.q = q; p.k = k; p.v = v; p.out_o = o; p.lse2 = lse2; p.kbias = kbias;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.dh = dh; p.scale = scale; p.premul = premul;
-    const bool masked = kbias != nullptr || (Lk % KT) != 0;
-    // pre-multiplied q: the fast kernels; masked launches with few queries keep the key-split path below
-    const int ntk = (Lk + KT - 1) / KT;
-    const bool pre = premul != 0.f && drop_p == 0.f &&   // (attention dropout lives in the general kernels only)
-                     (!masked || (pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
-    p.ksplit = (ws && !pre) ? plan_ksplit(B, H, Lq, Lk, dh, ws_bytes / 4, &p.tiles_per_split) : 1;
-    if (p.ksplit == 1) p.tiles_per_split = ntk;
-    else bind_ws(p, ws);
-    dim3 grid((unsigned)(((Lq + 127) / 128) * p.ksplit), (unsigned)H, (unsigned)B);
-    if (pre && (B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
-        p.head_xcd = ((B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
-        p.nxt = (Lq + 127) / 128;
-        grid = dim3((unsigned)(B * H * p.nxt));
+int svol_attn_fwd_bf16_launch(const AttnCall& c) {
+    const Plan pl = attn_plan(c);
+    Args p = make_args(c, pl.fwd_ksplit, pl.fwd_tps, pl.gf);
+    const dim3 grid = pl.gf.dim, wg(256);
+    hipStream_t s = c.stream;
+    switch (pl.fwd) {
+    case Fwd::pre_masked:
+        p.tile_flags = reinterpret_cast<const int*>(c.ws);
+        hipLaunchKernelGGL(attn_tile_flags_bf16, dim3((unsigned)pl.ntk, (unsigned)c.B), dim3(64), 0, s, c.kbias, c.Lk, pl.ntk, reinterpret_cast<int*>(c.ws));
+        hipLaunchKernelGGL(attn_fwd_bf16_pre_masked, grid, wg, 0, s, p);
+        break;
+    case Fwd::fast2_redo:
+        p.redo = reinterpret_cast<int*>(c.ws);
+        hipLaunchKernelGGL(attn_fwd_bf16_fast2, grid, wg, 0, s, p);
+        [[fallthrough]];   // attn_fwd_bf16_pre behind it recomputes the flagged workgroups only (p.redo)
+    case Fwd::pre_all: hipLaunchKernelGGL(attn_fwd_bf16_pre, grid, wg, 0, s, p); break;
+    case Fwd::general_m:
+    case Fwd::ksplit_m: hipLaunchKernelGGL(attn_fwd_bf16<true>, grid, wg, 0, s, p); break;
+    case Fwd::general_u:
+    case Fwd::ksplit_u: hipLaunchKernelGGL(attn_fwd_bf16<false>, grid, wg, 0, s, p); break;
     }
-    if (pre && masked) {
-        p.tile_flags = reinterpret_cast<const int*>(ws);
-        hipLaunchKernelGGL(attn_tile_flags_bf16, dim3((unsigned)ntk, (unsigned)B), dim3(64), 0, s, kbias, Lk, ntk, reinterpret_cast<int*>(ws));
-        hipLaunchKernelGGL(attn_fwd_bf16_pre_masked, grid, dim3(256), 0, s, p);
-    } else if (pre) {
-        const int64_t nwg = (int64_t)grid.x * grid.y * grid.z;
-        if (p.head_xcd && dh == 32 && ws && ws_bytes >= nwg * 4) {
-            p.redo = reinterpret_cast<int*>(ws);
-            hipLaunchKernelGGL(attn_fwd_bf16_fast2, grid, dim3(256), 0, s, p);
-        }
-        hipLaunchKernelGGL(attn_fwd_bf16_pre, grid, dim3(256), 0, s, p);  // all workgroups, or (p.redo) only the flagged ones
-    } else if (masked) hipLaunchKernelGGL(attn_fwd_bf16<true>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(attn_fwd_bf16<false>, grid, dim3(256), 0, s, p);
-    if (p.ksplit > 1) {
-        const int64_t total = (int64_t)B * Lq * H;
-        hipLaunchKernelGGL(attn_combine_bf16, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, p);
-    }
+    const int64_t total = (int64_t)c.B * c.Lq * c.H;
+    if (pl.fwd_ksplit > 1) hipLaunchKernelGGL(attn_combine_bf16, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
 
-int svol_attn_bwd_bf16_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                              const void* o, int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta,
-                              const float* kbias, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int B,
-                              int H, int Lq, int Lk, int dh, float scale, float premul, float* ws, int64_t ws_bytes,
-                              float drop_p, uint64_t drop_seed, int flags, void* ev_prep, hipStream_t s) {
-    // ev_prep: recorded behind the launches that must precede work on the caller's OTHER workspace (single pass: behind the prep
-    // kernel, i.e. in front of the long key-stationary kernel; every other path: behind the last launch)
-    struct PrepEvent {
-        void* ev; hipStream_t s; bool done = false;
-        void fire() { if (ev && !done) (void)hipEventRecord(static_cast<hipEvent_t>(ev), s); done = true; }
-        ~PrepEvent() { fire(); }
-    } prep_ev{ev_prep, s};
-    Args p{};
-    p.drop_p = drop_p; p.drop_inv = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; p.drop_seed = drop_seed;
-    p.q = q; p.k = k; p.v = v; p.o = o; p.d_o = d_o; p.lse2 = const_cast<float*>(lse2); p.delta = delta; p.kbias = kbias;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-    p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.dh = dh; p.scale = scale; p.premul = premul;
-    const int64_t total = (int64_t)B * Lq * H;
-    const bool masked = kbias != nullptr || (Lk % KT) != 0;
-    const int ntk = (Lk + KT - 1) / KT;
-    const bool pre = premul != 0.f && drop_p == 0.f &&
-                     (!masked || (pre_masked_ok(B, H, Lq, Lk, dh) && ws && ws_bytes >= (int64_t)B * ntk * 4));
-    p.ksplit = (ws && !pre && !attn_deterministic()) ? plan_ksplit(B, H, Lq, Lk, dh, ws_bytes / 4, &p.tiles_per_split) : 1;
-    if (p.ksplit == 1) p.tiles_per_split = ntk;
-    else bind_ws(p, ws);
-    dim3 gd((unsigned)((total + 255) / 256));
-    dim3 gq((unsigned)(((Lq + 127) / 128) * p.ksplit), (unsigned)H, (unsigned)B);
-    dim3 gk((unsigned)((Lk + 127) / 128), (unsigned)H, (unsigned)B);
-    if (!pre) hipLaunchKernelGGL(attn_delta_bf16, gd, dim3(256), 0, s, p);  // (the fast dQ kernel computes delta in its prologue)
-    if (pre) {
-        Args pq = p, pk = p;
-        dim3 gq2((unsigned)((Lq + 255) / 256), (unsigned)H, (unsigned)B);
-        dim3 gk2 = gk;
-        if ((B * H) % 8 == 0) {  // heads dealt to the XCDs (block_coords)
-            pq.head_xcd = pk.head_xcd = ((B * H) % 16 == 0 && H % 2 == 0 && dh == 32) ? 2 : 1;
-            pq.nxt = (Lq + 255) / 256;
-            pk.nxt = (Lk + 127) / 128;
-            pq.tail_last = (Lq % 256 >= 1 && Lq % 256 <= 128 && pq.nxt > 1) ? 1 : 0;
-            gq2 = dim3((unsigned)(B * H * pq.nxt));
-            gk2 = dim3((unsigned)(B * H * pk.nxt));
-        }
-        if (masked) {
-            pq.tile_flags = pk.tile_flags = reinterpret_cast<const int*>(ws);
-            hipLaunchKernelGGL(attn_tile_flags_bf16, dim3((unsigned)ntk, (unsigned)B), dim3(64), 0, s, kbias, Lk, ntk, reinterpret_cast<int*>(ws));
-            hipLaunchKernelGGL(attn_bwd_dq_bf16_pre_masked, gq2, dim3(256), 0, s, pq);
-            hipLaunchKernelGGL(attn_bwd_dkdv_bf16_pre_masked, gk2, dim3(256), 0, s, pk);
-        } else {
-            if (pq.head_xcd && sp_taken(B, H, Lq, Lk, dh, ws, ws_bytes)) {
-                // single pass: row constants + zeroed fp32 dQ image, the key-stationary kernel, rounding of dQ
-                Args ps = pq;
-                const int64_t n = (int64_t)B * H * Lq;
-                ps.ws_dq = ws;
-                ps.nl2 = reinterpret_cast<unsigned*>(delta + n);     // here: plain fp32 -lse2
-                ps.nd2 = reinterpret_cast<unsigned*>(delta + 2 * n);  //       plain fp32 -delta
-                if (flags & SVOL_ATTN_DQ_PREZEROED) hipLaunchKernelGGL(attn_bwd_sp_prep_bf16<false>, dim3((unsigned)((int64_t)B * Lq / 32)), dim3(256), 0, s, ps);
-                else hipLaunchKernelGGL(attn_bwd_sp_prep_bf16<true>, dim3((unsigned)((int64_t)B * Lq / 32)), dim3(256), 0, s, ps);
-                prep_ev.fire();
-                hipLaunchKernelGGL(attn_bwd_sp_bf16, dim3(sp_grid(B, H, Lk)), dim3(256), 0, s, ps);
-                hipLaunchKernelGGL(attn_dq_round_bf16, dim3(sp_round_grid(B, H, Lq, Lk)), dim3(256), 0, s, ps);
-                return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
-            }
-            // delta is a 3 x [B,H,Lq] scratch: fp32 delta | -lse2 pairs | -delta pairs (the last two for the DMA dK/dV kernel)
-            const bool dma = dh == 32 && Lq % KT == 0;
-            if (dma) {
-                const int64_t n = (int64_t)B * H * Lq;
-                pq.nl2 = pk.nl2 = reinterpret_cast<unsigned*>(delta + n);
-                pq.nd2 = pk.nd2 = reinterpret_cast<unsigned*>(delta + 2 * n);
-            }
-            if (dh == 32) hipLaunchKernelGGL(attn_bwd_dq_bf16_rot, gq2, dim3(256), 0, s, pq);
-            else hipLaunchKernelGGL(attn_bwd_dq_bf16_pre, gq2, dim3(256), 0, s, pq);
-            if (dma) hipLaunchKernelGGL(attn_bwd_dkdv_bf16_pre_dma, gk2, dim3(256), 0, s, pk);
-            else hipLaunchKernelGGL(attn_bwd_dkdv_bf16_pre, gk2, dim3(256), 0, s, pk);
-        }
-    } else if (fewq_ok(p)) {
+int svol_attn_bwd_bf16_launch(const AttnCall& c) {
+    const Plan pl = attn_plan(c);
+    // (the general kernels' grids carry no head deal: pq and pk are the same there, and pq serves the launches that are neither's)
+    Args pq = make_args(c, pl.bwd_ksplit, pl.bwd_tps, pl.gq), pk = make_args(c, pl.bwd_ksplit, pl.bwd_tps, pl.gk);
+    const int64_t total = (int64_t)c.B * c.Lq * c.H;
+    const dim3 gd((unsigned)((total + 255) / 256)), wg(256);
+    hipStream_t s = c.stream;
+    // delta is a 3 x [B,H,Lq] scratch: fp32 delta | -lse2 pairs | -delta pairs (the last two for the DMA dK/dV kernel; the single
+    // pass keeps plain fp32 -lse2 and -delta there)
+    auto bind_rows = [&](Args& a) { a.nl2 = reinterpret_cast<unsigned*>(c.delta + total); a.nd2 = reinterpret_cast<unsigned*>(c.delta + 2 * total); };
+    void (*dq)(Args) = nullptr, (*dkdv)(Args) = nullptr;   // the plans of two kernels: dQ over gq, then dK/dV over gk
+    if (!pl.pre) hipLaunchKernelGGL(attn_delta_bf16, gd, wg, 0, s, pq);  // (the fast dQ kernel computes delta in its prologue)
+    switch (pl.bwd) {
+    case Bwd::bwd_pre_masked:
+        pq.tile_flags = pk.tile_flags = reinterpret_cast<const int*>(c.ws);
+        hipLaunchKernelGGL(attn_tile_flags_bf16, dim3((unsigned)pl.ntk, (unsigned)c.B), dim3(64), 0, s, c.kbias, c.Lk, pl.ntk, reinterpret_cast<int*>(c.ws));
+        dq = attn_bwd_dq_bf16_pre_masked, dkdv = attn_bwd_dkdv_bf16_pre_masked;
+        break;
+    case Bwd::bwd_sp:   // single pass: row constants + zeroed fp32 dQ image here; the key-stationary kernel and the rounding of dQ below
+        pq.ws_dq = c.ws;
+        bind_rows(pq);   // here: plain fp32 -lse2 and -delta
+        hipLaunchKernelGGL((c.flags & SVOL_ATTN_DQ_PREZEROED) ? attn_bwd_sp_prep_bf16<false> : attn_bwd_sp_prep_bf16<true>,
+                           dim3((unsigned)((int64_t)c.B * c.Lq / 32)), wg, 0, s, pq);
+        break;
+    case Bwd::bwd_rot_dma:
+        bind_rows(pq), bind_rows(pk);
+        dq = attn_bwd_dq_bf16_rot, dkdv = attn_bwd_dkdv_bf16_pre_dma;
+        break;
+    case Bwd::bwd_rot: dq = attn_bwd_dq_bf16_rot, dkdv = attn_bwd_dkdv_bf16_pre; break;
+    case Bwd::bwd_pre: dq = attn_bwd_dq_bf16_pre, dkdv = attn_bwd_dkdv_bf16_pre; break;
+    case Bwd::fq_m:
+    case Bwd::fq_u: {
         // few queries against many keys (the query -> video cross attention): ONE key-stationary pass (attn_bwd_fq_bf16); the delta launch
         // above has zeroed the fp32 dQ image (ksplit > 1), attn_dq_finish_bf16 scales and rounds it
-        Args pf = p;
-        const int want = max(1, 512 / (B * H));                 // ~512 workgroups
-        const int chunks = min(ntk, want);
-        pf.tiles_per_split = (ntk + chunks - 1) / chunks;
-        const dim3 gf((unsigned)((ntk + pf.tiles_per_split - 1) / pf.tiles_per_split), (unsigned)H, (unsigned)B);
-        if (kbias) hipLaunchKernelGGL(attn_bwd_fq_bf16<true>, gf, dim3(256), 0, s, pf);
-        else hipLaunchKernelGGL(attn_bwd_fq_bf16<false>, gf, dim3(256), 0, s, pf);
-        hipLaunchKernelGGL(attn_dq_finish_bf16, gd, dim3(256), 0, s, p);
-    } else if (masked) {
-        hipLaunchKernelGGL(attn_bwd_dq_bf16<true>, gq, dim3(256), 0, s, p);
-        if (p.ksplit > 1) hipLaunchKernelGGL(attn_dq_finish_bf16, gd, dim3(256), 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dkdv_bf16<true>, gk, dim3(256), 0, s, p);
-    } else {
-        hipLaunchKernelGGL(attn_bwd_dq_bf16<false>, gq, dim3(256), 0, s, p);
-        if (p.ksplit > 1) hipLaunchKernelGGL(attn_dq_finish_bf16, gd, dim3(256), 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dkdv_bf16<false>, gk, dim3(256), 0, s, p);
+        Args pf = pq;
+        pf.tiles_per_split = pl.fq_tps;
+        hipLaunchKernelGGL(pl.bwd == Bwd::fq_m ? attn_bwd_fq_bf16<true> : attn_bwd_fq_bf16<false>, pl.fq_grid, wg, 0, s, pf);
+        hipLaunchKernelGGL(attn_dq_finish_bf16, gd, wg, 0, s, pq);
+        break;
+    }
+    case Bwd::two_pass_m: dq = attn_bwd_dq_bf16<true>, dkdv = attn_bwd_dkdv_bf16<true>; break;
+    case Bwd::two_pass_u: dq = attn_bwd_dq_bf16<false>, dkdv = attn_bwd_dkdv_bf16<false>; break;
+    }
+    if (dq) {
+        hipLaunchKernelGGL(dq, pl.gq.dim, wg, 0, s, pq);
+        if (pl.bwd_ksplit > 1) hipLaunchKernelGGL(attn_dq_finish_bf16, gd, wg, 0, s, pq);
+        hipLaunchKernelGGL(dkdv, pl.gk.dim, wg, 0, s, pk);
+    }
+    // ev_prep: recorded behind the launches that must precede work on the caller's OTHER workspace — for the single pass behind its
+    // prep kernel, i.e. in front of the long key-stationary kernel; for every other plan behind the last launch
+    if (c.ev_prep) (void)hipEventRecord(static_cast<hipEvent_t>(c.ev_prep), s);
+    if (pl.bwd == Bwd::bwd_sp) {
+        hipLaunchKernelGGL(attn_bwd_sp_bf16, dim3(sp_grid(c.B, c.H, c.Lk)), wg, 0, s, pq);
+        hipLaunchKernelGGL(attn_dq_round_bf16, dim3(sp_round_grid(c.B, c.H, c.Lq, c.Lk)), wg, 0, s, pq);
     }
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }

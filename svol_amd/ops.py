@@ -408,7 +408,7 @@ def posenc_sine(mask_f32: torch.Tensor, D: int, dtype: torch.dtype) -> torch.Ten
     return pos
 
 
-def _attn_ws(q, B, H, Lq, Lk, dh, masked):
+def _attn_ws(q, B, H, Lq, Lk, dh):
     """scratch of the attention launches: partial results of the key-split (few queries, many keys), the key-tile classes of
     the masked fast kernels, or the per-workgroup redo flags of the fast unmasked forward; None when the library needs none."""
     n = _lib.lib().svol_attn_ws_bytes(B, H, Lq, Lk, dh) if q.dtype != torch.float32 else 0
@@ -436,22 +436,17 @@ def dropout_add(t32, res32, p, seed):
 
 def attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias=None, premul=0.0, drop=None):
     """q/k/v: 2-D [B*L, >=H*dh] views (column slices allowed). Returns o [B*Lq, H*dh], lse2 [B,H,Lq].
-    drop = (p, seed): attention-probability dropout (svol_attn_fwd_dropout)."""
+    drop = (p, seed): attention-probability dropout (None or p <= 0: none)."""
     o = torch.empty((B * Lq, H * dh), dtype=q.dtype, device=q.device)
     lse2 = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-    ws = _attn_ws(q, B, H, Lq, Lk, dh, kbias is not None or Lk % 128 != 0)
+    ws = _attn_ws(q, B, H, Lq, Lk, dh)
+    p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
     if B * H * Lq * Lk >= _WGRAD_FLUSH_MIN_SCORES:
         _BIG_ATTN['left'] += 1
     tok = timer.start('attn_fwd', (B, H, Lq, Lk, dh))
-    if drop is not None and drop[0] > 0.0:
-        rc = _lib.lib().svol_attn_fwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o),
-                                              o.stride(0), _ptr(lse2), _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh),
-                                              float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, float(drop[0]),
-                                              int(drop[1]), _dt(q), _stream())
-    else:
-        rc = _lib.lib().svol_attn_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o),
-                                      o.stride(0), _ptr(lse2), _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh),
-                                      float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, _dt(q), _stream())
+    rc = _lib.lib().svol_attn_fwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                          _ptr(lse2), _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws),
+                                          ws.numel() * 4 if ws is not None else 0, p, seed, _dt(q), _stream())
     timer.stop(tok)
     _lib.check(rc, 'svol_attn_fwd')
     return o, lse2
@@ -464,21 +459,14 @@ def attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, pre
         _BIG_ATTN['left'] -= 1
         flush_wgrad(gate=True)   # the queued weight-gradient GEMMs run beside this launch
     delta = torch.empty((3, B, H, Lq), dtype=torch.float32, device=q.device)  # delta | -lse2 pairs | -delta pairs (svol_hip.h)
-    ws = _attn_ws(q, B, H, Lq, Lk, dh, kbias is not None or Lk % 128 != 0)
+    ws = _attn_ws(q, B, H, Lq, Lk, dh)
+    p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
     tok = timer.start('attn_bwd', (B, H, Lq, Lk, dh))
-    if drop is not None and drop[0] > 0.0:
-        rc = _lib.lib().svol_attn_bwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o),
-                                              o.stride(0), _ptr(do), do.stride(0), _ptr(lse2), _ptr(delta), _ptr(kbias),
-                                              _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), B, H, Lq,
-                                              Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws),
-                                              ws.numel() * 4 if ws is not None else 0, float(drop[0]), int(drop[1]), _dt(q),
-                                              _stream())
-    else:
-        rc = _lib.lib().svol_attn_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o),
-                                      o.stride(0), _ptr(do), do.stride(0), _ptr(lse2), _ptr(delta), _ptr(kbias),
-                                      _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), B, H, Lq,
-                                      Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws),
-                                      ws.numel() * 4 if ws is not None else 0, _dt(q), _stream())
+    rc = _lib.lib().svol_attn_bwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                          _ptr(do), do.stride(0), _ptr(lse2), _ptr(delta), _ptr(kbias), _ptr(dq), dq.stride(0),
+                                          _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh),
+                                          float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, p, seed, _dt(q),
+                                          _stream())
     timer.stop(tok)
     _lib.check(rc, 'svol_attn_bwd')
 

@@ -2,8 +2,10 @@
 fault runners (plain torch on the CPU, importable without the device library).  tests/test_attn_range_cases.py holds this file to
 fp64 on the CPU, tests/test_gpu_attn_range.py runs the cases on the device.
 
-1. A dispatch twin: `plan()` restates the plan selection of svol_attn_fwd_bf16_launch / svol_attn_bwd_bf16_launch
-   (csrc/attention_bf16.hip) and names the kernels a launch takes.  CASES holds one smallest shape per plan.
+1. A dispatch twin: `plan()` restates attn_plan (csrc/attention_bf16.hip), the one function svol_attn_fwd_bf16_launch,
+   svol_attn_bwd_bf16_launch and the scratch queries take their decisions from, under the names of its Fwd / Bwd enumerators
+   ('fast2+redo' = fast2_redo, '2pass_m+ksplit' = two_pass_m with bwd_ksplit > 1), and so names the kernels a launch takes.
+   tests/test_abi.py holds ws_floats and sp_shape_ok to the library over a grid of shapes.  CASES holds one smallest shape per plan.
 2. Planted inputs (`make_case`).  check_attention's randn inputs with channel 0 of every head reserved: k[:, 0] = 0 except at planted
    keys (beta), q[:, 0] = 0 except at planted rows (a); a planted row's other channels are scaled by 0.25, so its score (log2 domain)
    is a * beta * f at a planted key (f = 1 for pre-multiplied q, else scale * log2 e) and within a few units of 0 everywhere else.

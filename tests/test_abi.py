@@ -99,6 +99,33 @@ def test_argument_validation_without_gpu():
     assert L.svol_cast(0, 0, 0, 1, 10, 0) == -1
 
 
+def test_attention_scratch_queries_agree_with_the_dispatch_twin():
+    """The launch plan of csrc/attention_bf16.hip (attn_plan) and its twin (tests/attn_range_cases.py) are held together through the
+    two exported scratch queries, over a grid of shapes: svol_attn_ws_bytes is the twin's ws_floats, and with that much scratch the
+    single-pass image (svol_attn_bwd_sp_image_bytes) is there exactly when the twin's shape test holds and the scratch covers the
+    single pass's need; one float less than that need and the image is gone."""
+    if 'SVOL_DETERMINISTIC' in os.environ:
+        pytest.skip('SVOL_DETERMINISTIC is set: the library reads it once and it changes the single-pass shapes')
+    import itertools
+    from svol_amd import _lib
+    from tests import attn_range_cases as A
+    L = _lib.lib()
+    lens = (1, 70, 100, 128, 129, 200, 256, 384, 640, 1024, 1100, 1152, 2048, 6272, 8400)
+    n = images = 0
+    for B, H, Lq, Lk, dh in itertools.product((1, 2, 3, 8), (1, 4, 8, 16), lens, lens, (8, 16, 32)):
+        dims = (B, H, Lq, Lk, dh)
+        ws = int(L.svol_attn_ws_bytes(*dims))
+        assert ws == 4 * A.ws_floats(*dims), dims
+        sp = 4 * A.sp_ws_floats(B, H, Lq, Lk)
+        want = B * Lq * H * 32 * 4 if A.sp_shape_ok(*dims) and ws >= sp else 0
+        assert int(L.svol_attn_bwd_sp_image_bytes(*dims, ws, 1)) == want, dims   # (1: SVOL_BF16)
+        if want:
+            assert int(L.svol_attn_bwd_sp_image_bytes(*dims, sp - 4, 1)) == 0, dims
+            images += 1
+        n += 1
+    assert n == 10800 and images > 0
+
+
 def test_reference_style_cli_trains_the_resnet_backbone_by_default():
     """the reference's shipped runs (train_*.sh: --backbone resnet; train.py:72 optimises every parameter under
     model.train(); its --freeze_backbone is parsed and never read) train the backbone.  A reference command line through
