@@ -210,8 +210,8 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
 // ---- short-sequence attention backward ------------------------------------------------------------------------------
 // One workgroup of 8 waves per (image, head) owns ALL of that head's dQ / dK / dV: no atomics, bit-reproducible.  Q, K, V and
 // dO sit in LDS (same XOR-swizzled images as the forward, 4 x 32 KB at L = 256, dh = 64), with lse2 and
-// delta = rowsum(dO * O) beside them.  P = exp2(s * scale_log2e - lse2) and dS = P (dP - delta) are recomputed in two phases
-// that need no barrier between them (the images are read-only after staging):
+// delta = rowsum(dO * O) beside them (the diagonal of an MFMA dO O^T: the same chain as dP).  P = exp2(s * scale_log2e - lse2)
+// and dS = P (dP - delta) are recomputed in two phases that need no barrier between them (the images are read-only after staging):
 //   key-stationary    wave w owns keys [32w, 32w + 32): X = S[q][key] = mfma(Q rows, K rows) has the key on the lane and the
 //                     queries in the registers, so dV^T += dO^T P and dK^T += Q^T dS take P / dS straight from the
 //                     accumulators (dO^T and Q^T through ds_read_tr16_b64, as V in the forward)
@@ -285,8 +285,12 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
     const bf16_t* dO = p.dout + row0 * p.lddo + hh * DH;
     const float* lse = p.lse2 + ((int64_t)seq * p.H + hh) * p.L;
     const int Lp = p.nkb * 32;
-    // stage Q, K, V, dO (zero rows past L); delta of a row = the sum over its CPR chunks, which sit in CPR consecutive lanes
-    // (Lp * CPR is a multiple of 128: every wave is wholly inside or outside the loop, the shuffles see full waves)
+    // this wave's O rows (block `wave`: nkb <= 8 waves have one) as MFMA B fragments, in flight while the images are staged
+    const int orow = wave * 32 + r;
+    uint4 ob[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) ob[ks] = ld16_or_zero(O + (int64_t)orow * p.ldo + (ks * 2 + h) * 8, orow < p.L);
+    // stage Q, K, V, dO (zero rows past L)
     for (int c = tid; c < Lp * CPR; c += 512) {
         const int row = c / CPR, ch = c % CPR;
         const bool valid = row < p.L;
@@ -294,21 +298,31 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
         const uint4 kv = ld16_or_zero(K + (int64_t)row * p.ldk + ch * 8, valid);
         const uint4 vv = ld16_or_zero(V + (int64_t)row * p.ldv + ch * 8, valid);
         const uint4 dv = ld16_or_zero(dO + (int64_t)row * p.lddo + ch * 8, valid);
-        const uint4 ov = ld16_or_zero(O + (int64_t)row * p.ldo + ch * 8, valid);
         *reinterpret_cast<uint4*>(sQ + img_off<DH>(row, ch)) = qv;
         *reinterpret_cast<uint4*>(sK + img_off<DH>(row, ch)) = kv;
         *reinterpret_cast<uint4*>(sV + img_off<DH>(row, ch)) = vv;
         *reinterpret_cast<uint4*>(sD + img_off<DH>(row, ch)) = dv;
-        const bf16x8 a = __builtin_bit_cast(bf16x8, dv), b = __builtin_bit_cast(bf16x8, ov);
-        float part = 0.f;
+        if (ch == 0) sLse[row] = valid ? lse[row] : 0.f;
+    }
+    __syncthreads();
+    // delta of wave w's 32 rows = the diagonal of dO O^T, from the SAME MFMA chain that forms dP = dO V^T below: where P is one-hot,
+    // O is a V row bit for bit and dP - delta is then exactly 0, which an fma chain over the same products is not.  Element [m][m]
+    // sits on lane m + 32 ((m >> 2) & 1) in register 4 (m >> 3) + (m & 3).
+    if (wave < p.nkb) {
+        f32x16 D;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) part = __builtin_fmaf((float)a[j], (float)b[j], part);
+        for (int i = 0; i < 16; ++i) D[i] = 0.f;
 #pragma unroll
-        for (int off = 1; off < CPR; off <<= 1) part += __shfl_xor(part, off, 64);
-        if (ch == 0) {
-            sDel[row] = part;
-            sLse[row] = valid ? lse[row] : 0.f;
+        for (int ks = 0; ks < KS; ++ks) {
+            const uint4 da = row_frag<DH>(sD, orow, ks * 2 + h);
+            D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, da), __builtin_bit_cast(bf16x8, ob[ks]), D, 0, 0, 0);
         }
+        const int idx = 4 * (r >> 3) + (r & 3);
+        float dl = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (i == idx) dl = D[i];
+        if (h == ((r >> 2) & 1)) sDel[orow] = dl;
     }
     __syncthreads();
     const float c2 = p.scale_log2e;

@@ -74,12 +74,12 @@ def _span(i, blk, n):
     return f'{i * blk}:{min((i + 1) * blk, n)}'
 
 
-def _partitions(kind, shape, heads):
+def _partitions(kind, shape, heads, row_block=TILE):
     """-> [(view shape [B, R, C], row block, column block, namer(b, r, c))] for one tensor kind."""
     if kind == 'act':                      # [B, L, D]
         B, L, D = shape
         dh = D // heads
-        return [((B, L, D), TILE, dh, lambda b, r, c: f'b={b}, head={c}, rows {_span(r, TILE, L)}')]
+        return [((B, L, D), row_block, dh, lambda b, r, c: f'b={b}, head={c}, rows {_span(r, row_block, L)}')]
     if kind == 'bd':                       # [B, D]
         B, D = shape
         dh = D // heads
@@ -120,9 +120,10 @@ def param_kind(name):
     return 'vector'
 
 
-def compare(label, got, ref, kind, heads, ref_norm=None):
+def compare(label, got, ref, kind, heads, ref_norm=None, row_block=TILE):
     """SliceResult of ``got`` against ``ref`` on the partition ``kind`` ('act', 'bd', a param_kind).  ``ref_norm`` replaces ||R|| in
-    the floor where the reference is exactly zero (the norm of a related gradient sets the scale)."""
+    the floor where the reference is exactly zero (the norm of a related gradient sets the scale).  ``row_block``: the rows of an
+    'act' tile (the short-sequence attention kernels work in 32-row blocks)."""
     ref = ref.detach().to(torch.float64)
     got = got.detach().to(device=ref.device, dtype=torch.float64)
     assert got.shape == ref.shape, (label, tuple(got.shape), tuple(ref.shape))
@@ -133,7 +134,7 @@ def compare(label, got, ref, kind, heads, ref_norm=None):
     rmax = float(ref.abs().max())
     elem = float(diff.abs().max()) / max(rmax, 1e-300)
     worst, where = -1.0, ''
-    for vshape, rb, cb, namer in _partitions(kind, tuple(ref.shape), heads):
+    for vshape, rb, cb, namer in _partitions(kind, tuple(ref.shape), heads, row_block):
         e, w = _worst(diff.reshape(vshape), ref.reshape(vshape), rb, cb, namer, ref_norm)
         if e > worst:
             worst, where = e, w
