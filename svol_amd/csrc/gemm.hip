@@ -12,9 +12,7 @@
 // element types: bf16 feeds v_mfma_f32_16x16x32_bf16 (one MFMA per chunk-group of 4 chunks), f32
 // feeds v_mfma_f32_16x16x4_f32 (four MFMAs per chunk group, element e of every lane's chunk) —
 // the contraction index permutation is identical for A and B so the sum is unchanged.
-#include <cstdlib>
-
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -573,11 +571,11 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_skinny(SkArgs p) {
 
 // the shapes the skinny fp32 kernel takes: few rows, K a multiple of 128 (four waves x 32-deep batches), N a multiple of 32,
 // 16-byte aligned rows everywhere
-inline bool skinny_f32_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* A, const void* B,
-                          const void* C) {
+inline bool skinny_f32_ok(const GemmCall& c) {
     constexpr int64_t max_m = 2048;   // (8192 would put the fp32 heads of the bf16 mode, M = 4800, on this kernel: -0.07 ms per step — but also the fp32 mode's video GEMMs at B = 1, whose summation order the golden assignments are pinned on)
-    return M <= max_m && K % 128 == 0 && N % 32 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(A) &&
-           aligned16(B) && aligned16(C) && (M + 31) / 32 <= 65535;
+    auto rows16 = [](const void* p, int64_t ld) { return !p || (ld % 4 == 0 && aligned16(p)); };   // an optional operand's rows
+    return c.kwrap == c.K && c.M <= max_m && c.K % 128 == 0 && c.N % 32 == 0 && c.lda % 4 == 0 && c.ldb % 4 == 0 && c.ldc % 4 == 0 && aligned16(c.A) &&
+           aligned16(c.B) && aligned16(c.C) && (c.M + 31) / 32 <= 65535 && rows16(c.res, c.ldr) && rows16(c.pre, c.ldp) && rows16(c.aux, c.ldaux);
 }
 
 inline int grid_1d(int64_t n, int block) {
@@ -587,29 +585,12 @@ inline int grid_1d(int64_t n, int block) {
 
 }  // namespace
 
-// bf16 fast path (gemm_bf16.hip)
-int svol_gemm_tn_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum,
-                           int64_t Mc, int64_t N, int64_t K, hipStream_t s);
-int svol_gemm_nt_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias,
-                           int act, void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux,
-                           int64_t ldaux, float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K,
-                           int64_t kwrap, hipStream_t s);
-
-int svol_gemm_tn_f16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum,
-                          int64_t Mc, int64_t N, int64_t K, hipStream_t s);
-int svol_gemm_tn_bf16_grouped(const svol_tn_problem* pr, int n, hipStream_t s);
-int svol_gemm_tn_f16_grouped(const svol_tn_problem* pr, int n, hipStream_t s);
-int svol_gemm_nt_f16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias,
-                          int act, void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux,
-                          int64_t ldaux, float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K,
-                          int64_t kwrap, hipStream_t s);
-
 // split plan of the generic TN kernel (shared by svol_gemm_tn and svol_gemm_tn_grouped)
-static int tn_generic_plan(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum, int64_t Mc,
-                           int64_t N, int64_t K, int dtype, TnArgs& out, int64_t& wgs) {
+static int tn_generic_plan(const svol_tn_problem& q, int dtype, TnArgs& out, int64_t& wgs) {
+    const int64_t Mc = q.Mc, N = q.N, K = q.K;
     const int epc = svol_is16(dtype) ? 8 : 4;
-    if (N % epc || K % epc || lda % epc || ldb % epc) return SVOL_E_UNSUPPORTED;
-    if (!aligned16(A) || !aligned16(B)) return SVOL_E_INVALID;
+    if (N % epc || K % epc || q.lda % epc || q.ldb % epc) return SVOL_E_UNSUPPORTED;
+    if (!aligned16(q.A) || !aligned16(q.B)) return SVOL_E_INVALID;
     if (Mc > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return SVOL_E_UNSUPPORTED;
     const int ct = svol_is16(dtype) ? 64 : 32;
     const int64_t tiles = ((N + 127) / 128) * ((K + 127) / 128);
@@ -639,7 +620,7 @@ static int tn_generic_plan(const void* A, int64_t lda, const void* B, int64_t ld
     }
     const int64_t ktiles = (K + 127) / 128;
     if (splits * tiles > (1ll << 30)) return SVOL_E_UNSUPPORTED;
-    out = TnArgs{A, B, C, colsum, lda, ldb, ldc, (int)Mc, (int)N, (int)K, (int)chunk, (int)ktiles, (int)splits};
+    out = TnArgs{q.A, q.B, q.C, q.colsum, q.lda, q.ldb, q.ldc, (int)Mc, (int)N, (int)K, (int)chunk, (int)ktiles, (int)splits};
     wgs = splits * tiles;
     return SVOL_OK;
 }
@@ -658,50 +639,55 @@ const char* svol_strerror(int code) {
     }
 }
 
-static int gemm_nt_impl(const void* A, int64_t lda, const void* A2, int64_t n_split, const void* B, int64_t ldb, void* C,
-                        int64_t ldc, const float* bias, const float* colscale, int act, void* pre_act_out, int64_t ldp,
-                        const void* residual, int64_t ldr, int out_f32, int64_t M, int64_t N, int64_t K, int64_t kwrap, int dtype,
-                        void* stream) {
-    if (!A || !B || !C || M < 0 || N < 0 || K <= 0) return SVOL_E_INVALID;
-    if (act == SVOL_ACT_GELU_D && !pre_act_out) return SVOL_E_INVALID;   // the derivative is what this variant exists to save
+// One NT product through the cascade of gemm_call.h.  A2 / n_split (the generic kernel's alone) and the element type ride beside
+// the record; svol_gemm_nt, svol_gemm_nt_split and svol_gemm_nt_dact only fill it in.
+static int gemm_nt_dispatch(const GemmCall& c, const void* A2, int64_t n_split, int dtype) {
+    const int64_t M = c.M, N = c.N, K = c.K;
+    if (!c.A || !c.B || !c.C || (c.epi && !c.aux) || M < 0 || N < 0 || K <= 0) return SVOL_E_INVALID;
+    const bool act_ok = c.epi ? (c.act == SVOL_ACT_GELU || c.act == SVOL_ACT_RELU || c.act == SVOL_ACT_GELU_D) : (c.act != SVOL_ACT_GELU_D || c.pre);
+    if (!act_ok) return SVOL_E_INVALID;   // (epi 0, GELU_D without `pre`: the derivative is what that variant exists to save)
     if (M == 0 || N == 0) return SVOL_OK;
-    const int epc = svol_is16(dtype) ? 8 : 4;
-    if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
-    if (K % epc || lda % epc || ldb % epc) return SVOL_E_UNSUPPORTED;
-    if (!aligned16(A) || !aligned16(B) || (A2 && !aligned16(A2))) return SVOL_E_INVALID;
-    if (A2 && (n_split % 128)) return SVOL_E_UNSUPPORTED;
-    if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return SVOL_E_UNSUPPORTED;
-    NtArgs p{A, A2, B, C, bias, colscale, pre_act_out, residual, lda, ldb, ldc, ldr, ldp, n_split, (int)M, (int)N, (int)K, act, (int)kwrap};
-    dim3 grid((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128));
-    if (grid.y > 65535u) return SVOL_E_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (c.epi && c.colsum && svol_deterministic()) {   // the fused column sums meet through atomics in arrival order: a single-adder pass instead
+        GemmCall d = c; d.colsum = nullptr;
+        const int rc = gemm_nt_dispatch(d, A2, n_split, dtype);
+        return rc ? rc : svol_colsum(c.C, c.ldc, c.colsum, M, N, dtype, c.stream);
+    }
+    if (!c.epi) {   // (epi 1 has always met these checks where it ends: in the plain product of its generic composition)
+        const int epc = svol_is16(dtype) ? 8 : 4;
+        if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
+        if (K % epc || c.lda % epc || c.ldb % epc) return SVOL_E_UNSUPPORTED;
+        if (!aligned16(c.A) || !aligned16(c.B) || (A2 && !aligned16(A2))) return SVOL_E_INVALID;
+        if (A2 && (n_split % 128)) return SVOL_E_UNSUPPORTED;
+        if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return SVOL_E_UNSUPPORTED;
+        if ((M + 127) / 128 > 65535) return SVOL_E_UNSUPPORTED;
+    }
     if (svol_is16(dtype) && !A2) {
-        const int rc = (dtype == SVOL_BF16 ? svol_gemm_nt_bf16_fast : svol_gemm_nt_f16_fast)(
-            A, lda, B, ldb, C, ldc, bias, act, pre_act_out, ldp, residual, ldr, out_f32, nullptr, 0, nullptr, 0, colscale, M, N, K, kwrap, s);
+        const int rc = (dtype == SVOL_BF16 ? svol_gemm_nt_bf16_fast : svol_gemm_nt_f16_fast)(c);
         if (rc != SVOL_E_UNSUPPORTED) return rc;
     }
-    if (dtype == SVOL_F32 && !A2 && kwrap == K && skinny_f32_ok(M, N, K, lda, ldb, ldc, A, B, C) && (!residual || (ldr % 4 == 0 && aligned16(residual))) &&
-        (!pre_act_out || (ldp % 4 == 0 && aligned16(pre_act_out)))) {
-        SkArgs q{(const float*)A, (const float*)B, (float*)C, bias, colscale, (float*)pre_act_out, (const float*)residual, nullptr,
-                 nullptr, lda, ldb, ldc, ldp, ldr, 0, (int)M, (int)N, (int)K, act, 0};
-        hipLaunchKernelGGL(gemm_nt_f32_skinny, dim3((unsigned)(N / 32), (unsigned)((M + 31) / 32)), dim3(256), 0, s, q);
+    if (dtype == SVOL_F32 && !A2 && skinny_f32_ok(c)) {
+        SkArgs q{(const float*)c.A, (const float*)c.B, (float*)c.C, c.bias, c.colscale, (float*)c.pre, (const float*)c.res, (const float*)c.aux,
+                 c.colsum, c.lda, c.ldb, c.ldc, c.ldp, c.ldr, c.ldaux, (int)M, (int)N, (int)K, c.act, c.epi};
+        hipLaunchKernelGGL(gemm_nt_f32_skinny, dim3((unsigned)(N / 32), (unsigned)((M + 31) / 32)), dim3(256), 0, c.stream, q);
         SVOL_CHECK_LAUNCH();
         return SVOL_OK;
     }
+    if (c.epi) {   // generic composition (f32 / odd shapes): the plain product, then dpre = dh * act'(aux) in place, then column sums
+        if (c.ldc != N || c.ldaux != N) return SVOL_E_UNSUPPORTED;
+        GemmCall g = c;
+        g.aux = nullptr; g.ldaux = 0; g.colsum = nullptr; g.act = SVOL_ACT_NONE; g.epi = 0;
+        if (const int rc = gemm_nt_dispatch(g, nullptr, 0, dtype)) return rc;
+        if (const int rc = svol_act_bwd(c.C, c.aux, c.C, c.act, M * N, dtype, c.stream)) return rc;
+        return c.colsum ? svol_colsum(c.C, c.ldc, c.colsum, M, N, dtype, c.stream) : SVOL_OK;
+    }
+    NtArgs p{c.A, A2, c.B, c.C, c.bias, c.colscale, c.pre, c.res, c.lda, c.ldb, c.ldc, c.ldr, c.ldp, n_split, (int)M, (int)N, (int)K, c.act, (int)c.kwrap};
+    const dim3 grid((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128)), g64((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
     // 64x64 tiles when the 128x128 tiling would leave most of the 256 CUs idle (the fp32 heads: M = 4800, N = 256 -> 76 workgroups)
     const bool small = (int64_t)grid.x * grid.y < 256 && (M + 63) / 64 <= 65535;
-    const dim3 g64((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
-    if (dtype == SVOL_BF16) {
-        if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, s, p);
-    } else if (dtype == SVOL_F16) {
-        if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<f16_t, float>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<f16_t, f16_t>), grid, dim3(256), 0, s, p);
-    } else if (small) {
-        hipLaunchKernelGGL((gemm_nt_kernel<float, float, 64>), g64, dim3(256), 0, s, p);
-    } else {
-        hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, dim3(256), 0, s, p);
-    }
+    void (*kern)(NtArgs) = dtype == SVOL_BF16 ? (c.out_f32 ? gemm_nt_kernel<bf16_t, float> : gemm_nt_kernel<bf16_t, bf16_t>)
+                           : dtype == SVOL_F16 ? (c.out_f32 ? gemm_nt_kernel<f16_t, float> : gemm_nt_kernel<f16_t, f16_t>)
+                           : small ? gemm_nt_kernel<float, float, 64> : gemm_nt_kernel<float, float>;
+    hipLaunchKernelGGL(kern, dtype == SVOL_F32 && small ? g64 : grid, dim3(256), 0, c.stream, p);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
@@ -709,49 +695,31 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* A2, int64_t n_sp
 int svol_gemm_nt(const void* A, int64_t lda, const void* A2, int64_t n_split, const void* B, int64_t ldb, void* C,
                  int64_t ldc, const float* bias, const float* colscale, int act, void* pre_act_out, int64_t ldp,
                  const void* residual, int64_t ldr, int out_f32, int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
-    return gemm_nt_impl(A, lda, A2, n_split, B, ldb, C, ldc, bias, colscale, act, pre_act_out, ldp, residual, ldr, out_f32, M, N, K, K,
-                        dtype, stream);
+    GemmCall c{};
+    c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.C = C; c.ldc = ldc; c.pre = pre_act_out; c.ldp = ldp; c.res = residual; c.ldr = ldr;
+    c.bias = bias; c.colscale = colscale; c.act = act; c.out_f32 = out_f32; c.M = M; c.N = N; c.K = K; c.kwrap = K;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
+    return gemm_nt_dispatch(c, A2, n_split, dtype);
 }
 
 // C = A (W_hi + W_lo)^T + bias as ONE K-concatenated product [A | A] [W_hi | W_lo]^T: the kernels wrap A's contraction index
 int svol_gemm_nt_split(const void* A, int64_t lda, const void* W_hilo, int64_t ldw, void* C, int64_t ldc, const float* bias,
                        int64_t M, int64_t N, int64_t K, void* stream) {
     if (K <= 0 || K % 8) return SVOL_E_UNSUPPORTED;
-    return gemm_nt_impl(A, lda, nullptr, 0, W_hilo, ldw, C, ldc, bias, nullptr, SVOL_ACT_NONE, nullptr, 0, nullptr, 0, 0, M, N, 2 * K, K,
-                        SVOL_BF16, stream);
+    GemmCall c{};
+    c.A = A; c.lda = lda; c.B = W_hilo; c.ldb = ldw; c.C = C; c.ldc = ldc; c.bias = bias;
+    c.M = M; c.N = N; c.K = 2 * K; c.kwrap = K;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
+    return gemm_nt_dispatch(c, nullptr, 0, SVOL_BF16);
 }
 
 int svol_gemm_nt_dact(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* aux,
                       int64_t ldaux, int act, float* colsum, int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
-    if (!A || !B || !C || !aux || M < 0 || N < 0 || K <= 0) return SVOL_E_INVALID;
-    if (act != SVOL_ACT_GELU && act != SVOL_ACT_RELU && act != SVOL_ACT_GELU_D) return SVOL_E_INVALID;
-    if (M == 0 || N == 0) return SVOL_OK;
-    if (colsum && svol_deterministic()) {   // the fused column sums meet through atomics in arrival order: a single-adder pass instead
-        const int rc = svol_gemm_nt_dact(A, lda, B, ldb, C, ldc, aux, ldaux, act, nullptr, M, N, K, dtype, stream);
-        return rc ? rc : svol_colsum(C, ldc, colsum, M, N, dtype, stream);
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (svol_is16(dtype)) {
-        const int rc = (dtype == SVOL_BF16 ? svol_gemm_nt_bf16_fast : svol_gemm_nt_f16_fast)(
-            A, lda, B, ldb, C, ldc, nullptr, act, nullptr, 0, nullptr, 0, 0, aux, ldaux, colsum, 1, nullptr, M, N, K, K, s);
-        if (rc != SVOL_E_UNSUPPORTED) return rc;
-    }
-    if (dtype == SVOL_F32 && skinny_f32_ok(M, N, K, lda, ldb, ldc, A, B, C) && ldaux % 4 == 0 && aligned16(aux)) {
-        SkArgs q{(const float*)A, (const float*)B, (float*)C, nullptr, nullptr, nullptr, nullptr, (const float*)aux, colsum,
-                 lda, ldb, ldc, 0, 0, ldaux, (int)M, (int)N, (int)K, act, 1};
-        hipLaunchKernelGGL(gemm_nt_f32_skinny, dim3((unsigned)(N / 32), (unsigned)((M + 31) / 32)), dim3(256), 0, s, q);
-        SVOL_CHECK_LAUNCH();
-        return SVOL_OK;
-    }
-    // generic composition (f32 / odd shapes): GEMM, then dpre = dh * act'(aux) in place, then column sums
-    if (ldc != N || ldaux != N) return SVOL_E_UNSUPPORTED;
-    int rc = svol_gemm_nt(A, lda, nullptr, 0, B, ldb, C, ldc, nullptr, nullptr, SVOL_ACT_NONE, nullptr, 0, nullptr, 0, 0, M, N, K,
-                          dtype, stream);
-    if (rc) return rc;
-    rc = svol_act_bwd(C, aux, C, act, M * N, dtype, stream);
-    if (rc) return rc;
-    if (colsum) rc = svol_colsum(C, ldc, colsum, M, N, dtype, stream);
-    return rc;
+    GemmCall c{};
+    c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.C = C; c.ldc = ldc; c.aux = aux; c.ldaux = ldaux; c.colsum = colsum;
+    c.M = M; c.N = N; c.K = K; c.kwrap = K; c.act = act; c.epi = 1;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
+    return gemm_nt_dispatch(c, nullptr, 0, dtype);
 }
 
 int svol_gemm_nt_dgelu(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* pre,
@@ -759,28 +727,28 @@ int svol_gemm_nt_dgelu(const void* A, int64_t lda, const void* B, int64_t ldb, v
     return svol_gemm_nt_dact(A, lda, B, ldb, C, ldc, pre, ldp, SVOL_ACT_GELU, colsum, M, N, K, dtype, stream);
 }
 
-int svol_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum, int64_t Mc,
-                 int64_t N, int64_t K, int dtype, void* stream) {
-    if (!A || !B || !C || Mc < 0 || N <= 0 || K <= 0) return SVOL_E_INVALID;
-    if (Mc == 0) return SVOL_OK;
+// one TN product: the 16-bit fast kernel where it fits (gemm_call.h), else the generic one
+static int gemm_tn_dispatch(const svol_tn_problem& q, int dtype, hipStream_t s) {
+    if (!q.A || !q.B || !q.C || q.Mc < 0 || q.N <= 0 || q.K <= 0) return SVOL_E_INVALID;
+    if (q.Mc == 0) return SVOL_OK;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     if (svol_is16(dtype)) {
-        const int rc = (dtype == SVOL_BF16 ? svol_gemm_tn_bf16_fast : svol_gemm_tn_f16_fast)(A, lda, B, ldb, C, ldc, colsum, Mc, N, K,
-                                                                                              reinterpret_cast<hipStream_t>(stream));
+        const int rc = (dtype == SVOL_BF16 ? svol_gemm_tn_bf16_fast : svol_gemm_tn_f16_fast)(q, s);
         if (rc != SVOL_E_UNSUPPORTED) return rc;
     }
     TnArgs p{};
     int64_t wgs = 0;
-    const int prc = tn_generic_plan(A, lda, B, ldb, C, ldc, colsum, Mc, N, K, dtype, p, wgs);
-    if (prc) return prc;
-    const int64_t splits = 1, tiles = wgs;
-    dim3 grid((unsigned)(splits * tiles));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == SVOL_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(256), 0, s, p);
-    else if (dtype == SVOL_F16) hipLaunchKernelGGL(gemm_tn_kernel<f16_t>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, dim3(256), 0, s, p);
+    if (const int rc = tn_generic_plan(q, dtype, p, wgs)) return rc;
+    if (dtype == SVOL_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, dim3((unsigned)wgs), dim3(256), 0, s, p);
+    else if (dtype == SVOL_F16) hipLaunchKernelGGL(gemm_tn_kernel<f16_t>, dim3((unsigned)wgs), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(gemm_tn_kernel<float>, dim3((unsigned)wgs), dim3(256), 0, s, p);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
+}
+
+int svol_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum, int64_t Mc,
+                 int64_t N, int64_t K, int dtype, void* stream) {
+    return gemm_tn_dispatch(svol_tn_problem{A, lda, B, ldb, C, ldc, colsum, Mc, N, K}, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
 int svol_gemm_tn_grouped(const svol_tn_problem* pr, int32_t n, int dtype, void* stream) {
@@ -801,8 +769,7 @@ int svol_gemm_tn_grouped(const svol_tn_problem* pr, int32_t n, int dtype, void* 
             rc = SVOL_OK;
             for (int i = 0; i < m && rc == SVOL_OK; ++i) {
                 int64_t wgs = 0;
-                const svol_tn_problem& q = pr[i0 + i];
-                rc = tn_generic_plan(q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.colsum, q.Mc, q.N, q.K, dtype, g.a[i], wgs);
+                rc = tn_generic_plan(pr[i0 + i], dtype, g.a[i], wgs);
                 g.begin[i] = (int)tot;
                 tot += wgs;
             }
@@ -816,8 +783,7 @@ int svol_gemm_tn_grouped(const svol_tn_problem* pr, int32_t n, int dtype, void* 
         }
         if (rc == SVOL_E_UNSUPPORTED) {   // one by one (odd shapes, a single problem)
             for (int i = 0; i < m; ++i) {
-                const svol_tn_problem& q = pr[i0 + i];
-                const int r1 = svol_gemm_tn(q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.colsum, q.Mc, q.N, q.K, dtype, stream);
+                const int r1 = gemm_tn_dispatch(pr[i0 + i], dtype, s);
                 if (r1) return r1;
             }
         } else if (rc) {

@@ -16,9 +16,7 @@
 //    coalesced side;
 //  * fused backward epilogue: out = acc * gelu'(pre) plus per-column sums (the bias gradient), which
 //    removes a 205 MB read-modify-write pass and a column-sum pass per MLP.
-#include <cstdlib>
-
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -417,61 +415,53 @@ __device__ __forceinline__ void gemm_nt_bf16_skinny_body(const FastArgs& p) {
 __global__ __launch_bounds__(256) void gemm_nt_bf16_skinny_f32(FastArgs p) { gemm_nt_bf16_skinny_body<float>(p); }
 __global__ __launch_bounds__(256) void gemm_nt_bf16_skinny_b16(FastArgs p) { gemm_nt_bf16_skinny_body<h16_t>(p); }
 
-}  // namespace
-
-int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
-                      void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux, int64_t ldaux,
-                      float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K, hipStream_t s);
-
-int svol_gemm_n256_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
-                        void* pre, const void* res, int64_t ldr, int out_f32, int epi, const float* colscale, int64_t M,
-                        int64_t N, int64_t K, int64_t kwrap, hipStream_t s);
-
-// launcher used by gemm.hip's C-ABI entry points.  Returns SVOL_E_UNSUPPORTED when the shape does not
-// qualify (the caller then uses the generic kernel).
-int svol_gemm_nt_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias,
-                           int act, void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux,
-                           int64_t ldaux, float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K,
-                           int64_t kwrap, hipStream_t s) {
+// what every 16-bit family needs of a call (each adds its own conditions in its plan)
+bool fast_fits(const GemmCall& c) {
     // kwrap != K: the split-weight product C = A [W_hi | W_lo]^T, K = 2 * kwrap, A has kwrap columns (svol_gemm_nt_split)
-    if (kwrap != K && (2 * kwrap != K || kwrap % 32)) return SVOL_E_UNSUPPORTED;
-    if (K % 32 || lda % 8 || ldb % 8 || !aligned16(A) || !aligned16(B)) return SVOL_E_UNSUPPORTED;
-    // vector epilogue needs 8-byte (bf16) / 16-byte (f32) aligned rows; otherwise the scalar tail path is used per lane
-    if ((int64_t)128 * lda * 2 >= (1ll << 31) || (int64_t)128 * ldb * 2 >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
-    const int celt = out_f32 ? 4 : 2;
-    if ((ldc * celt) % (4 * celt) || (reinterpret_cast<uintptr_t>(C) % (4 * celt))) return SVOL_E_UNSUPPORTED;
-    if (res && ((ldr * celt) % (4 * celt) || (reinterpret_cast<uintptr_t>(res) % (4 * celt)))) return SVOL_E_UNSUPPORTED;
-    if (pre && (ldp % 4 || (reinterpret_cast<uintptr_t>(pre) % 8))) return SVOL_E_UNSUPPORTED;
-    if (aux && (ldaux % 4 || (reinterpret_cast<uintptr_t>(aux) % 8))) return SVOL_E_UNSUPPORTED;
-    FastArgs p{(const h16_t*)A, (const h16_t*)B, C, bias, colscale, (h16_t*)pre, res, (const h16_t*)aux, colsum,
-               lda, ldb, ldc, ldp, ldr, ldaux, (int)M, (int)N, (int)K, act, epi};
-    p.kwrap = (int)kwrap;
-    if (kwrap == K) {   // K = 256, tall M: weight-stationary kernel (gemm_ws_bf16.hip)
-        const int rc = svol_gemm_ws_bf16(A, lda, B, ldb, C, ldc, bias, act, pre, ldp, res, ldr, out_f32, aux, ldaux, colsum, epi,
-                                         colscale, M, N, K, s);
-        if (rc != SVOL_E_UNSUPPORTED) return rc;
-    }
-    {   // N = 256, deep K, tall M: full-width tiles (gemm_n256_bf16.hip)
-        const int rc = svol_gemm_n256_bf16(A, lda, B, ldb, C, ldc, bias, act, pre, res, ldr, out_f32, epi, colscale, M, N, K, kwrap, s);
-        if (rc != SVOL_E_UNSUPPORTED) return rc;
-    }
-    if (M <= 2048 && K % 256 == 0 && N % SK_BN == 0 && kwrap % (K / 4) == 0) {
-        dim3 g((unsigned)(N / SK_BN), (unsigned)((M + SK_BM - 1) / SK_BM));
-        if (out_f32) hipLaunchKernelGGL(gemm_nt_bf16_skinny_f32, g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(gemm_nt_bf16_skinny_b16, g, dim3(256), 0, s, p);
-        return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
-    }
-    dim3 grid((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128));
-    if (grid.y > 65535u) return SVOL_E_UNSUPPORTED;
+    if (c.kwrap != c.K && (2 * c.kwrap != c.K || c.kwrap % 32)) return false;
+    if (c.K % 32 || c.lda % 8 || c.ldb % 8 || !aligned16(c.A) || !aligned16(c.B)) return false;
+    if ((int64_t)128 * c.lda * 2 >= (1ll << 31) || (int64_t)128 * c.ldb * 2 >= (1ll << 31)) return false;
+    // vector epilogue: 8-byte (bf16) / 16-byte (f32) aligned rows
+    const int celt = c.out_f32 ? 4 : 2;
+    if ((c.ldc * celt) % (4 * celt) || (reinterpret_cast<uintptr_t>(c.C) % (4 * celt))) return false;
+    if (c.res && ((c.ldr * celt) % (4 * celt) || (reinterpret_cast<uintptr_t>(c.res) % (4 * celt)))) return false;
+    if (c.pre && (c.ldp % 4 || (reinterpret_cast<uintptr_t>(c.pre) % 8))) return false;
+    if (c.aux && (c.ldaux % 4 || (reinterpret_cast<uintptr_t>(c.aux) % 8))) return false;
+    return true;
+}
+
+// plans of the two families of this file (both take FastArgs): null (the call does not fit) or the kernel, with its grid
+typedef void (*FastKernel)(FastArgs);
+FastKernel skinny_plan(const GemmCall& c, dim3& grid) {
+    if (c.M > 2048 || c.K % 256 || c.N % SK_BN || c.kwrap % (c.K / 4)) return nullptr;
+    grid = dim3((unsigned)(c.N / SK_BN), (unsigned)((c.M + SK_BM - 1) / SK_BM));
+    return c.out_f32 ? gemm_nt_bf16_skinny_f32 : gemm_nt_bf16_skinny_b16;
+}
+FastKernel tile_plan(const GemmCall& c, dim3& grid) {
+    grid = dim3((unsigned)((c.N + 127) / 128), (unsigned)((c.M + 127) / 128));
+    if (grid.y > 65535u) return nullptr;
     // K-step 32 keeps the two-stage ring at 32 KiB per workgroup (4-5 workgroups per CU hide the DMA latency of the
     // short K = 256 loops); deep-K launches use 64-deep steps (half the barriers)
-    if (K % 64 == 0 && K >= 1024 && kwrap % 64 == 0) {
-        if (out_f32) hipLaunchKernelGGL(gemm_nt_bf16_f32_k64, grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(gemm_nt_bf16_b16_k64, grid, dim3(256), 0, s, p);
-    } else {
-        if (out_f32) hipLaunchKernelGGL(gemm_nt_bf16_f32_k32, grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(gemm_nt_bf16_b16_k32, grid, dim3(256), 0, s, p);
-    }
+    if (c.K % 64 == 0 && c.K >= 1024 && c.kwrap % 64 == 0) return c.out_f32 ? gemm_nt_bf16_f32_k64 : gemm_nt_bf16_b16_k64;
+    return c.out_f32 ? gemm_nt_bf16_f32_k32 : gemm_nt_bf16_b16_k32;
+}
+
+}  // namespace
+
+// The 16-bit families in priority order (gemm_call.h); SVOL_E_UNSUPPORTED when none takes the call (gemm.hip then goes on).
+int svol_gemm_nt_bf16_fast(const GemmCall& c) {
+    if (!fast_fits(c)) return SVOL_E_UNSUPPORTED;
+    int rc = svol_gemm_ws_bf16(c);                                  // K = 256, tall M: weight-stationary (gemm_ws_bf16.hip)
+    if (rc == SVOL_E_UNSUPPORTED) rc = svol_gemm_n256_bf16(c);      // N % 256 == 0, deep K, tall M: full-width tiles (gemm_n256_bf16.hip)
+    if (rc != SVOL_E_UNSUPPORTED) return rc;
+    dim3 grid;
+    FastKernel kern = skinny_plan(c, grid);                         // few rows: split-K inside the workgroup
+    if (!kern) kern = tile_plan(c, grid);                           // 128 x 128 tiles
+    if (!kern) return SVOL_E_UNSUPPORTED;
+    FastArgs p{(const h16_t*)c.A, (const h16_t*)c.B, c.C, c.bias, c.colscale, (h16_t*)c.pre, c.res, (const h16_t*)c.aux, c.colsum,
+               c.lda, c.ldb, c.ldc, c.ldp, c.ldr, c.ldaux, (int)c.M, (int)c.N, (int)c.K, c.act, c.epi};
+    p.kwrap = (int)c.kwrap;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, c.stream, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
 

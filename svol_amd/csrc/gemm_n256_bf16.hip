@@ -11,10 +11,9 @@
 //    (the loop is unrolled over the ring), 12 ds_read_b128 per wave for 32 MFMAs;
 //  * operands swapped and W's rows permuted in its LDS image (as in gemm_ws_bf16.hip) so that a lane owns 8
 //    consecutive output columns: bias / fp32 residual / 16-byte stores straight from the accumulators.
-#include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -202,27 +201,30 @@ __global__ __launch_bounds__(256, 2) void gemm_n256_bf16_b16(N256Args p) { gemm_
 
 }  // namespace
 
-// launcher used by gemm_bf16.hip's fast-path dispatcher.  Returns SVOL_E_UNSUPPORTED when the call does not fit.
-int svol_gemm_n256_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
-                        void* pre, const void* res, int64_t ldr, int out_f32, int epi, const float* colscale, int64_t M,
-                        int64_t N, int64_t K, int64_t kwrap, hipStream_t s) {
+// plan of one call: refuses it (the call does not fit, gemm_call.h) or yields the kernel arguments and the grid
+static int n256_plan(const GemmCall& c, N256Args& p, dim3& grid) {
+    const int64_t M = c.M, N = c.N, K = c.K;
     if (N % BN || K % BK || K < 512 || M < 4096) return SVOL_E_UNSUPPORTED;
-    if (epi != 0 || pre || colscale) return SVOL_E_UNSUPPORTED;
-    if (kwrap != K && (kwrap % BK || 2 * kwrap != K)) return SVOL_E_UNSUPPORTED;
-    if (act != SVOL_ACT_NONE && ((act != SVOL_ACT_GELU && act != SVOL_ACT_RELU) || out_f32)) return SVOL_E_UNSUPPORTED;   // (GELU_D: needs `pre`, not here)
-    if (res && !out_f32) return SVOL_E_UNSUPPORTED;
-    auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-    if (lda % 8 || ldw % 8 || !al16(A) || !al16(W) || !al16(C)) return SVOL_E_UNSUPPORTED;
-    if (out_f32 ? (ldc % 4 || (res && (ldr % 4 || !al16(res)))) : (ldc % 8 != 0)) return SVOL_E_UNSUPPORTED;
-    if ((int64_t)BM * lda * 2 >= (1ll << 31) || (int64_t)BN * ldw * 2 >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
+    if (c.epi != 0 || c.pre || c.colscale) return SVOL_E_UNSUPPORTED;
+    if (c.kwrap != K && (c.kwrap % BK || 2 * c.kwrap != K)) return SVOL_E_UNSUPPORTED;
+    if (c.act != SVOL_ACT_NONE && ((c.act != SVOL_ACT_GELU && c.act != SVOL_ACT_RELU) || c.out_f32)) return SVOL_E_UNSUPPORTED;   // (GELU_D: needs `pre`, not here)
+    if (c.res && !c.out_f32) return SVOL_E_UNSUPPORTED;
+    if (c.lda % 8 || c.ldb % 8 || !aligned16(c.A) || !aligned16(c.B) || !aligned16(c.C)) return SVOL_E_UNSUPPORTED;
+    if (c.out_f32 ? (c.ldc % 4 || (c.res && (c.ldr % 4 || !aligned16(c.res)))) : (c.ldc % 8 != 0)) return SVOL_E_UNSUPPORTED;
+    if ((int64_t)BM * c.lda * 2 >= (1ll << 31) || (int64_t)BN * c.ldb * 2 >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
     const int64_t ncg = N / BN;
     int64_t nrt = (M + BM - 1) / BM;
     if (ncg > 1) nrt = (nrt + 7) / 8 * 8;
     if (nrt * ncg > (1ll << 30)) return SVOL_E_UNSUPPORTED;
-    N256Args p{(const h16_t*)A, (const h16_t*)W, C, bias, (const float*)res, lda, ldw, ldc, ldr, (int)M, (int)K, act, (int)nrt,
-               (int)(kwrap / BK)};
-    dim3 grid((unsigned)(nrt * ncg));
-    if (out_f32) hipLaunchKernelGGL(gemm_n256_bf16_f32, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gemm_n256_bf16_b16, grid, dim3(256), 0, s, p);
+    p = N256Args{(const h16_t*)c.A, (const h16_t*)c.B, c.C, c.bias, (const float*)c.res, c.lda, c.ldb, c.ldc, c.ldr, (int)M, (int)K, c.act,
+                 (int)nrt, (int)(c.kwrap / BK)};
+    grid = dim3((unsigned)(nrt * ncg));
+    return SVOL_OK;
+}
+
+int svol_gemm_n256_bf16(const GemmCall& c) {
+    N256Args p; dim3 grid;
+    if (const int rc = n256_plan(c, p, grid)) return rc;
+    hipLaunchKernelGGL(c.out_f32 ? gemm_n256_bf16_f32 : gemm_n256_bf16_b16, grid, dim3(256), 0, c.stream, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }

@@ -16,9 +16,7 @@
 //    output elements that are masked at the final atomics;
 //  * split-M over workgroups with fp32 atomics as before; the bias gradient (column sums of A) rides
 //    the matrix pipe (A^T * ones) in the k-tile-0 workgroups.
-#include <cstdlib>
-
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -286,9 +284,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_dma_grouped(TnGroupArgs g
 }
 
 // split plan of one problem (shared by the single and the grouped launcher); false = the shape does not qualify
-bool tn_plan(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum, int64_t Mc, int64_t N,
-             int64_t K, TnFastArgs& out, int64_t& wgs, int wgs_override = 0) {
-    if (N % 8 || K % 8 || lda % 8 || ldb % 8 || !aligned16(A) || !aligned16(B)) return false;
+bool tn_plan(const svol_tn_problem& q, TnFastArgs& out, int64_t& wgs, int wgs_override = 0) {
+    const int64_t Mc = q.Mc, N = q.N, K = q.K, lda = q.lda, ldb = q.ldb;
+    if (N % 8 || K % 8 || lda % 8 || ldb % 8 || !aligned16(q.A) || !aligned16(q.B)) return false;
     if (Mc < 1 || Mc > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return false;
     const int64_t tiles = ((N + 127) / 128) * ((K + 127) / 128);
     // split the contraction: every split ends in fp32 atomics over its whole output tile, and the kernel shares the chip with the
@@ -314,7 +312,7 @@ bool tn_plan(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, i
     if (splits < 8) split_major = false;       // (short problems: the row chunks have a minimum length)
     const int64_t ldmax = lda > ldb ? lda : ldb;
     if (chunk * ldmax * 2 >= (1ll << 31)) return false;  // 32-bit buffer offsets
-    out = TnFastArgs{(const h16_t*)A, (const h16_t*)B, C, colsum, lda, ldb, ldc, (int)Mc, (int)N, (int)K, (int)chunk,
+    out = TnFastArgs{(const h16_t*)q.A, (const h16_t*)q.B, q.C, q.colsum, lda, ldb, q.ldc, (int)Mc, (int)N, (int)K, (int)chunk,
                      (int)((K + 127) / 128), (int)splits, split_major ? 1 : 0};
     if (split_major) wgs = ((splits + 7) / 8) * 8 * tiles;
     else wgs = ((splits * ((N + 127) / 128) + 7) / 8) * 8 * ((K + 127) / 128);   // items padded to whole groups of 8 (tn_dma_body)
@@ -331,8 +329,7 @@ int svol_gemm_tn_bf16_grouped(const svol_tn_problem* pr, int n, hipStream_t s) {
     int64_t tot = 0;
     for (int i = 0; i < n; ++i) {
         int64_t wgs = 0;
-        if (!tn_plan(pr[i].A, pr[i].lda, pr[i].B, pr[i].ldb, pr[i].C, pr[i].ldc, pr[i].colsum, pr[i].Mc, pr[i].N, pr[i].K, g.a[i], wgs))
-            return SVOL_E_UNSUPPORTED;
+        if (!tn_plan(pr[i], g.a[i], wgs)) return SVOL_E_UNSUPPORTED;
         g.begin[i] = (int)tot;
         tot += wgs;
     }
@@ -354,18 +351,18 @@ int svol_conv_wgrad_bf16_fast(const void* dz, const void* x, float* dwp, int64_t
     // the convolutions' weight gradients are most of the backbone's backward, not a side dish beside an attention kernel: fill the chip
     // (measured in profiles/round5_resnet_train_kernel_stats.txt)
     constexpr int conv_wgs = 256;   // 128 -> 34.2, 256 -> 29.6, 512 -> 29.9, 1024 -> 30.6 ms per step
-    if (!tn_plan(dz, Cout, x, 8, dwp, Kp, nullptr, M, Cout, Kp, a.t, wgs, conv_wgs)) return SVOL_E_UNSUPPORTED;   // (ldb is not used by the gather)
+    const svol_tn_problem q{dz, Cout, x, 8, dwp, Kp, nullptr, M, Cout, Kp};   // (ldb is not used by the gather)
+    if (!tn_plan(q, a.t, wgs, conv_wgs)) return SVOL_E_UNSUPPORTED;
     a.g = TnConvGeom{(int)H, (int)W, (int)C, (int)Ho, (int)Wo, (int)kw, (int)stride, (int)pad, (int)K, (int)(N * H * W * C * 2)};
     hipLaunchKernelGGL(gemm_tn_bf16_conv, dim3((unsigned)wgs), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
 
 // launcher used by gemm.hip's svol_gemm_tn.  Returns SVOL_E_UNSUPPORTED when the shape does not qualify.
-int svol_gemm_tn_bf16_fast(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum,
-                           int64_t Mc, int64_t N, int64_t K, hipStream_t s) {
+int svol_gemm_tn_bf16_fast(const svol_tn_problem& q, hipStream_t s) {
     TnFastArgs p{};
     int64_t wgs = 0;
-    if (!tn_plan(A, lda, B, ldb, C, ldc, colsum, Mc, N, K, p, wgs)) return SVOL_E_UNSUPPORTED;
+    if (!tn_plan(q, p, wgs)) return SVOL_E_UNSUPPORTED;
     hipLaunchKernelGGL(gemm_tn_bf16_dma, dim3((unsigned)wgs), dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }

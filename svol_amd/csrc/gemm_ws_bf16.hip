@@ -17,9 +17,7 @@
 //  * operands the epilogue needs per element (the fp32 residual stream, the saved pre-activation of the
 //    GELU backward) ride the same ring as extra slab planes, so nothing is loaded "late" (a late load would
 //    force every older DMA to retire first).
-#include <cstdlib>
-
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -604,28 +602,27 @@ WSP_KERNEL(gemm_wsp_bf16_drelu, 2, SVOL_ACT_RELU, false, false, 3)
 
 }  // namespace
 
-// launcher used by gemm_bf16.hip's fast-path dispatcher.  Returns SVOL_E_UNSUPPORTED when the call does not fit.
-int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const float* bias, int act,
-                      void* pre, int64_t ldp, const void* res, int64_t ldr, int out_f32, const void* aux, int64_t ldaux,
-                      float* colsum, int epi, const float* colscale, int64_t M, int64_t N, int64_t K, hipStream_t s) {
-    if (K != WS_K || N % 64 || M < 4096) return SVOL_E_UNSUPPORTED;
+// plan of one call: refuses it (SVOL_E_UNSUPPORTED: the call does not fit, gemm_call.h) or yields the kernel, its arguments and the grid
+static int ws_plan(const GemmCall& c, WsArgs& p, dim3& grid, void (*&kern)(WsArgs)) {
+    const int64_t M = c.M, N = c.N;
+    const int act = c.act;
+    if (c.kwrap != c.K || c.K != WS_K || N % 64 || M < 4096) return SVOL_E_UNSUPPORTED;
     int mode;
-    if (epi == 1) {
-        if (!aux || out_f32) return SVOL_E_UNSUPPORTED;
+    if (c.epi == 1) {
+        if (!c.aux || c.out_f32) return SVOL_E_UNSUPPORTED;
         mode = 2;
-    } else if (out_f32) {
-        if (!res || act != SVOL_ACT_NONE || pre || colscale) return SVOL_E_UNSUPPORTED;
+    } else if (c.out_f32) {
+        if (!c.res || act != SVOL_ACT_NONE || c.pre || c.colscale) return SVOL_E_UNSUPPORTED;
         mode = 1;
     } else {
-        if (res || (act != SVOL_ACT_NONE && act != SVOL_ACT_GELU && act != SVOL_ACT_RELU && act != SVOL_ACT_GELU_D)) return SVOL_E_UNSUPPORTED;
-        if (act == SVOL_ACT_GELU_D && !pre) return SVOL_E_INVALID;
+        if (c.res || (act != SVOL_ACT_NONE && act != SVOL_ACT_GELU && act != SVOL_ACT_RELU && act != SVOL_ACT_GELU_D)) return SVOL_E_UNSUPPORTED;
+        if (act == SVOL_ACT_GELU_D && !c.pre) return SVOL_E_INVALID;
         mode = 0;
     }
-    auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-    if (lda % 8 || ldw % 8 || !al16(A) || !al16(W) || !al16(C)) return SVOL_E_UNSUPPORTED;
-    if (mode == 1 ? (ldc % 4 || ldr % 4 || !al16(res)) : (ldc % 8 != 0)) return SVOL_E_UNSUPPORTED;
-    if (pre && (ldp % 8 || !al16(pre))) return SVOL_E_UNSUPPORTED;
-    if (mode == 2 && (ldaux % 8 || !al16(aux))) return SVOL_E_UNSUPPORTED;
+    if (c.lda % 8 || c.ldb % 8 || !aligned16(c.A) || !aligned16(c.B) || !aligned16(c.C)) return SVOL_E_UNSUPPORTED;
+    if (mode == 1 ? (c.ldc % 4 || c.ldr % 4 || !aligned16(c.res)) : (c.ldc % 8 != 0)) return SVOL_E_UNSUPPORTED;
+    if (c.pre && (c.ldp % 8 || !aligned16(c.pre))) return SVOL_E_UNSUPPORTED;
+    if (mode == 2 && (c.ldaux % 8 || !aligned16(c.aux))) return SVOL_E_UNSUPPORTED;
     const int64_t ntile = (M + TR - 1) / TR;
     const int64_t ncg = (N + 255) / 256;
     // slabs per workgroup: every workgroup first reads its 128 KiB slice of W, so few long-lived workgroups win as
@@ -633,10 +630,10 @@ int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, vo
     int64_t tpw = (ntile * ncg + (ncg <= 2 ? 255 : 511)) / (ncg <= 2 ? 256 : 512);
     if (tpw < 4) tpw = 4;
     if (tpw > 64) tpw = 64;
-    const int64_t ldmax = lda > ldr * 2 ? lda : ldr * 2;
-    int64_t ldbig = ldmax > ldaux ? ldmax : ldaux;  // 32-bit buffer offsets inside one workgroup's rows (loads and stores)
-    if (ldc > ldbig) ldbig = ldc;
-    if (pre && ldp > ldbig) ldbig = ldp;
+    const int64_t ldmax = c.lda > c.ldr * 2 ? c.lda : c.ldr * 2;
+    int64_t ldbig = ldmax > c.ldaux ? ldmax : c.ldaux;  // 32-bit buffer offsets inside one workgroup's rows (loads and stores)
+    if (c.ldc > ldbig) ldbig = c.ldc;
+    if (c.pre && c.ldp > ldbig) ldbig = c.ldp;
     if (tpw * TR * ldbig * 2 >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
     int64_t nchunk = (ntile + tpw - 1) / tpw;
     if (ncg > 1 && nchunk > 8 && nchunk % 8) {  // a multiple of the 8 XCDs when column groups share rows
@@ -645,21 +642,24 @@ int svol_gemm_ws_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, vo
         if (t8 >= 1 && (ntile + t8 - 1) / t8 == n8) { tpw = t8; nchunk = n8; }
     }
     if (nchunk * ncg > (1ll << 30)) return SVOL_E_UNSUPPORTED;
-    WsArgs p{(const h16_t*)A, (const h16_t*)W, C, bias, colscale, (h16_t*)pre, res, (const h16_t*)aux, colsum,
-             lda, ldw, ldc, ldp, ldr, ldaux, (int)M, (int)N, act, (int)tpw, (int)nchunk};
-    dim3 grid((unsigned)(ncg * nchunk));
-    void (*kp)(WsArgs) = nullptr;   // the pipelined kernels, where one exists for the mode and epilogue
-    if (mode == 0) {
-        if (act == SVOL_ACT_NONE && !pre) kp = colscale ? gemm_wsp_bf16_none_scale : gemm_wsp_bf16_none;
-        else if (act == SVOL_ACT_GELU && !colscale) kp = pre ? gemm_wsp_bf16_gelu_pre : gemm_wsp_bf16_gelu;
-        else if (act == SVOL_ACT_GELU_D && !colscale) kp = gemm_wsp_bf16_gelu_dpre;
-        else if (act == SVOL_ACT_RELU && !pre && !colscale) kp = gemm_wsp_bf16_relu;
+    p = WsArgs{(const h16_t*)c.A, (const h16_t*)c.B, c.C, c.bias, c.colscale, (h16_t*)c.pre, c.res, (const h16_t*)c.aux, c.colsum,
+               c.lda, c.ldb, c.ldc, c.ldp, c.ldr, c.ldaux, (int)M, (int)N, act, (int)tpw, (int)nchunk};
+    grid = dim3((unsigned)(ncg * nchunk));
+    kern = mode == 0 ? gemm_ws_bf16_m0 : (mode == 1 ? gemm_ws_bf16_m1 : gemm_ws_bf16_m2);
+    if (mode == 0) {   // the pipelined kernels, where one exists for the mode and epilogue
+        if (act == SVOL_ACT_NONE && !c.pre) kern = c.colscale ? gemm_wsp_bf16_none_scale : gemm_wsp_bf16_none;
+        else if (act == SVOL_ACT_GELU && !c.colscale) kern = c.pre ? gemm_wsp_bf16_gelu_pre : gemm_wsp_bf16_gelu;
+        else if (act == SVOL_ACT_GELU_D && !c.colscale) kern = gemm_wsp_bf16_gelu_dpre;
+        else if (act == SVOL_ACT_RELU && !c.pre && !c.colscale) kern = gemm_wsp_bf16_relu;
     } else if (mode == 2) {
-        kp = act == SVOL_ACT_RELU ? gemm_wsp_bf16_drelu : (act == SVOL_ACT_GELU_D ? gemm_wsp_bf16_dmul : gemm_wsp_bf16_dgelu);
+        kern = act == SVOL_ACT_RELU ? gemm_wsp_bf16_drelu : (act == SVOL_ACT_GELU_D ? gemm_wsp_bf16_dmul : gemm_wsp_bf16_dgelu);
     }
-    if (kp) hipLaunchKernelGGL(kp, grid, dim3(256), 0, s, p);
-    else if (mode == 0) hipLaunchKernelGGL(gemm_ws_bf16_m0, grid, dim3(256), 0, s, p);
-    else if (mode == 1) hipLaunchKernelGGL(gemm_ws_bf16_m1, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gemm_ws_bf16_m2, grid, dim3(256), 0, s, p);
+    return SVOL_OK;
+}
+
+int svol_gemm_ws_bf16(const GemmCall& c) {
+    WsArgs p; dim3 grid; void (*kern)(WsArgs);   // (ws_plan sets all three or refuses)
+    if (const int rc = ws_plan(c, p, grid, kern)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, c.stream, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }

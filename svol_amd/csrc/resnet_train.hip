@@ -15,7 +15,7 @@
 //
 // The column reductions meet their workgroups' partials through fp32 atomics; under SVOL_DETERMINISTIC=1 through rows of a scratch
 // folded in index order (common.h).
-#include "common.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -320,12 +320,6 @@ int64_t reduce_wgs(int64_t M, int64_t C, int64_t& rows_per_wg) {
 }
 
 }  // namespace
-
-// gemm_tn_bf16.hip (compiled once per 16-bit type)
-int svol_conv_wgrad_bf16_fast(const void* dz, const void* x, float* dwp, int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh,
-                              int64_t kw, int64_t stride, int64_t pad, int64_t Kp, hipStream_t stream);
-int svol_conv_wgrad_f16_fast(const void* dz, const void* x, float* dwp, int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh,
-                             int64_t kw, int64_t stride, int64_t pad, int64_t Kp, hipStream_t stream);
 
 extern "C" {
 

@@ -99,6 +99,92 @@ def test_argument_validation_without_gpu():
     assert L.svol_cast(0, 0, 0, 1, 10, 0) == -1
 
 
+def test_gemm_entries_refuse_before_any_launch():
+    """The refusal contract of the five GEMM entry points (csrc/gemm.hip and the 16-bit families behind it), as a table: every call
+    below returns before a kernel is launched, and its code is written out.  Non-null operands are small integers used as addresses
+    (nothing dereferences them on the host); the grouped records live in a real host array.  Entries that set two faults pin the order
+    of precedence.  With a GPU present the test skips itself: an entry that a later change stopped refusing would otherwise launch a
+    kernel on a made-up address."""
+    if torch.cuda.is_available():
+        pytest.skip('made-up addresses: only safe where a launch cannot happen')
+    import ctypes
+    from svol_amd import _lib
+    L = _lib.lib()
+    F32, BF16, F16, NODT = 0, 1, 2, 7
+    NONE, RELU, GELU, SIGMOID, RELU_RES, GELU_D = 0, 1, 2, 3, 4, 5
+    PA, PB, PC, PX, ODD = 0x1000, 0x2000, 0x3000, 0x4000, 0x5008   # ODD: 8 bytes off the 16-byte grid
+    BIG = (1 << 30) + 64
+
+    def nt(A=PA, lda=64, A2=0, n_split=0, B=PB, ldb=64, C=PC, ldc=64, bias=0, colscale=0, act=NONE, pre=0, ldp=0, res=0, ldr=0,
+           out_f32=0, M=4, N=64, K=64, dtype=BF16):
+        return L.svol_gemm_nt(A, lda, A2, n_split, B, ldb, C, ldc, bias, colscale, act, pre, ldp, res, ldr, out_f32, M, N, K, dtype, 0)
+
+    def split(A=PA, lda=64, W=PB, ldw=128, C=PC, ldc=64, bias=0, M=4, N=64, K=64):
+        return L.svol_gemm_nt_split(A, lda, W, ldw, C, ldc, bias, M, N, K, 0)
+
+    def dact(A=PA, lda=64, B=PB, ldb=64, C=PC, ldc=64, aux=PX, ldaux=64, act=GELU, colsum=0, M=4, N=64, K=64, dtype=BF16):
+        return L.svol_gemm_nt_dact(A, lda, B, ldb, C, ldc, aux, ldaux, act, colsum, M, N, K, dtype, 0)
+
+    def tn(A=PA, lda=64, B=PB, ldb=64, C=PC, ldc=64, colsum=0, Mc=128, N=64, K=64, dtype=BF16):
+        return L.svol_gemm_tn(A, lda, B, ldb, C, ldc, colsum, Mc, N, K, dtype, 0)
+
+    def grouped(recs, dtype=BF16, n=None, null=False):   # recs: keyword overrides of one valid record each
+        arr = (_lib.TnProblem * max(len(recs), 1))()
+        for i, kw in enumerate(recs):
+            r = dict(A=PA, lda=64, B=PB, ldb=64, C=PC, ldc=64, colsum=0, Mc=128, N=64, K=64)
+            r.update(kw)
+            arr[i] = _lib.TnProblem(r['A'], r['lda'], r['B'], r['ldb'], r['C'], r['ldc'], r['colsum'], r['Mc'], r['N'], r['K'])
+        return L.svol_gemm_tn_grouped(0 if null else ctypes.cast(arr, ctypes.c_void_p), len(recs) if n is None else n, dtype, 0)
+
+    table = [
+        # svol_gemm_nt: null operands, negative sizes, K <= 0
+        (nt, dict(A=0), -1), (nt, dict(B=0), -1), (nt, dict(C=0), -1), (nt, dict(M=-1), -1), (nt, dict(N=-1), -1),
+        (nt, dict(K=0), -1), (nt, dict(K=-8), -1),
+        # GELU_D without `pre` (before the empty product), the empty product (before the dtype), an unknown dtype (before the grid)
+        (nt, dict(act=GELU_D), -1), (nt, dict(act=GELU_D, M=0), -1), (nt, dict(M=0), 0), (nt, dict(N=0), 0),
+        (nt, dict(M=0, dtype=NODT), 0), (nt, dict(dtype=NODT), -1), (nt, dict(dtype=NODT, K=60), -1),
+        # K / leading dimensions off the 16-byte grid (before pointer alignment), per element size
+        (nt, dict(K=60), -2), (nt, dict(lda=60), -2), (nt, dict(ldb=60), -2), (nt, dict(K=60, dtype=F16), -2),
+        (nt, dict(K=6, dtype=F32), -2), (nt, dict(lda=6, dtype=F32), -2), (nt, dict(K=60, A=ODD), -2),
+        # misaligned pointers; A2 / n_split
+        (nt, dict(A=ODD), -1), (nt, dict(B=ODD), -1), (nt, dict(A=ODD, dtype=F32), -1), (nt, dict(A2=ODD, n_split=128), -1),
+        (nt, dict(A2=PX, n_split=64), -2), (nt, dict(A2=ODD, n_split=64), -1), (nt, dict(A2=PX, n_split=64, dtype=F32), -2),
+        # sizes above 2^30; more row tiles than a grid takes
+        (nt, dict(M=BIG), -2), (nt, dict(N=BIG), -2), (nt, dict(K=BIG), -2), (nt, dict(M=BIG, dtype=F32), -2),
+        (nt, dict(M=128 * 65535 + 1), -2), (nt, dict(M=128 * 65535 + 1, dtype=F32), -2),
+        # svol_gemm_nt_split: K <= 0 or off the grid is `unsupported` (before the null check), the rest as svol_gemm_nt
+        (split, dict(K=0), -2), (split, dict(K=-8), -2), (split, dict(K=12), -2), (split, dict(K=0, A=0), -2), (split, dict(A=0), -1),
+        (split, dict(W=0), -1), (split, dict(C=0), -1), (split, dict(M=-1), -1), (split, dict(M=0), 0), (split, dict(N=0), 0),
+        (split, dict(lda=60), -2), (split, dict(ldw=124), -2), (split, dict(A=ODD), -1), (split, dict(W=ODD), -1),
+        (split, dict(M=BIG), -2), (split, dict(N=BIG), -2),
+        # svol_gemm_nt_dact: null operands (aux among them), sizes, the activations it does not take (before the empty product)
+        (dact, dict(A=0), -1), (dact, dict(B=0), -1), (dact, dict(C=0), -1), (dact, dict(aux=0), -1), (dact, dict(M=-1), -1),
+        (dact, dict(N=-1), -1), (dact, dict(K=0), -1), (dact, dict(act=NONE), -1), (dact, dict(act=SIGMOID), -1),
+        (dact, dict(act=RELU_RES), -1), (dact, dict(act=9), -1), (dact, dict(act=NONE, M=0), -1), (dact, dict(M=0), 0),
+        (dact, dict(N=0, act=RELU), 0), (dact, dict(M=0, dtype=NODT, colsum=PX), 0),
+        # what no fused kernel takes ends in the generic composition: dense C / aux first, then svol_gemm_nt's own checks
+        (dact, dict(A=ODD), -1), (dact, dict(A=ODD, ldc=128), -2), (dact, dict(A=ODD, ldaux=128), -2), (dact, dict(K=60), -2),
+        (dact, dict(lda=60, act=GELU_D), -2), (dact, dict(dtype=NODT), -1), (dact, dict(dtype=NODT, ldc=128), -2),
+        (dact, dict(K=6, dtype=F32), -2), (dact, dict(A=ODD, dtype=F32), -1), (dact, dict(M=BIG, dtype=F32), -2),
+        (dact, dict(M=BIG), -2), (dact, dict(K=60, dtype=F16, colsum=PX), -2),
+        # svol_gemm_tn: N = 0 is invalid here, Mc = 0 is the empty product (before the dtype)
+        (tn, dict(A=0), -1), (tn, dict(B=0), -1), (tn, dict(C=0), -1), (tn, dict(Mc=-1), -1), (tn, dict(N=0), -1), (tn, dict(K=0), -1),
+        (tn, dict(K=-8), -1), (tn, dict(Mc=0), 0), (tn, dict(Mc=0, dtype=NODT), 0), (tn, dict(dtype=NODT), -1),
+        (tn, dict(N=60), -2), (tn, dict(K=60), -2), (tn, dict(lda=60), -2), (tn, dict(ldb=60), -2), (tn, dict(K=60, A=ODD), -2),
+        (tn, dict(A=ODD), -1), (tn, dict(B=ODD), -1), (tn, dict(Mc=BIG), -2), (tn, dict(N=BIG), -2), (tn, dict(K=BIG), -2),
+        (tn, dict(N=6, dtype=F32), -2), (tn, dict(A=ODD, dtype=F32), -1), (tn, dict(N=BIG, dtype=F32), -2), (tn, dict(K=60, dtype=F16), -2),
+        # svol_gemm_tn_grouped: the array and the count, then each record's own refusal (issued one by one when the group does not fit)
+        (grouped, dict(recs=[{}, {}], null=True), -1), (grouped, dict(recs=[{}, {}], n=-1), -1), (grouped, dict(recs=[{}, {}], dtype=NODT), -1),
+        (grouped, dict(recs=[], n=0), 0), (grouped, dict(recs=[dict(A=0), {}]), -1), (grouped, dict(recs=[dict(Mc=0), dict(K=0)]), -1),
+        (grouped, dict(recs=[dict(A=ODD), dict(A=ODD)]), -1), (grouped, dict(recs=[dict(N=12), dict(N=12)]), -2),
+        (grouped, dict(recs=[dict(N=6), dict(N=6)], dtype=F32), -2), (grouped, dict(recs=[dict(B=ODD)], dtype=F32), -1),
+        (grouped, dict(recs=[dict(Mc=BIG), dict(Mc=BIG)], dtype=F16), -2),
+    ]
+    got = [(fn.__name__, kw, fn(**kw)) for fn, kw, _ in table]
+    assert got == [(fn.__name__, kw, rc) for fn, kw, rc in table]
+    assert len(table) == 112
+
+
 def test_attention_scratch_queries_agree_with_the_dispatch_twin():
     """The launch plan of csrc/attention_bf16.hip (attn_plan) and its twin (tests/attn_range_cases.py) are held together through the
     two exported scratch queries, over a grid of shapes: svol_attn_ws_bytes is the twin's ws_floats, and with that much scratch the
