@@ -8,7 +8,8 @@ order as ``ops.GateFn`` / ``ops.AttnLNFn`` / ``ops.MLPLNFn`` (which stay for the
 
 * the slot tables (one ``void*`` array per block call: parameters and weight copies are filled once per plan, activations per call),
 * the arenas: everything a block saves for backward + its outputs live in ONE allocation, backward temporaries in another,
-* the weight-gradient deferral (``ops.gemm_tn_sink``'s policy, one queue item per block instead of one per GEMM).
+* the call skeleton the three blocks share (``_open`` / ``_open_bwd`` / ``_close_bwd``); their weight gradients are one
+  ``wgrad.issue`` per block instead of one per GEMM.
 
 PyTorch remains plumbing: device memory, streams, the autograd tape.
 """
@@ -21,9 +22,8 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, wgrad
 
-WGRAD_SPLIT = os.environ.get('SVOL_WGRAD_SPLIT') is not None   # measured: +0.16 ms/step (more work beside the attention backward than the shorter tail saves)
 ENABLED = os.environ.get('SVOL_NO_BLOCKS') is None
 # SVOL_GATE_SCORES_FUSE=1: layer i's LN3 also writes layer i + 1's gate scores (svol_layernorm_gate_scores_fwd) and that layer skips its
 # own score pass — same bits (tests/test_gpu_head.py).  OFF by default: alone the pair of launches is 25 us per layer shorter
@@ -116,9 +116,8 @@ def _dims(B, L, N, D, H, F, dt, qdt, ws_bytes):
     return (ctypes.c_int64 * 9)(B, L, N, D, H, F, ops._DT[dt], ops._DT[qdt], ws_bytes)
 
 
-def _attn_ws_bytes(B, H, Lq, Lk, dh, dt):
-    n = _lib.lib().svol_attn_ws_bytes(B, H, Lq, Lk, dh) if dt != torch.float32 else 0
-    return max(int(n), 0)
+def _c(t):
+    return t if t is None or t.is_contiguous() else t.contiguous()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -166,64 +165,33 @@ class BlockPlan:
         self.casts = []    # (weight, dtype, wc, wt) / (weight, row0, rows, ws): the copies whose POINTERS sit in the template
         self.epoch = W.epoch
 
-        def both(name, w, dtype, name_t=None):
+        def both(name, w, dtype):
             wc, wt = W.get(w, dtype)
             t.set_t(name, wc)
-            t.set_t(name_t or (name + '_T'), wt)
+            t.set_t(name + '_T', wt)
             self.keep += [wc, wt]
             self.casts.append((w, dtype, wc, wt))
 
-        def qscale(dtype, n):
-            if dtype == torch.float32:
-                return None
+        wdt = dt if block == VH else qdt   # the block's GEMMs run in the dtype of the stream they belong to,
+        adt = qdt if block == QS else dt   # its attention core in that of its keys (ops.AttnLNFn: premul follows dkv)
+        for slot, p in zip(self.grad_slots, self.params):   # the forward slot is the gradient slot without its 'D'
+            if p.dim() == 1:
+                t.set_t(slot[1:], p)
+            elif block == QC and slot == 'DW_IN':   # one weight, two readers: the queries' projection and the video's K | V
+                both('W_INQ', p, qdt)
+                both('W_KV', p, dt)
+            else:
+                both(slot[1:], p, wdt)
+        if adt == torch.bfloat16 and self.split_v:
+            w_in = self.params[self.grad_slots.index('DW_IN')]
+            hl = W.get_split(w_in, 2 * D, D)
+            t.set_t('WV_HILO', hl)
+            self.keep.append(hl)
+            self.casts.append((w_in, 2 * D, D, hl))
+        if adt != torch.float32:
             q = ops._qscale(D, ops.LOG2E / math.sqrt(D // layer.nhead), dev)
+            t.set_t('QSCALE', q)
             self.keep.append(q)
-            return q
-
-        if block == VH:
-            m, mlp = layer.content_self_attn, layer.mlp1
-            for n_, p_ in (('G1', layer.norm1.weight), ('BT1', layer.norm1.bias), ('G2', layer.norm2.weight), ('BT2', layer.norm2.bias),
-                           ('G3', layer.norm3.weight), ('BT3', layer.norm3.bias), ('B_IN', m.in_proj_bias), ('B_O', m.out_proj.bias),
-                           ('B_FC1', mlp.fc1.bias), ('B_FC2', mlp.fc2.bias)):
-                t.set_t(n_, p_)
-            both('W_IN', m.in_proj_weight, dt)
-            both('W_O', m.out_proj.weight, dt)
-            both('W_FC1', mlp.fc1.weight, dt)
-            both('W_FC2', mlp.fc2.weight, dt)
-            if dt == torch.bfloat16 and self.split_v:
-                hl = W.get_split(m.in_proj_weight, 2 * D, D)
-                t.set_t('WV_HILO', hl)
-                self.keep.append(hl)
-                self.casts.append((m.in_proj_weight, 2 * D, D, hl))
-            t.set_t('QSCALE', qscale(dt, 2 * D))
-        elif block == QS:
-            m = layer.token_self_attn
-            for n_, p_ in (('G4', layer.norm4.weight), ('BT4', layer.norm4.bias), ('B_IN', m.in_proj_bias), ('B_O', m.out_proj.bias)):
-                t.set_t(n_, p_)
-            both('W_IN', m.in_proj_weight, qdt)
-            both('W_O', m.out_proj.weight, qdt)
-            if qdt == torch.bfloat16 and self.split_v:
-                hl = W.get_split(m.in_proj_weight, 2 * D, D)
-                t.set_t('WV_HILO', hl)
-                self.keep.append(hl)
-                self.casts.append((m.in_proj_weight, 2 * D, D, hl))
-            t.set_t('QSCALE', qscale(qdt, 2 * D))
-        else:
-            m, mlp = layer.content_token_cross_attn, layer.mlp2
-            for n_, p_ in (('G5', layer.norm5.weight), ('BT5', layer.norm5.bias), ('G6', layer.norm6.weight), ('BT6', layer.norm6.bias),
-                           ('B_IN', m.in_proj_bias), ('B_O', m.out_proj.bias), ('B_FC1', mlp.fc1.bias), ('B_FC2', mlp.fc2.bias)):
-                t.set_t(n_, p_)
-            both('W_INQ', m.in_proj_weight, qdt)
-            both('W_KV', m.in_proj_weight, dt)
-            both('W_O', m.out_proj.weight, qdt)
-            both('W_FC1', mlp.fc1.weight, qdt)
-            both('W_FC2', mlp.fc2.weight, qdt)
-            if dt == torch.bfloat16 and self.split_v:
-                hl = W.get_split(m.in_proj_weight, 2 * D, D)
-                t.set_t('WV_HILO', hl)
-                self.keep.append(hl)
-                self.casts.append((m.in_proj_weight, 2 * D, D, hl))
-            t.set_t('QSCALE', qscale(dt, D))   # the attention core's dtype decides (ops.AttnLNFn: premul follows dkv)
         # gradient targets: the reducer's bucket views where there are sinks
         self.sinks = [ops._claim(p, p.requires_grad) for p in self.params]
         self.nosink = [(i, p.numel()) for i, (p, s) in enumerate(zip(self.params, self.sinks)) if s is None]
@@ -327,37 +295,63 @@ def plan(layer, block, dt, qdt):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# weight-gradient deferral (policy of ops.gemm_tn_sink, one queue item per block)
+# the call skeleton of the three blocks
 # ----------------------------------------------------------------------------------------------------------------------
-def _issue_wgrad(fn_name, dims, tbl, keep, dev, part=None):
-    """the block's weight-gradient GEMMs: on the weight-gradient stream behind an event when every target is a sink, else in line."""
-    fn = getattr(_lib.lib(), fn_name)
+def _call(name, ctx, *extra, stream=None):
+    """one block program on the current stream (or on the raw handle `stream`)."""
+    rc = getattr(_lib.lib(), name)(ctx.dims, ctx.tbl.arr, *extra, ops._stream() if stream is None else stream)
+    _lib.check(rc, name)
 
-    def run(stream_handle):
-        if part is None:
-            _lib.check(fn(dims, tbl.arr, stream_handle), fn_name)
-        else:
-            _lib.check(fn(dims, tbl.arr, part, stream_handle), fn_name)
 
-    if not ops.WGRAD_ASYNC or (not ops.WGRAD_IN_CAPTURE and torch.cuda.is_current_stream_capturing()):
-        run(ops._stream())
-        return
-    cur = ops._current_stream_obj()
-    ev = torch.cuda.Event()
-    ev.record(cur)
+def _open(ctx, pl, block, key, dims, n_par, dev, fwd_items, scr_items, **inputs):
+    """what every forward does before its C call: this call's table from the plan's template, the arena (everything saved for backward
+    + the outputs) and the stream's scratch laid out in it, the input slots set.  -> the arena's layout"""
+    ctx.set_materialize_grads(False)
+    lay = _layout(('f', block) + key, fwd_items)
+    slay = _layout(('s', block) + key, scr_items)
+    arena = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
+    tbl = _Table(block, pl.tpl)
+    lay.fill(tbl, arena.data_ptr())
+    slay.fill(tbl, _scratch(dev, slay.total).data_ptr())
+    for name, t in inputs.items():
+        tbl.set(name, t.data_ptr())
+    ctx.pl, ctx.tbl, ctx.dims, ctx.arena, ctx.key, ctx.n_par = pl, tbl, dims, arena, (block,) + key, n_par
+    return lay
 
-    def later():
-        ws = ops._wgrad_stream(dev)
-        ws.wait_event(ev)
-        run(ws.cuda_stream)
-        for t in keep:
-            t.record_stream(ws)
 
-    if ops.WGRAD_DEFER and ops._BIG_ATTN['left'] > 0 and not torch.cuda.is_current_stream_capturing():
-        ops._WGRAD_PENDING.append(later)
-        ops.arm_wgrad_flush()
-    else:
-        later()
+def _no_grads(ctx, n_in):
+    """no gradient arrived: the reducer still hears that this block's parameters are done."""
+    ctx.pl.done(ctx.n_par > 0)
+    return (None,) * (n_in + ctx.n_par)
+
+
+def _open_bwd(ctx, dev, bwd_items, **grads):
+    """what every backward does before its C calls: the temporaries laid out in one allocation, the incoming gradients set, the scratch
+    filled in again, zeroed buffers for parameters without a sink.  -> (layout, temporaries, those buffers | None, the gradients as set:
+    contiguous, the None ones left out — the caller holds them until its calls are issued)"""
+    tbl = ctx.tbl
+    lay = _layout(('b',) + ctx.key, bwd_items)
+    tmp = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
+    lay.fill(tbl, tmp.data_ptr())
+    gs = []
+    for name, g in grads.items():
+        g = _c(g)
+        tbl.set_t(name, g)
+        if g is not None:
+            gs.append(g)
+    slay = _layout(('s',) + ctx.key, None)
+    slay.fill(tbl, _scratch(dev, slay.total).data_ptr())
+    return lay, tmp, ctx.pl.grad_buffers(tbl, dev), gs
+
+
+def _close_bwd(ctx, name, bufs, keep, n_in):
+    """the block's weight-gradient GEMMs — one launch group through svol_amd.wgrad when every target is a sink, else in line — and the
+    reducer told.  `keep`: what that group reads.  -> what the Function returns for its parameter inputs"""
+    if bufs is not None or not wgrad.issue(lambda ws: _call(name, ctx, stream=ws.cuda_stream), keep, ops._current_stream_obj()):
+        _call(name, ctx)
+    in_graph = ctx.n_par > 0
+    ctx.pl.done(in_graph)
+    return tuple(ctx.pl.grads_out(bufs, ctx.needs_input_grad[n_in:], in_graph))
 
 
 def _maybe_events(name, meta):
@@ -452,6 +446,11 @@ def _vh_bwd_layout(B, L, D, H, F, e):
             ('GATE_WS2', (B * L + B * H) * 4), ('DX32', M * D * 4)]
 
 
+def _attn_events(tbl, ev):
+    tbl.set('EV_A0', ev[0].cuda_event if ev else None)
+    tbl.set('EV_A1', ev[1].cuda_event if ev else None)
+
+
 class VideoHalfFn(torch.autograd.Function):
     """(m32, m, m + pos) = LN3(. + MLP1(.)) o LN2(. + SelfAttn(.)) o LN1(gate(x32))  — cross_modal_transformer.py:122-143."""
 
@@ -460,7 +459,6 @@ class VideoHalfFn(torch.autograd.Function):
         """u_next: the NEXT layer's gate vectors or None; sc_in: the gate workspace the layer before filled with THIS layer's scores
         (its fourth output) or None.  Fourth output: the next layer's gate workspace (empty when u_next is None) — plain storage,
         not differentiable: the next layer's gate backward differentiates the scores through ITS x32, as it always did."""
-        ctx.set_materialize_grads(False)
         B, L, D = x32.shape
         layer = pl.layer()
         H, F = layer.nhead, layer.mlp1.fc1.weight.shape[0]
@@ -468,24 +466,13 @@ class VideoHalfFn(torch.autograd.Function):
         e = _ESZ[dt]
         dev = x32.device
         M = B * L
-        x2 = x32.reshape(M, D)
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        pos2 = pos.reshape(M, D)
-        pos2 = pos2 if pos2.is_contiguous() else pos2.contiguous()
-        u = u.contiguous()
+        x2, pos2, u = _c(x32.reshape(M, D)), _c(pos.reshape(M, D)), _c(u)
         assert x2.dtype == torch.float32 and pos2.dtype == dt and u.dtype == torch.float32
-        wsb = _attn_ws_bytes(B, H, L, L, D // H, dt)
-        key = (VH, B, L, D, H, F, dt)
-        lay = _layout(('f',) + key, lambda: _vh_fwd_layout(B, L, D, H, F, e))
-        slay = _layout(('s',) + key, lambda: [('Y1_32', M * D * 4), ('Y2_32', M * D * 4), ('ATTN_WS', max(wsb, 16))])
-        arena = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        scr = _scratch(dev, slay.total)
-        tbl = _Table(VH, pl.tpl)
-        lay.fill(tbl, arena.data_ptr())
-        slay.fill(tbl, scr.data_ptr())
-        tbl.set('X32', x2.data_ptr())
-        tbl.set('POS', pos2.data_ptr())
-        tbl.set('U', u.data_ptr())
+        wsb = ops.attn_ws_bytes(dt, B, H, L, L, D // H)
+        lay = _open(ctx, pl, VH, (B, L, D, H, F, dt), _dims(B, L, 0, D, H, F, dt, dt, wsb), len(params), dev,
+                    lambda: _vh_fwd_layout(B, L, D, H, F, e),
+                    lambda: [('Y1_32', M * D * 4), ('Y2_32', M * D * 4), ('ATTN_WS', max(wsb, 16))], X32=x2, POS=pos2, U=u)
+        tbl = ctx.tbl
         if sc_in is not None:
             assert sc_in.dtype == torch.float32 and sc_in.numel() == B * H * (L + 2) and sc_in.is_contiguous()
             tbl.set('GATE_WS', sc_in.data_ptr())
@@ -498,86 +485,44 @@ class VideoHalfFn(torch.autograd.Function):
             tbl.set('GATE_WS_NEXT', sc_next.data_ptr())
         else:
             sc_next = torch.empty((0,), dtype=torch.float32, device=dev)
-        dims = _dims(B, L, 0, D, H, F, dt, dt, wsb)
-        big = B * H * L * L >= ops._WGRAD_FLUSH_MIN_SCORES
-        if big:
-            ops._BIG_ATTN['left'] += 1
-        ev = _maybe_events('attn_fwd', (B, H, L, L, D // H))
-        if ev:
-            tbl.set('EV_A0', ev[0].cuda_event)
-            tbl.set('EV_A1', ev[1].cuda_event)
-        _lib.check(_lib.lib().svol_video_half_fwd(dims, tbl.arr, ops._stream()), 'svol_video_half_fwd')
-        tbl.set('EV_A0', None)
-        tbl.set('EV_A1', None)
+        ctx.big = wgrad.attn_forward(B * H * L * L)
+        _attn_events(tbl, _maybe_events('attn_fwd', (B, H, L, L, D // H)))
+        _call('svol_video_half_fwd', ctx)
+        _attn_events(tbl, None)
         tbl.set('U_NEXT', None)
         tbl.set('GATE_WS_NEXT', None)
-        ctx.pl, ctx.tbl, ctx.dims, ctx.arena, ctx.shape, ctx.big = pl, tbl, dims, arena, (B, L, D, H, F), big
-        ctx.n_par = len(params)
+        ctx.shape = (B, L, D, H, F)
         ctx.sc_in = sc_in   # (GATE_WS of the backward; statistics are written behind the scores: not a saved TENSOR, its version moves)
         ctx.save_for_backward(x2, pos2, u)
         ctx.mark_non_differentiable(sc_next)
-        return (lay.view(arena, 'M32', torch.float32, (B, L, D)), lay.view(arena, 'M', dt, (B, L, D)),
-                lay.view(arena, 'MPOS', dt, (B, L, D)), sc_next)
+        return (lay.view(ctx.arena, 'M32', torch.float32, (B, L, D)), lay.view(ctx.arena, 'M', dt, (B, L, D)),
+                lay.view(ctx.arena, 'MPOS', dt, (B, L, D)), sc_next)
 
     @staticmethod
     def backward(ctx, dm32, dm, dmpos, _dsc=None):
-        pl, tbl, dims = ctx.pl, ctx.tbl, ctx.dims
-        B, L, D, H, F = ctx.shape
-        x2, pos2, u = ctx.saved_tensors
-        n_par = ctx.n_par
         if dm32 is None and dm is None and dmpos is None:
-            pl.done(n_par > 0)
-            return (None,) * (6 + n_par)
-        dt = pl.dt
-        e = _ESZ[dt]
-        dev = x2.device
-        M = B * L
-        cont = lambda t_: None if t_ is None else (t_.reshape(M, D) if t_.is_contiguous() else t_.reshape(M, D).contiguous())
-        dm32, dm, dmpos = cont(dm32), cont(dm), cont(dmpos)
-        lay = _layout(('b', VH, B, L, D, H, F, dt), lambda: _vh_bwd_layout(B, L, D, H, F, e))
-        tmp = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        lay.fill(tbl, tmp.data_ptr())
+            return _no_grads(ctx, 6)
+        tbl = ctx.tbl
+        B, L, D, H, F = ctx.shape
+        dt = ctx.pl.dt
+        dev = ctx.saved_tensors[0].device
         du = torch.zeros((B, H, D), dtype=torch.float32, device=dev)
         tbl.set('DU', du.data_ptr())
-        tbl.set_t('DM32', dm32)
-        tbl.set_t('DM', dm)
-        tbl.set_t('DMPOS', dmpos)
-        slay = _layout(('s', VH, B, L, D, H, F, dt), None)
-        scr = _scratch(dev, slay.total)
-        slay.fill(tbl, scr.data_ptr())
-        bufs = pl.grad_buffers(tbl, dev)
-        L_ = _lib.lib()
-        s = ops._stream()
-        _lib.check(L_.svol_video_half_bwd(dims, tbl.arr, 1, s), 'svol_video_half_bwd')
-        keep = [t_ for t_ in (ctx.arena, tmp, dm32, dm, dmpos) if t_ is not None]
-        split = bufs is None and ctx.big and WGRAD_SPLIT
-        if ctx.big:
-            ops._BIG_ATTN['left'] -= 1
-            if split:   # this layer's MLP / out-proj weight gradients exist already: they go beside ITS attention backward
-                _issue_wgrad('svol_video_half_wgrad_part', dims, tbl, keep, dev, part=1)
-            ops.flush_wgrad(gate=True)   # queued weight-gradient GEMMs run beside the attention backward (issue-bound; they are HBM / atomic bound)
-        ev = _maybe_events('attn_bwd', (B, H, L, L, D // H))
-        if ev:
-            tbl.set('EV_A0', ev[0].cuda_event)
-            tbl.set('EV_A1', ev[1].cuda_event)
-        pz = _dq_prezero(dev, B, H, L, D // H, dt, dims[8]) if ctx.big else None
+        lay, tmp, bufs, gs = _open_bwd(ctx, dev, lambda: _vh_bwd_layout(B, L, D, H, F, _ESZ[dt]), DM32=dm32, DM=dm, DMPOS=dmpos)
+        # two phases, with the flush between them: phase 1 is the chain down to the attention backward's inputs
+        _call('svol_video_half_bwd', ctx, 1)
+        wgrad.attn_backward(B * H * L * L)   # queued weight-gradient GEMMs run beside the attention backward
+        _attn_events(tbl, _maybe_events('attn_bwd', (B, H, L, L, D // H)))
+        pz = _dq_prezero(dev, B, H, L, D // H, dt, ctx.dims[8]) if ctx.big else None
         if pz is not None:
             pz.bind(tbl)
-        _lib.check(L_.svol_video_half_bwd(dims, tbl.arr, 2, s), 'svol_video_half_bwd')
+        _call('svol_video_half_bwd', ctx, 2)
         if pz is not None:
             pz.advance(tbl)
-        tbl.set('EV_A0', None)
-        tbl.set('EV_A1', None)
-        if split:
-            _issue_wgrad('svol_video_half_wgrad_part', dims, tbl, keep, dev, part=2)
-        elif bufs is None:
-            _issue_wgrad('svol_video_half_wgrad', dims, tbl, keep, dev)
-        else:
-            _lib.check(L_.svol_video_half_wgrad(dims, tbl.arr, s), 'svol_video_half_wgrad')
-        pl.done(n_par > 0)
+        _attn_events(tbl, None)
+        pg = _close_bwd(ctx, 'svol_video_half_wgrad', bufs, [ctx.arena, tmp] + gs, 6)
         dx32 = lay.view(tmp, 'DX32', torch.float32, (B, L, D))
-        needs = ctx.needs_input_grad
-        return (None, dx32, None, du if needs[3] else None, None, None) + tuple(pl.grads_out(bufs, needs[6:], n_par > 0))
+        return (None, dx32, None, du if ctx.needs_input_grad[3] else None, None, None) + pg
 
 
 def gate_scores_fusable(L, D, H):
@@ -598,19 +543,20 @@ def video_half(layer, x32, pos, u, dt, u_next=None, sc_in=None):
 # ----------------------------------------------------------------------------------------------------------------------
 # query self-attention
 # ----------------------------------------------------------------------------------------------------------------------
-def _qpos_target(pl, qpos, tbl, dev, N, D):
+def _qpos_target(ctx, qpos, need, N, D):
     """where the gradient of the broadcast query_pos goes: straight into the query embedding's bucket view when qpos IS that
-    parameter (fp32 query stream) and it has a sink, else a zeroed buffer returned to autograd."""
-    if not qpos.requires_grad:
-        tbl.set('DQPOS', None)
-        return None, False
-    s = ops._claim(qpos, True) if (qpos.is_leaf and qpos.dtype == torch.float32) else None
-    if s is not None:
-        tbl.set_t('DQPOS', s.view)
-        return None, True
-    g = torch.zeros((N, D), dtype=torch.float32, device=dev)
-    tbl.set('DQPOS', g.data_ptr())
-    return g, False
+    parameter (fp32 query stream) and it has a sink, else a zeroed buffer returned to autograd (-> that buffer, or None)."""
+    g = s = None
+    if need and qpos.requires_grad:
+        s = ops._claim(qpos, True) if (qpos.is_leaf and qpos.dtype == torch.float32) else None
+        if s is None:
+            g = torch.zeros((N, D), dtype=torch.float32, device=qpos.device)
+    ctx.tbl.set_t('DQPOS', s.view if s is not None else g)
+    return g
+
+
+def _qpos_grad(g, qdt):
+    return ops.cast(g, qdt) if (g is not None and qdt != torch.float32) else g
 
 
 class QuerySelfFn(torch.autograd.Function):
@@ -618,83 +564,38 @@ class QuerySelfFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pl, o32, o, opos, qpos, *params):
-        ctx.set_materialize_grads(False)
         B, N, D = o.shape
-        layer = pl.layer()
-        H = layer.nhead
-        qdt = pl.qdt
-        e = _ESZ[qdt]
-        dev = o.device
-        R = B * N
-        c = lambda t_: t_ if t_.is_contiguous() else t_.contiguous()
-        o32_, o_, opos_, qpos_ = c(o32), c(o), c(opos), c(qpos)
+        H, qdt = pl.layer().nhead, pl.qdt
+        e, R = _ESZ[qdt], B * N
+        o32_, o_, opos_, qpos_ = _c(o32), _c(o), _c(opos), _c(qpos)
         assert o32_.dtype == torch.float32 and o_.dtype == qdt and opos_.dtype == qdt and qpos_.dtype == qdt
-        wsb = _attn_ws_bytes(B, H, N, N, D // H, qdt)
-        key = (QS, B, N, D, H, qdt)
-        lay = _layout(('f',) + key, lambda: [('QKV', R * 3 * D * e), ('OA', R * D * e), ('LSE', B * H * N * 4), ('S4', R * D * 4),
-                                              ('MEAN4', R * 4), ('RSTD4', R * 4), ('Y32', R * D * 4), ('Y', R * D * e), ('YPOS', R * D * e)])
-        slay = _layout(('s',) + key, lambda: [('ATTN_WS', max(wsb, 16))])
-        arena = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        scr = _scratch(dev, slay.total)
-        tbl = _Table(QS, pl.tpl)
-        lay.fill(tbl, arena.data_ptr())
-        slay.fill(tbl, scr.data_ptr())
-        tbl.set('O32', o32_.data_ptr())
-        tbl.set('O', o_.data_ptr())
-        tbl.set('OPOS', opos_.data_ptr())
-        tbl.set('QPOS', qpos_.data_ptr())
-        dims = _dims(B, 0, N, D, H, 0, qdt, qdt, wsb)
-        _lib.check(_lib.lib().svol_query_self_fwd(dims, tbl.arr, ops._stream()), 'svol_query_self_fwd')
-        ctx.pl, ctx.tbl, ctx.dims, ctx.arena, ctx.shape = pl, tbl, dims, arena, (B, N, D, H)
-        ctx.n_par = len(params)
+        wsb = ops.attn_ws_bytes(qdt, B, H, N, N, D // H)
+        lay = _open(ctx, pl, QS, (B, N, D, H, qdt), _dims(B, 0, N, D, H, 0, qdt, qdt, wsb), len(params), o.device,
+                    lambda: [('QKV', R * 3 * D * e), ('OA', R * D * e), ('LSE', B * H * N * 4), ('S4', R * D * 4), ('MEAN4', R * 4),
+                             ('RSTD4', R * 4), ('Y32', R * D * 4), ('Y', R * D * e), ('YPOS', R * D * e)],
+                    lambda: [('ATTN_WS', max(wsb, 16))], O32=o32_, O=o_, OPOS=opos_, QPOS=qpos_)
+        _call('svol_query_self_fwd', ctx)
+        ctx.shape = (B, N, D, H)
         ctx.save_for_backward(o32_, o_, opos_, qpos)
-        return (lay.view(arena, 'Y32', torch.float32, (B, N, D)), lay.view(arena, 'Y', qdt, (B, N, D)),
-                lay.view(arena, 'YPOS', qdt, (B, N, D)))
+        return (lay.view(ctx.arena, 'Y32', torch.float32, (B, N, D)), lay.view(ctx.arena, 'Y', qdt, (B, N, D)),
+                lay.view(ctx.arena, 'YPOS', qdt, (B, N, D)))
 
     @staticmethod
     def backward(ctx, dy32, dy, dypos):
-        pl, tbl, dims = ctx.pl, ctx.tbl, ctx.dims
+        if dy32 is None and dy is None and dypos is None:
+            return _no_grads(ctx, 5)
         B, N, D, H = ctx.shape
         o32_, o_, opos_, qpos = ctx.saved_tensors
-        n_par = ctx.n_par
-        if dy32 is None and dy is None and dypos is None:
-            pl.done(n_par > 0)
-            return (None,) * (5 + n_par)
-        qdt = pl.qdt
-        e = _ESZ[qdt]
-        dev = o_.device
-        R = B * N
-        cont = lambda t_: None if t_ is None else (t_ if t_.is_contiguous() else t_.contiguous())
-        dy32, dy, dypos = cont(dy32), cont(dy), cont(dypos)
-        lay = _layout(('b', QS, B, N, D, H, qdt), lambda: [('G', R * D * e), ('DOA', R * D * e), ('DQKV', R * 3 * D * e),
-                                                            ('DELTA', 3 * B * H * N * 4), ('DO32', R * D * 4), ('DXQ', R * D * e),
-                                                            ('DXQP', R * D * e)])
-        tmp = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        lay.fill(tbl, tmp.data_ptr())
-        tbl.set_t('DY32', dy32)
-        tbl.set_t('DY', dy)
-        tbl.set_t('DYPOS', dypos)
-        slay = _layout(('s', QS, B, N, D, H, qdt), None)
-        scr = _scratch(dev, slay.total)
-        slay.fill(tbl, scr.data_ptr())
-        needs = ctx.needs_input_grad
-        gq, _ = _qpos_target(pl, qpos, tbl, dev, N, D) if needs[4] else (None, False)
-        if not needs[4]:
-            tbl.set('DQPOS', None)
-        bufs = pl.grad_buffers(tbl, dev)
-        L_ = _lib.lib()
-        s = ops._stream()
-        _lib.check(L_.svol_query_self_bwd(dims, tbl.arr, s), 'svol_query_self_bwd')
-        keep = (ctx.arena, tmp, o_, opos_)
-        if bufs is None:
-            _issue_wgrad('svol_query_self_wgrad', dims, tbl, list(keep), dev)
-        else:
-            _lib.check(L_.svol_query_self_wgrad(dims, tbl.arr, s), 'svol_query_self_wgrad')
-        pl.done(n_par > 0)
-        if gq is not None and qdt != torch.float32:
-            gq = ops.cast(gq, qdt)
+        qdt = ctx.pl.qdt
+        e, R = _ESZ[qdt], B * N
+        gq = _qpos_target(ctx, qpos, ctx.needs_input_grad[4], N, D)
+        lay, tmp, bufs, gs = _open_bwd(ctx, o_.device, lambda: [('G', R * D * e), ('DOA', R * D * e), ('DQKV', R * 3 * D * e),
+                                                               ('DELTA', 3 * B * H * N * 4), ('DO32', R * D * 4), ('DXQ', R * D * e),
+                                                               ('DXQP', R * D * e)], DY32=dy32, DY=dy, DYPOS=dypos)
+        _call('svol_query_self_bwd', ctx)
+        pg = _close_bwd(ctx, 'svol_query_self_wgrad', bufs, [ctx.arena, tmp, o_, opos_], 5)
         v = lambda n_, dt_: lay.view(tmp, n_, dt_, (B, N, D))
-        return (None, v('DO32', torch.float32), v('DXQ', qdt), v('DXQP', qdt), gq) + tuple(pl.grads_out(bufs, needs[5:], n_par > 0))
+        return (None, v('DO32', torch.float32), v('DXQ', qdt), v('DXQP', qdt), _qpos_grad(gq, qdt)) + pg
 
 
 def query_self(layer, out, qpos, dt, qdt):
@@ -727,82 +628,40 @@ class QueryCrossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pl, o32, o, opos, mv, mpos, kbias, qpos, *params):
-        ctx.set_materialize_grads(False)
         B, N, D = o.shape
         L = mv.shape[1]
         layer = pl.layer()
         H, F = layer.nhead, layer.mlp2.fc1.weight.shape[0]
         dt, qdt = pl.dt, pl.qdt
         e, qe = _ESZ[dt], _ESZ[qdt]
-        dev = o.device
-        c = lambda t_: t_ if t_.is_contiguous() else t_.contiguous()
-        o32_, o_, opos_, mv_, mpos_, kb_, qpos_ = c(o32), c(o), c(opos), c(mv), c(mpos), c(kbias), c(qpos)
+        o32_, o_, opos_, mv_, mpos_, kb_, qpos_ = _c(o32), _c(o), _c(opos), _c(mv), _c(mpos), _c(kbias), _c(qpos)
         assert o32_.dtype == torch.float32 and o_.dtype == qdt and opos_.dtype == qdt and qpos_.dtype == qdt
         assert mv_.dtype == dt and mpos_.dtype == dt and kb_.dtype == torch.float32
-        wsb = _attn_ws_bytes(B, H, N, L, D // H, dt)
-        key = (QC, B, N, L, D, H, F, dt, qdt)
-        lay = _layout(('f',) + key, lambda: _qc_fwd_layout(B, N, L, D, H, F, e, qe))
-        slay = _layout(('s',) + key, lambda: [('ATTN_WS', max(wsb, 16))])
-        arena = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        scr = _scratch(dev, slay.total)
-        tbl = _Table(QC, pl.tpl)
-        lay.fill(tbl, arena.data_ptr())
-        slay.fill(tbl, scr.data_ptr())
-        for n_, t_ in (('O32', o32_), ('O', o_), ('OPOS', opos_), ('MV', mv_), ('MPOS', mpos_), ('KBIAS', kb_), ('QPOS', qpos_)):
-            tbl.set(n_, t_.data_ptr())
-        dims = _dims(B, L, N, D, H, F, dt, qdt, wsb)
-        _lib.check(_lib.lib().svol_query_cross_fwd(dims, tbl.arr, ops._stream()), 'svol_query_cross_fwd')
-        ctx.pl, ctx.tbl, ctx.dims, ctx.arena, ctx.shape = pl, tbl, dims, arena, (B, N, L, D, H, F)
-        ctx.n_par = len(params)
+        wsb = ops.attn_ws_bytes(dt, B, H, N, L, D // H)
+        lay = _open(ctx, pl, QC, (B, N, L, D, H, F, dt, qdt), _dims(B, L, N, D, H, F, dt, qdt, wsb), len(params), o.device,
+                    lambda: _qc_fwd_layout(B, N, L, D, H, F, e, qe), lambda: [('ATTN_WS', max(wsb, 16))],
+                    O32=o32_, O=o_, OPOS=opos_, MV=mv_, MPOS=mpos_, KBIAS=kb_, QPOS=qpos_)
+        _call('svol_query_cross_fwd', ctx)
+        ctx.shape = (B, N, L, D, H, F)
         ctx.save_for_backward(o32_, o_, opos_, mv_, mpos_, kb_, qpos)
-        return (lay.view(arena, 'Y32', torch.float32, (B, N, D)), lay.view(arena, 'Y', qdt, (B, N, D)),
-                lay.view(arena, 'YPOS', qdt, (B, N, D)))
+        return (lay.view(ctx.arena, 'Y32', torch.float32, (B, N, D)), lay.view(ctx.arena, 'Y', qdt, (B, N, D)),
+                lay.view(ctx.arena, 'YPOS', qdt, (B, N, D)))
 
     @staticmethod
     def backward(ctx, dy32, dy, dypos):
-        pl, tbl, dims = ctx.pl, ctx.tbl, ctx.dims
+        if dy32 is None and dy is None and dypos is None:
+            return _no_grads(ctx, 8)
         B, N, L, D, H, F = ctx.shape
         o32_, o_, opos_, mv_, mpos_, kb_, qpos = ctx.saved_tensors
-        n_par = ctx.n_par
-        if dy32 is None and dy is None and dypos is None:
-            pl.done(n_par > 0)
-            return (None,) * (8 + n_par)
-        dt, qdt = pl.dt, pl.qdt
-        e, qe = _ESZ[dt], _ESZ[qdt]
-        dev = o_.device
-        cont = lambda t_: None if t_ is None else (t_ if t_.is_contiguous() else t_.contiguous())
-        dy32, dy, dypos = cont(dy32), cont(dy), cont(dypos)
-        lay = _layout(('b', QC, B, N, L, D, H, F, dt, qdt), lambda: _qc_bwd_layout(B, N, L, D, H, F, e, qe))
-        tmp = torch.empty((lay.total,), dtype=torch.uint8, device=dev)
-        lay.fill(tbl, tmp.data_ptr())
-        tbl.set_t('DY32', dy32)
-        tbl.set_t('DY', dy)
-        tbl.set_t('DYPOS', dypos)
-        slay = _layout(('s', QC, B, N, L, D, H, F, dt, qdt), None)
-        scr = _scratch(dev, slay.total)
-        slay.fill(tbl, scr.data_ptr())
-        needs = ctx.needs_input_grad
-        gq = None
-        if needs[7]:
-            gq, _ = _qpos_target(pl, qpos, tbl, dev, N, D)
-        else:
-            tbl.set('DQPOS', None)
-        bufs = pl.grad_buffers(tbl, dev)
-        L_ = _lib.lib()
-        s = ops._stream()
-        _lib.check(L_.svol_query_cross_bwd(dims, tbl.arr, s), 'svol_query_cross_bwd')
-        keep = (ctx.arena, tmp, opos_, mv_, mpos_)
-        if bufs is None:
-            _issue_wgrad('svol_query_cross_wgrad', dims, tbl, list(keep), dev)
-        else:
-            _lib.check(L_.svol_query_cross_wgrad(dims, tbl.arr, s), 'svol_query_cross_wgrad')
-        pl.done(n_par > 0)
-        if gq is not None and qdt != torch.float32:
-            gq = ops.cast(gq, qdt)
+        dt, qdt = ctx.pl.dt, ctx.pl.qdt
+        gq = _qpos_target(ctx, qpos, ctx.needs_input_grad[7], N, D)
+        lay, tmp, bufs, gs = _open_bwd(ctx, o_.device, lambda: _qc_bwd_layout(B, N, L, D, H, F, _ESZ[dt], _ESZ[qdt]),
+                                       DY32=dy32, DY=dy, DYPOS=dypos)
+        _call('svol_query_cross_bwd', ctx)
+        pg = _close_bwd(ctx, 'svol_query_cross_wgrad', bufs, [ctx.arena, tmp, opos_, mv_, mpos_], 8)
         vq = lambda n_, dt_: lay.view(tmp, n_, dt_, (B, N, D))
         vm = lambda n_: lay.view(tmp, n_, dt, (B, L, D))
-        return (None, vq('DO32', torch.float32), None, vq('DXQP', qdt), vm('DMV'), vm('DMPOS'), None, gq) + \
-            tuple(pl.grads_out(bufs, needs[8:], n_par > 0))
+        return (None, vq('DO32', torch.float32), None, vq('DXQP', qdt), vm('DMV'), vm('DMPOS'), None, _qpos_grad(gq, qdt)) + pg
 
 
 def query_cross(layer, out, mv, mpos, kbias, qpos, dt, qdt):

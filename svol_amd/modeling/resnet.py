@@ -30,7 +30,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, wgrad
 from ..ingest import FrameIngest, is_raw_frames
 
 _DTYPES = {'bf16': torch.bfloat16, 'fp32': torch.float32, torch.bfloat16: torch.bfloat16, torch.float32: torch.float32}
@@ -87,18 +87,14 @@ def _weight_grad(dz, make_dwp, weight, sink, keep):
     """dW of a convolution in the parameter's own layout: make_dwp() -> dz^T im2col(x) as [Cout, Kp] fp32 (svol_conv_wgrad_nhwc: the im2col
     view gathered inside the weight-gradient GEMM; the stem: svol_gemm_tn on its kept im2col matrix), folded back by one kernel.
     With a gradient sink (the parameter's .grad is a view of a BucketedGradAllReduce bucket) the three launches go to the
-    weight-gradient stream (ops.py "weight gradients off the critical path": nobody needs dW before the optimiser; the dx chain behind
+    weight-gradient stream (svol_amd.wgrad: nobody needs dW before the optimiser; the dx chain behind
     it is the backward's critical path) and add straight into the bucket: returns None.  `keep`: tensors the side stream reads."""
-    if sink is not None and ops.WGRAD_ASYNC and not torch.cuda.is_current_stream_capturing():
-        cur = torch.cuda.current_stream(dz.device)
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        ws = ops._wgrad_stream(dz.device)
-        ws.wait_event(ev)
+    def run(ws):
         with torch.cuda.stream(ws):
             ops.conv_weight_unpack_add(make_dwp(), sink.view.view(weight.shape))
-        for t in keep:
-            t.record_stream(ws)
+
+    # (the backbone's weight gradients are never queued behind an attention backward and stay in line under any stream capture)
+    if sink is not None and wgrad.issue(run, keep, torch.cuda.current_stream(dz.device), defer=False, capture_ok=False):
         return None
     dW = torch.zeros_like(weight, dtype=torch.float32, memory_format=torch.contiguous_format)
     ops.conv_weight_unpack_add(make_dwp(), dW)

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, wgrad
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SIGMOID, ACT_RELU_RES, ACT_GELU_D = 0, 1, 2, 3, 4, 5
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}   # SVOL_F32 / SVOL_BF16 / SVOL_F16
@@ -200,117 +200,11 @@ def gemm_tn_grouped(problems, stream=None):
     _lib.check(rc, 'svol_gemm_tn_grouped')
 
 
-# ---- weight gradients off the critical path --------------------------------------------------------------------------------
-# dW = dY^T X is needed by nobody until the optimizer step (or the bucket's all-reduce), while the dX chain behind it IS the
-# critical path of backward.  When the gradient lands in a reducer-owned bucket (a "sink": persistent memory, no autograd
-# consumer), the TN GEMM is issued on a dedicated stream that waits for the producing stream's work so far and is joined by
-# BucketedGradAllReduce (before a bucket's all-reduce and in finish()).  The split-M TN kernels are HBM / atomic bound, the
-# attention-backward kernels they now run beside are instruction-issue bound: the two overlap almost for free.
-WGRAD_ASYNC = os.environ.get('SVOL_NO_WGRAD_STREAM') is None
-WGRAD_IN_CAPTURE = False   # (svol_amd.graph: a captured step keeps everything on one stream unless told otherwise)
-_WGRAD = {}
-
-
-def wgrad_streams(dev):
-    """streams weight-gradient GEMMs have been issued on for `dev` (svol_amd.parallel joins them)."""
-    s = _WGRAD.get(torch.device(dev) if not isinstance(dev, torch.device) else dev)
-    return [s] if s is not None else []
-
-
-# Deferral: the weight-gradient GEMMs are HBM / atomic bound; the video attention backward — 1.3 ms per layer — is instruction-issue
-# bound and is the part of the backward they disturb least.  So a gradient-sink TN GEMM is only QUEUED here (with an event that says
-# "its operands exist") and the queue is flushed onto the weight-gradient stream right before the next large attention backward is
-# launched, before a bucket's all-reduce, and in BucketedGradAllReduce.finish() (same-box A/B: -0.2 ms per step).  The autograd engine
-# runs every backward node of a device on one thread, so the queue needs no lock.
-WGRAD_DEFER = os.environ.get('SVOL_NO_WGRAD_DEFER') is None
-_WGRAD_PENDING = []
-_WGRAD_FLUSH_MIN_SCORES = 1 << 27   # B*H*Lq*Lk of an attention backward worth hiding weight gradients under (cfg2: 2.5e9)
-_BIG_ATTN = {'left': 0}             # large attention forwards of this step whose backward has not run yet: nothing is deferred once
-                                    # it reaches 0 (after the first layer's attention backward there is nothing left to hide under)
-
-
-def _wgrad_stream(dev):
-    ws = _WGRAD.get(dev)
-    if ws is None:
-        ws = _WGRAD[dev] = torch.cuda.Stream(device=dev)
-    return ws
-
-
-# Round 3 gated the queued weight-gradient GEMMs to start beside the (two-pass, 256-VGPR, two workgroups per CU) attention backward.
-# Round 4's single-pass backward owns a CU's whole register file (one 512-register wave per SIMD): nothing can run beside it, a gated
-# GEMM only takes CUs away from it between its workgroup rounds — same box, same build: 19.72 ms/step gated (attention backward 1.31 ms
-# in the step against 1.04 alone), 19.45 ungated (1.04 in the step).  Off by default; SVOL_WGRAD_GATE=1 restores it.
-WGRAD_GATE = os.environ.get('SVOL_WGRAD_GATE') is not None and os.environ.get('SVOL_NO_WGRAD_GATE') is None
-
-
-def flush_wgrad(gate=False):
-    """issue every queued weight-gradient launch (callables that put it on the weight-gradient stream behind the event recorded when
-    it was queued).  ``gate=True`` (the caller is about to launch a large attention backward on the current stream): the
-    weight-gradient stream additionally waits for THIS point of the current stream.  Deferring the launches on the host alone orders
-    nothing on the device once the host runs ahead of it (block programs: a step is issued in ~6 ms): the queued GEMMs then start the
-    moment their operands exist, i.e. beside the next layer's LayerNorm / dgelu kernels, which are HBM-bound like they are
-    (tools/block_trace.py timeline: LN3' 182 us against 47 alone), instead of beside the issue-bound attention backward."""
-    if not _WGRAD_PENDING:
-        return
-    items = list(_WGRAD_PENDING)
-    _WGRAD_PENDING.clear()
-    if gate and WGRAD_GATE and not torch.cuda.is_current_stream_capturing():
-        cur = _current_stream_obj()
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        _wgrad_stream(cur.device).wait_event(ev)
-    for it in items:
-        it()
-
-
-_FLUSH_ARMED = [False]
-
-
-def _final_flush():
-    _FLUSH_ARMED[0] = False
-    flush_wgrad()
-
-
-def arm_wgrad_flush():
-    """called when something is queued during a backward: make the autograd engine drain the queue before ``backward()`` returns, so
-    a caller that never reaches ``BucketedGradAllReduce.finish()`` (an exception, a skipped batch) cannot leak a failed step's
-    weight-gradient GEMMs into the next step's freshly zeroed buckets."""
-    if _FLUSH_ARMED[0]:
-        return
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(_final_flush)
-        _FLUSH_ARMED[0] = True
-    except RuntimeError:   # not inside a backward pass: finish() / the next flush point drains the queue
-        pass
-
-
-def drop_pending_wgrad():
-    """a new step starts: whatever a FAILED backward left queued must not run into this step's buffers."""
-    _WGRAD_PENDING.clear()
-    _FLUSH_ARMED[0] = False
-
-
 def gemm_tn_sink(A, B, out, colsum=None):
-    """gemm_tn into a persistent gradient bucket view, off the critical path (see above).  `out` / `colsum` must be sink
+    """gemm_tn into a persistent gradient bucket view, off the critical path (svol_amd.wgrad).  `out` / `colsum` must be sink
     views: nothing on the current stream may read them before BucketedGradAllReduce.finish()."""
-    if not WGRAD_ASYNC or (not WGRAD_IN_CAPTURE and torch.cuda.is_current_stream_capturing()):
-        return gemm_tn(A, B, out=out, colsum=colsum)
-    cur = _current_stream_obj()
-    ev = torch.cuda.Event()
-    ev.record(cur)
-
-    def later():
-        ws = _wgrad_stream(A.device)
-        ws.wait_event(ev)
-        gemm_tn(A, B, out=out, colsum=colsum, stream=ws.cuda_stream)   # (explicit handle: no current-stream switch on the host)
-        A.record_stream(ws)
-        B.record_stream(ws)
-
-    if WGRAD_DEFER and _BIG_ATTN['left'] > 0 and not torch.cuda.is_current_stream_capturing():
-        _WGRAD_PENDING.append(later)
-        arm_wgrad_flush()
-    else:
-        later()
+    if not wgrad.issue(lambda ws: gemm_tn(A, B, out=out, colsum=colsum, stream=ws.cuda_stream), (A, B), _current_stream_obj()):
+        gemm_tn(A, B, out=out, colsum=colsum)
     return out
 
 
@@ -408,13 +302,15 @@ def posenc_sine(mask_f32: torch.Tensor, D: int, dtype: torch.dtype) -> torch.Ten
     return pos
 
 
+def attn_ws_bytes(dtype, B, H, Lq, Lk, dh):
+    """bytes of scratch the attention launches need: partial results of the key-split (few queries, many keys), the key-tile classes
+    of the masked fast kernels, or the per-workgroup redo flags of the fast unmasked forward; 0 when the library needs none."""
+    return max(int(_lib.lib().svol_attn_ws_bytes(B, H, Lq, Lk, dh)), 0) if dtype != torch.float32 else 0
+
+
 def _attn_ws(q, B, H, Lq, Lk, dh):
-    """scratch of the attention launches: partial results of the key-split (few queries, many keys), the key-tile classes of
-    the masked fast kernels, or the per-workgroup redo flags of the fast unmasked forward; None when the library needs none."""
-    n = _lib.lib().svol_attn_ws_bytes(B, H, Lq, Lk, dh) if q.dtype != torch.float32 else 0
-    if n <= 0:
-        return None
-    return torch.empty((n // 4,), dtype=torch.float32, device=q.device)
+    n = attn_ws_bytes(q.dtype, B, H, Lq, Lk, dh)
+    return torch.empty((n // 4,), dtype=torch.float32, device=q.device) if n else None
 
 
 def dropout(x, p, seed, out=None):
@@ -441,8 +337,7 @@ def attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias=None, premul=0.0, drop=None):
     lse2 = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
     ws = _attn_ws(q, B, H, Lq, Lk, dh)
     p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
-    if B * H * Lq * Lk >= _WGRAD_FLUSH_MIN_SCORES:
-        _BIG_ATTN['left'] += 1
+    wgrad.attn_forward(B * H * Lq * Lk)
     tok = timer.start('attn_fwd', (B, H, Lq, Lk, dh))
     rc = _lib.lib().svol_attn_fwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
                                           _ptr(lse2), _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws),
@@ -455,9 +350,7 @@ def attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias=None, premul=0.0, drop=None):
 def attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, premul=0.0, drop=None):
     """Writes dq/dk/dv (2-D views, column slices allowed)."""
     do = do if do.stride(1) == 1 else do.contiguous()
-    if B * H * Lq * Lk >= _WGRAD_FLUSH_MIN_SCORES:
-        _BIG_ATTN['left'] -= 1
-        flush_wgrad(gate=True)   # the queued weight-gradient GEMMs run beside this launch
+    wgrad.attn_backward(B * H * Lq * Lk)   # the queued weight-gradient GEMMs run beside this launch
     delta = torch.empty((3, B, H, Lq), dtype=torch.float32, device=q.device)  # delta | -lse2 pairs | -delta pairs (svol_hip.h)
     ws = _attn_ws(q, B, H, Lq, Lk, dh)
     p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
@@ -733,9 +626,7 @@ class _WeightCache:
         __slots__ = ('wc', 'wt', 'ws', 'ptr', 'epoch', 'version', 'shape')
 
     def new_epoch(self):
-        _BIG_ATTN['left'] = 0   # a new forward starts (see gemm_tn_sink)
-        if not torch.is_grad_enabled() or not _FLUSH_ARMED[0]:
-            drop_pending_wgrad()   # (an armed flush belongs to a backward that is still running: leave it alone)
+        wgrad.forward_starts()
         if self.static:
             return
         self.epoch += 1

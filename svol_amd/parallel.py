@@ -28,7 +28,7 @@ from typing import Iterable, List, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops   # (neither loads the kernel library at import)
+from . import _lib, ops, wgrad   # (none loads the kernel library at import)
 from .ops import _ptr, _stream
 
 _LATE = ('query_embed', 'input_', 'backbone', 'pos_embed', 'position_embedding')   # first used in forward = last in backward
@@ -175,7 +175,7 @@ class BucketedGradAllReduce:
         created under ``torch.cuda.stream(side)``), and the stream of the node whose hook is running."""
         from .modeling import cross_modal_transformer as cmt
         ss = ([self.main_stream, torch.cuda.current_stream(self.device)] + list(cmt.side_streams(self.device)) +
-              list(ops.wgrad_streams(self.device)))   # weight-gradient GEMMs run on a stream of their own (ops.gemm_tn_sink)
+              list(wgrad.streams(self.device)))   # weight-gradient GEMMs run on a stream of their own
         out = []
         for s in ss:
             if s is not None and all(s != t for t in out):
@@ -196,7 +196,7 @@ class BucketedGradAllReduce:
             # By the time the last hook of a bucket fires every producing kernel of the bucket has been ENQUEUED on
             # its stream (autograd issues nodes in order on the host), so waiting on all producer streams here is
             # sufficient.
-            ops.flush_wgrad()   # weight-gradient GEMMs still queued on the host (ops.gemm_tn_sink) may belong to this bucket
+            wgrad.flush()   # weight-gradient GEMMs still queued on the host may belong to this bucket
             for s in self._producer_streams():
                 self.comm_stream.wait_stream(s)
             with torch.cuda.stream(self.comm_stream):
@@ -221,7 +221,7 @@ class BucketedGradAllReduce:
 
     def _early_step_local(self, b):
         """world size 1, FlatAdamW(step_in_backward=True): the bucket's update as soon as its gradients are final, on the communication
-        stream behind every producer stream's work so far.  Weight-gradient launches still QUEUED on the host (ops: deferred to
+        stream behind every producer stream's work so far.  Weight-gradient launches still QUEUED on the host (wgrad: deferred to
         the next large attention backward) belong in front of it: the update joins that queue behind them, so the deferral keeps its
         schedule and the update lands beside the attention backward — an issue-bound launch that leaves the memory side idle."""
         def issue():
@@ -230,11 +230,7 @@ class BucketedGradAllReduce:
             self._early_any = True
             self.on_bucket_reduced(b['index'], self.comm_stream.cuda_stream)
 
-        if ops._WGRAD_PENDING:
-            ops._WGRAD_PENDING.append(issue)
-            ops.arm_wgrad_flush()
-        else:
-            issue()
+        wgrad.run_behind_pending(issue)
 
     def modelled_exchange_ms(self, nbytes: int, ranks: int = 8, link_gbs: float = 153.0) -> float:
         """duration of one bucket's all-reduce over xGMI in the SVOL_ALLREDUCE_SPIN model (see __init__)."""
@@ -260,7 +256,7 @@ class BucketedGradAllReduce:
         """Zero the flat buckets (replaces optimizer.zero_grad(); keeps the grad views alive)."""
         if self.on_gpu:
             self.main_stream = torch.cuda.current_stream(self.device)
-            ops.drop_pending_wgrad()   # weight-gradient launches a failed backward left queued must not land in the zeroed buckets
+            wgrad.drop_pending()   # weight-gradient launches a failed backward left queued must not land in the zeroed buckets
         self.fire_order = []
         self.spans = []
         self._early_any = False
@@ -289,8 +285,8 @@ class BucketedGradAllReduce:
             # kernels that accumulate straight into the buckets (gradient sinks) may have run on the model's side
             # stream (query-stream / video-stream overlap): join it before anyone reads the buckets
             from .modeling import cross_modal_transformer as cmt
-            ops.flush_wgrad()
-            for s in list(cmt.side_streams(self.device)) + list(ops.wgrad_streams(self.device)):
+            wgrad.flush()
+            for s in list(cmt.side_streams(self.device)) + list(wgrad.streams(self.device)):
                 torch.cuda.current_stream().wait_stream(s)
         collective = self.world > 1 or self.force
         for b in self.buckets:

@@ -66,7 +66,7 @@ def test_training_step_does_not_depend_on_stream_timing(dtype):
     front of the backward, so that the others run far ahead of it: losses identical, every gradient equal to the undisturbed step's
     up to the order of its fp32 atomics.  A missing cross-stream dependency or a tensor recycled under a queued kernel shows up as a
     gross difference."""
-    from svol_amd import ops, parallel
+    from svol_amd import parallel, wgrad
     from svol_amd.modeling import cross_modal_transformer as cmt
     from svol_amd.modeling.loss import build_loss
     from svol_amd.modeling.svanet import build_svanet
@@ -87,7 +87,7 @@ def test_training_step_does_not_depend_on_stream_timing(dtype):
         if which is None:
             return
         streams = {'main': torch.cuda.current_stream(), 'side': cmt._side_stream(dev)}
-        ws = ops.wgrad_streams(dev)
+        ws = wgrad.streams(dev)
         if ws:
             streams['wgrad'] = ws[0]
         if which in streams:
