@@ -3,7 +3,7 @@
 One ``torch.autograd.Function`` and ONE C call per block and direction of a ``CrossModalTransformerLayer`` (reference
 cross_modal_transformer.py:105-160) instead of one Function per op and one ctypes call + ``torch.empty`` per kernel:
 the per-op host path needed 19.6 ms to issue a 20.8 ms step.  The arithmetic is the same kernels in the same
-order as ``ops.GateFn`` / ``ops.AttnLNFn`` / ``ops.MLPLNFn`` (which stay for the enc/dec heads and as the A/B reference,
+order as ``layers.GateFn`` / ``layers.AttnLNFn`` / ``layers.MLPLNFn`` (which stay for the enc/dec heads and as the A/B reference,
 ``SVOL_NO_BLOCKS=1``); what this module owns is
 
 * the slot tables (one ``void*`` array per block call: parameters and weight copies are filled once per plan, activations per call),
@@ -22,7 +22,7 @@ import weakref
 
 import torch
 
-from . import _lib, ops, wgrad
+from . import _lib, layers, ops, params, wgrad
 
 ENABLED = os.environ.get('SVOL_NO_BLOCKS') is None
 # SVOL_GATE_SCORES_FUSE=1: layer i's LN3 also writes layer i + 1's gate scores (svol_layernorm_gate_scores_fwd) and that layer skips its
@@ -146,7 +146,7 @@ _PARAMS = {VH: _VH_PARAMS, QS: _QS_PARAMS, QC: _QC_PARAMS}
 
 
 class BlockPlan:
-    """static rows of one block's slot table for one layer: parameter pointers, compute-dtype weight copies (ops.weights keeps them
+    """static rows of one block's slot table for one layer: parameter pointers, compute-dtype weight copies (params.weights keeps them
     alive and refreshes them once per forward), gradient sinks.  ``key`` changes when any of those pointers does."""
 
     def __init__(self, block, layer, dt, qdt):
@@ -157,23 +157,23 @@ class BlockPlan:
         self.tpl = _Table(block)
         self.keep = []   # tensors whose pointers sit in the template
         D = layer.d_model
-        self.split_v = ops.SPLIT_V and D % 32 == 0
+        self.split_v = params.SPLIT_V and D % 32 == 0
         t = self.tpl
-        W = ops.weights
+        W = params.weights
         dev = self.params[0].device
 
-        self.casts = []    # (weight, dtype, wc, wt) / (weight, row0, rows, ws): the copies whose POINTERS sit in the template
+        self.casts = []    # (cache method, its arguments, what it returned): the copies whose POINTERS sit in the template
         self.epoch = W.epoch
 
         def both(name, w, dtype):
-            wc, wt = W.get(w, dtype)
+            got = wc, wt = W.get(w, dtype)
             t.set_t(name, wc)
             t.set_t(name + '_T', wt)
             self.keep += [wc, wt]
-            self.casts.append((w, dtype, wc, wt))
+            self.casts.append((W.get, (w, dtype), got))
 
         wdt = dt if block == VH else qdt   # the block's GEMMs run in the dtype of the stream they belong to,
-        adt = qdt if block == QS else dt   # its attention core in that of its keys (ops.AttnLNFn: premul follows dkv)
+        adt = qdt if block == QS else dt   # its attention core in that of its keys (layers.AttnLNFn: premul follows dkv)
         for slot, p in zip(self.grad_slots, self.params):   # the forward slot is the gradient slot without its 'D'
             if p.dim() == 1:
                 t.set_t(slot[1:], p)
@@ -187,13 +187,13 @@ class BlockPlan:
             hl = W.get_split(w_in, 2 * D, D)
             t.set_t('WV_HILO', hl)
             self.keep.append(hl)
-            self.casts.append((w_in, 2 * D, D, hl))
+            self.casts.append((W.get_split, (w_in, 2 * D, D), hl))
         if adt != torch.float32:
-            q = ops._qscale(D, ops.LOG2E / math.sqrt(D // layer.nhead), dev)
+            q = layers._qscale(D, layers.LOG2E / math.sqrt(D // layer.nhead), dev)
             t.set_t('QSCALE', q)
             self.keep.append(q)
         # gradient targets: the reducer's bucket views where there are sinks
-        self.sinks = [ops._claim(p, p.requires_grad) for p in self.params]
+        self.sinks = [params.claim(p, p.requires_grad) for p in self.params]
         self.nosink = [(i, p.numel()) for i, (p, s) in enumerate(zip(self.params, self.sinks)) if s is None]
         for name, s in zip(self.grad_slots, self.sinks):
             if s is not None:
@@ -215,26 +215,20 @@ class BlockPlan:
             g = p.grad
             s = getattr(p, '_svol_sink', None)
             k.append((p.data_ptr(), g.data_ptr() if (g is not None and s is not None) else 0, p.requires_grad))
-        return (ops.SPLIT_V, tuple(k))
+        return (params.SPLIT_V, tuple(k))
 
     def valid(self):
         return self.layer() is not None and self._key() == self.key
 
     def fresh_copies(self):
         """The compute-dtype / transposed / split weight copies behind the template's pointers are those of the CURRENT parameter
-        values: the per-op path re-validated every copy on every call (version counter + cache epoch, ops._WeightCache.get),
+        values: the per-op path re-validated every copy on every call (version counter + cache epoch, params._WeightCache.get),
         a plan caches raw pointers.  Same check here, once per use: a hit costs a dictionary lookup; a copy that an in-place update
         made stale (a torch optimizer step, load_state_dict, copy_ — anything that bumps ``_version`` — or a new cache epoch) is
         re-cast INTO ITS BUFFER, so the template stays valid; a copy that moved invalidates the plan."""
-        W = ops.weights
-        for c in self.casts:
-            if len(c) == 4 and isinstance(c[1], torch.dtype):
-                wc, wt = W.get(c[0], c[1])
-                if wc is not c[2] or wt is not c[3]:
-                    return False
-            else:
-                if W.get_split(c[0], c[1], c[2]) is not c[3]:
-                    return False
+        for again, args, got in self.casts:   # (the cache hands out the same object for as long as the buffers are the same)
+            if again(*args) is not got:
+                return False
         return True
 
     def grad_buffers(self, tbl, dev):
@@ -548,7 +542,7 @@ def _qpos_target(ctx, qpos, need, N, D):
     parameter (fp32 query stream) and it has a sink, else a zeroed buffer returned to autograd (-> that buffer, or None)."""
     g = s = None
     if need and qpos.requires_grad:
-        s = ops._claim(qpos, True) if (qpos.is_leaf and qpos.dtype == torch.float32) else None
+        s = params.claim(qpos, True) if (qpos.is_leaf and qpos.dtype == torch.float32) else None
         if s is None:
             g = torch.zeros((N, D), dtype=torch.float32, device=qpos.device)
     ctx.tbl.set_t('DQPOS', s.view if s is not None else g)

@@ -30,7 +30,7 @@ and the same forward bits as the frozen path, one autograd Function per piece:
                   backward svol_attn_small_bwd into one packed dQKV, dx = dQKV [W_q; W_k; W_v] in one NT GEMM)
                   -> LNStreamFn(layernorm_after) -> MLPLNFn(gamma=None, GELU)
     final norm    LNStreamFn
-The trainable path casts its own bf16 weights at the start of every training forward: ops.weights is refreshed by the head's
+The trainable path casts its own bf16 weights at the start of every training forward: params.weights is refreshed by the head's
 forward, which runs AFTER the backbone, and fused AdamW on ROCm does not bump ``_version``.
 """
 from __future__ import annotations
@@ -40,7 +40,7 @@ from types import SimpleNamespace
 import torch
 from torch import nn
 
-from .. import _lib, ops
+from .. import _lib, layers, ops, params
 from ..ingest import FrameIngest, is_raw_frames
 from ..ops import _DT, _ptr, _stream
 
@@ -106,26 +106,6 @@ def _embed(proj, cls, pos, n, P, d):
     return x32
 
 
-def _wgrad(sinks, shapes, A, B, has_colsum=True):
-    """gemm_tn of the weight (and with has_colsum the bias) gradient of A^T B: into the gradient sinks when the reducer owns
-    both, else into one fresh zeroed buffer.  -> (dW or None, db or None) as the Function returns them."""
-    sW, sb = sinks
-    if sW is not None and (sb is not None or not has_colsum):
-        ops.gemm_tn_sink(A, B, out=sW.view.view(A.shape[1], B.shape[1]), colsum=sb.view if sb is not None else None)
-        return None, None
-    N, K = A.shape[1], B.shape[1]
-    buf = torch.zeros((N * K + N,), dtype=torch.float32, device=A.device)
-    dW, db = buf[:N * K].view(N, K), buf[N * K:]
-    ops.gemm_tn(A, B, out=dW, colsum=db if has_colsum else None)
-    if sW is not None:
-        sW.view.add_(dW.view(sW.view.shape))
-        dW = None
-    if sb is not None:
-        sb.view.add_(db)
-        db = None
-    return (dW.view(shapes[0]) if dW is not None else None), (db if has_colsum else None)
-
-
 class _ViTEmbedFn(torch.autograd.Function):
     """patchify -> patch GEMM (+ bias, fp32 out) -> [CLS] + position embeddings: the fp32 stream [n*(P+1), d].  No pixel gradient."""
 
@@ -140,7 +120,7 @@ class _ViTEmbedFn(torch.autograd.Function):
         ctx.save_for_backward(patches)
         ctx.dims, ctx.wshape = (n, P, d), W.shape
         nig = ctx.needs_input_grad
-        ctx.sinks = tuple(ops._claim(t, nig[i]) for i, t in ((1, W), (2, b), (3, cls), (4, pos)))
+        ctx.sinks = tuple(params.claim(t, nig[i]) for i, t in ((1, W), (2, b), (3, cls), (4, pos)))
         return x32
 
     @staticmethod
@@ -153,7 +133,10 @@ class _ViTEmbedFn(torch.autograd.Function):
         dW = db = dcls = dpos = None
         if nig[1] or nig[2]:
             dproj = ops.cast(dx32.view(n, P + 1, d)[:, 1:].reshape(n * P, d), torch.bfloat16)
-            dW, db = _wgrad((sW, sb), (ctx.wshape,), dproj, patches)
+            grads = params.GradGroup(((sW, (d, patches.shape[1])), (sb, (d,))), dproj.device)
+            grads.tn(dproj, patches, 0, 1)
+            dW, db = grads.finish()
+            dW = dW.view(ctx.wshape) if dW is not None else None
         if nig[3] or nig[4]:
             # position embeddings: the stream gradient summed over the images; the [CLS] token: the same sum's first row
             g = ops.colsum(dx32.view(n, (P + 1) * d))
@@ -187,7 +170,7 @@ class _ViTAttnFn(torch.autograd.Function):
         ctx.save_for_backward(y, qkv, o, lse2)
         ctx.dims, ctx.WqkvT, ctx.WoT = dims, WqkvT, WoT
         nig = ctx.needs_input_grad
-        ctx.sinks = tuple(ops._claim(t, nig[i]) for i, t in enumerate((Wq, bq, Wk, bk, Wv, bv, Wo, bo), start=2))
+        ctx.sinks = tuple(params.claim(t, nig[i]) for i, t in enumerate((Wq, bq, Wk, bk, Wv, bv, Wo, bo), start=2))
         return out
 
     @staticmethod
@@ -198,25 +181,23 @@ class _ViTAttnFn(torch.autograd.Function):
         dout32 = dout32 if dout32.is_contiguous() else dout32.contiguous()
         ds = ops.cast(dout32, torch.bfloat16)
         sk = ctx.sinks
-        dWo, dbo = _wgrad((sk[6], sk[7]), ((d, d),), ds, o)
+        grads = params.GradGroup(((sk[6], (d, d)), (sk[7], (d,))), ds.device)
+        grads.tn(ds, o, 0, 1)
+        dWo, dbo = grads.finish()
         do = ops.gemm_nt(ds, ctx.WoT)
         dqkv = torch.empty((n * L, 3 * d), dtype=torch.bfloat16, device=y.device)
         ops.attn_small_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse2, n, H, L, d // H,
                            dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:])
-        g = []
-        if all(s is not None for s in sk[:6]):
+        grads = params.GradGroup([(sk[2 * j], (d, d)) for j in range(3)] + [(sk[2 * j + 1], (d,)) for j in range(3)], y.device)
+        if grads.direct:
             for j in range(3):
-                g += list(_wgrad((sk[2 * j], sk[2 * j + 1]), ((d, d),), dqkv[:, j * d:(j + 1) * d], y))
-        else:   # one launch for the three projections, split into views
-            dW, db = _wgrad((None, None), ((3 * d, d),), dqkv, y)
-            for j in range(3):
-                gw, gb = dW[j * d:(j + 1) * d], db[j * d:(j + 1) * d]
-                for s_, t_ in ((sk[2 * j], gw), (sk[2 * j + 1], gb)):
-                    if s_ is not None:
-                        s_.view.add_(t_)
-                g += [None if sk[2 * j] is not None else gw, None if sk[2 * j + 1] is not None else gb]
+                grads.tn(dqkv[:, j * d:(j + 1) * d], y, j, 3 + j)
+        else:   # one launch for the three projections: dW_q | dW_k | dW_v and db_q | db_k | db_v are contiguous in the buffer
+            ops.gemm_tn(dqkv, y, out=grads.buf[:3 * d * d].view(3 * d, d), colsum=grads.buf[3 * d * d:])
+        g = grads.finish()
+        g = tuple(t for j in range(3) for t in (g[j], g[3 + j]))
         dy = ops.gemm_nt(dqkv, ctx.WqkvT) if ctx.needs_input_grad[1] else None
-        return (dout32, dy) + tuple(g) + (dWo, dbo, None, None)
+        return (dout32, dy) + g + (dWo, dbo, None, None)
 
 
 class ViTExtractor(nn.Module):
@@ -313,16 +294,16 @@ class ViTExtractor(nn.Module):
             a = lyr.attention
             wqkv, wqkvT = ops.cast_transpose(torch.cat([a.q_proj.weight.detach(), a.k_proj.weight.detach(), a.v_proj.weight.detach()]), dt)
             woc, woT = ops.cast_transpose(a.o_proj.weight.detach(), dt)
-            y = ops.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, dt, False)
+            y = layers.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, dt, False)
             x32 = _ViTAttnFn.apply(x32, y, a.q_proj.weight, a.q_proj.bias, a.k_proj.weight, a.k_proj.bias, a.v_proj.weight,
                                    a.v_proj.bias, a.o_proj.weight, a.o_proj.bias, (wqkv, wqkvT, woc, woT), (n, L, H))
-            y = ops.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
+            y = layers.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
             m = lyr.mlp
             w1c, w1T = ops.cast_transpose(m.fc1.weight.detach(), dt)
             w2c, w2T = ops.cast_transpose(m.fc2.weight.detach(), dt)
-            x32 = ops.MLPLNFn.apply(x32, y, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, None, None, ops.ACT_GELU, None,
+            x32 = layers.MLPLNFn.apply(x32, y, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, None, None, ops.ACT_GELU, None,
                                     (w1c, w1T, w2c, w2T))
-        last, _ = ops.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, dt, True)
+        last, _ = layers.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, dt, True)
         if return_pre_norm:
             return last.view(n, L, d), x32.view(n, L, d)
         return last.view(n, L, d)

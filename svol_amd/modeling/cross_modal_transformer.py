@@ -29,14 +29,15 @@ import os
 import torch
 from torch import nn
 
-from .. import blocks, ops
+from .. import _lib, blocks, layers, ops
+from ..params import GradGroup, claim, weights
 
 D_FF = 2048  # the reference hard-codes dim_feedforward=2048 here and ignores --dim_feedforward
 
 
 class MLP(nn.Module):
     """fc1 / fc2 parameter container (reference MLP, :163-179); the arithmetic is fused with the
-    residual add and the following post-norm in ``ops.mlp_ln``."""
+    residual add and the following post-norm in ``layers.mlp_ln``."""
 
     def __init__(self, in_features, hidden_features):
         super().__init__()
@@ -47,7 +48,7 @@ class MLP(nn.Module):
 OVERLAP_QUERY_STREAM = os.environ.get('SVOL_NO_STREAM_OVERLAP') is None
 # bf16 mode: the N object queries (a few hundred rows: < 1 % of the step's FLOPs) run their projections, MLP2, query
 # self-attention, residuals and norms in exact fp32 GEMMs; only the K / V projections of the L video tokens and the
-# query -> video attention core stay on the bf16 MFMA path (ops.AttnLNFn "mixed").  The final logits / boxes are linear
+# query -> video attention core stay on the bf16 MFMA path (layers.AttnLNFn "mixed").  The final logits / boxes are linear
 # heads of the query stream, so its bf16 operand roundings were the larger half of the output error: measured on the
 # reference goldens 1.0e-2 -> ~5e-3 max |logit error| (profiles/round2_bf16_output_error.md).  SVOL_QUERY_BF16=1 restores
 # the all-bf16 query stream (A/B).
@@ -81,7 +82,6 @@ class _GateVectorsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, skch, W_in, b_in, h):
-        from .. import _lib
         B, d = skch.shape
         skch = skch.contiguous().float()
         q = torch.empty((B, d), dtype=torch.float32, device=skch.device)
@@ -91,26 +91,24 @@ class _GateVectorsFn(torch.autograd.Function):
         _lib.check(rc, 'svol_gate_vectors_fwd')
         ctx.save_for_backward(skch, W_in, q)
         ctx.h = h
-        ctx.sinks = (ops._claim(W_in, ctx.needs_input_grad[1]), ops._claim(b_in, ctx.needs_input_grad[2]))
+        ctx.sinks = (claim(W_in, ctx.needs_input_grad[1]), claim(b_in, ctx.needs_input_grad[2]))
         return u
 
     @staticmethod
     def backward(ctx, du):
-        from .. import _lib
         skch, W_in, q = ctx.saved_tensors
         h = ctx.h
         B, d = skch.shape
         sW, sb = ctx.sinks
         du = du.contiguous().float()
         dev = du.device
-        dW = sW.view if sW is not None else torch.zeros((3 * d, d), dtype=torch.float32, device=dev)
-        db = sb.view if sb is not None else torch.zeros((3 * d,), dtype=torch.float32, device=dev)
+        gW, gb = GradGroup(((sW, (3 * d, d)),), dev), GradGroup(((sb, (3 * d,)),), dev)   # (one parameter each: its sink or its own zeros)
         dskch = torch.empty((B, d), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         ws = torch.empty((B, d), dtype=torch.float32, device=dev)
         rc = _lib.lib().svol_gate_vectors_bwd(ops._ptr(du), ops._ptr(skch), ops._ptr(W_in.detach()), ops._ptr(q), ops._ptr(ws),
-                                              ops._ptr(dskch), ops._ptr(dW), ops._ptr(db), B, d, h, ops._stream())
+                                              ops._ptr(dskch), ops._ptr(gW.out[0]), ops._ptr(gb.out[0]), B, d, h, ops._stream())
         _lib.check(rc, 'svol_gate_vectors_bwd')
-        return dskch, (None if sW is not None else dW), (None if sb is not None else db), None
+        return (dskch,) + gW.finish() + gb.finish() + (None,)
 
 
 def _ptr_array(tensors):
@@ -126,7 +124,6 @@ class _GateVectorsAllFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, skch, h, *params):
-        from .. import _lib
         B, d = skch.shape
         n = len(params) // 2
         skch = skch.contiguous().float()
@@ -139,30 +136,29 @@ class _GateVectorsAllFn(torch.autograd.Function):
         _lib.check(rc, 'svol_gate_vectors_fwd_multi')
         ctx.save_for_backward(skch, q, *Ws)
         ctx.h, ctx.n = h, n
-        ctx.sinks = [(ops._claim(Ws[l], ctx.needs_input_grad[2 + 2 * l]), ops._claim(bs[l], ctx.needs_input_grad[3 + 2 * l])) for l in range(n)]
+        ctx.sinks = [(claim(Ws[l], ctx.needs_input_grad[2 + 2 * l]), claim(bs[l], ctx.needs_input_grad[3 + 2 * l])) for l in range(n)]
         return tuple(us)
 
     @staticmethod
     def backward(ctx, *dus):
-        from .. import _lib
         skch, q = ctx.saved_tensors[:2]
         Ws = ctx.saved_tensors[2:]
         h, n = ctx.h, ctx.n
         B, d = skch.shape
         dev = skch.device
         dus = [torch.zeros((B, h, d), dtype=torch.float32, device=dev) if g is None else g.contiguous().float() for g in dus]
-        dWs = [sW.view if sW is not None else torch.zeros((3 * d, d), dtype=torch.float32, device=dev) for sW, _ in ctx.sinks]
-        dbs = [sb.view if sb is not None else torch.zeros((3 * d,), dtype=torch.float32, device=dev) for _, sb in ctx.sinks]
+        gWs = [GradGroup(((sW, (3 * d, d)),), dev) for sW, _ in ctx.sinks]   # (one parameter each: its sink or its own zeros)
+        gbs = [GradGroup(((sb, (3 * d,)),), dev) for _, sb in ctx.sinks]
         ws = torch.empty((n, B, d), dtype=torch.float32, device=dev)
         dsk = torch.empty((n, B, d), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         rc = _lib.lib().svol_gate_vectors_bwd_multi(_ptr_array(dus), ops._ptr(skch), _ptr_array([w.detach() for w in Ws]),
                                                     _ptr_array(list(q.unbind(0))), _ptr_array(list(ws.unbind(0))),
-                                                    None if dsk is None else _ptr_array(list(dsk.unbind(0))), _ptr_array(dWs),
-                                                    _ptr_array(dbs), n, B, d, h, ops._stream())
+                                                    None if dsk is None else _ptr_array(list(dsk.unbind(0))), _ptr_array([g.out[0] for g in gWs]),
+                                                    _ptr_array([g.out[0] for g in gbs]), n, B, d, h, ops._stream())
         _lib.check(rc, 'svol_gate_vectors_bwd_multi')
         grads = [None if dsk is None else dsk.sum(0), None]
-        for l, (sW, sb) in enumerate(ctx.sinks):
-            grads += [None if sW is not None else dWs[l], None if sb is not None else dbs[l]]
+        for gW, gb in zip(gWs, gbs):
+            grads += gW.finish() + gb.finish()
         return tuple(grads)
 
 
@@ -224,9 +220,9 @@ class CrossModalTransformerLayer(nn.Module):
         n = lambda m: (m.weight, m.bias)
         mha = lambda m: (m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias)
         mlp = lambda m: (m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias)
-        m32, m, mpos = ops.gate(mem32, pos, self.gate_vectors(skch32) if u is None else u, *n(self.norm1), h)
-        m32, m = ops.self_attn_ln(m32, m, mpos, *mha(self.content_self_attn), *n(self.norm2), None, h)
-        return ops.mlp_ln(m32, m, *mlp(self.mlp1), *n(self.norm3), pos)
+        m32, m, mpos = layers.gate(mem32, pos, self.gate_vectors(skch32) if u is None else u, *n(self.norm1), h)
+        m32, m = layers.self_attn_ln(m32, m, mpos, *mha(self.content_self_attn), *n(self.norm2), None, h)
+        return layers.mlp_ln(m32, m, *mlp(self.mlp1), *n(self.norm3), pos)
 
     def query_half(self, out, m, mpos, qpos, kbias):
         """the "decoder-like" half, :145-158: object queries attend to themselves, then to the video tokens."""
@@ -240,7 +236,7 @@ class CrossModalTransformerLayer(nn.Module):
         n = lambda m_: (m_.weight, m_.bias)
         mha = lambda m_: (m_.in_proj_weight, m_.in_proj_bias, m_.out_proj.weight, m_.out_proj.bias)
         o32, o, opos = out
-        return ops.self_attn_ln(o32, o, opos, *mha(self.token_self_attn), *n(self.norm4), qpos, self.nhead)
+        return layers.self_attn_ln(o32, o, opos, *mha(self.token_self_attn), *n(self.norm4), qpos, self.nhead)
 
     def query_cross(self, out, m, mpos, qpos, kbias):
         """:149-158: query -> video cross-attention + norm5, MLP2 + norm6."""
@@ -250,9 +246,9 @@ class CrossModalTransformerLayer(nn.Module):
         if blocks.ENABLED:
             return blocks.query_cross(self, out, m, mpos, kbias, qpos, m.dtype, qpos.dtype)
         o32, o, opos = out
-        o32, o = ops.cross_attn_ln(o32, o, opos, mpos, m, *mha(self.content_token_cross_attn), *n(self.norm5), None, self.nhead,
+        o32, o = layers.cross_attn_ln(o32, o, opos, mpos, m, *mha(self.content_token_cross_attn), *n(self.norm5), None, self.nhead,
                                    kbias)
-        return ops.mlp_ln(o32, o, *mlp(self.mlp2), *n(self.norm6), qpos)
+        return layers.mlp_ln(o32, o, *mlp(self.mlp2), *n(self.norm6), qpos)
 
 
 class CrossModalTransformer(nn.Module):
@@ -275,12 +271,12 @@ class CrossModalTransformer(nn.Module):
         # svanet_variants) open one per forward.  Driven on its own (a training loop around the bare transformer), nobody does:
         # open it here, or an optimizer that rewrites parameters without bumping their version counters (torch's fused AdamW on ROCm)
         # would leave every copy stale
-        if ops.weights.epoch == self._epoch_seen:
-            ops.weights.new_epoch()
-        self._epoch_seen = ops.weights.epoch
+        if weights.epoch == self._epoch_seen:
+            weights.new_epoch()
+        self._epoch_seen = weights.epoch
         B = src_vid32.shape[0]
         dt = torch.float32 if QUERY_FP32 else vid_pos.dtype   # element type of the QUERY stream's GEMM operands
-        qpos = ops.cast_ag(query_embed, dt)
+        qpos = layers.cast_ag(query_embed, dt)
         N, d = qpos.shape
         def initial_queries():  # reference :56: tgt = zeros; (fp32 stream, compute copy, copy + query_pos)
             return (torch.zeros((B, N, d), dtype=torch.float32, device=vid_pos.device),

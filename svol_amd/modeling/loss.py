@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
+from .. import layers
 from .matcher import build_matcher
 
 
@@ -70,7 +70,7 @@ class SetCriterion(nn.Module):
                 packed, self._prepacked = pre[2], None
             else:
                 packed = m.pack(targets, NL, B, N, logits_all.device)
-        losses, match = ops.SetCriterionFn.apply(logits_all, boxes_all, packed, m.cost_bbox, m.cost_giou,
+        losses, match = layers.SetCriterionFn.apply(logits_all, boxes_all, packed, m.cost_bbox, m.cost_giou,
                                                  m.cost_class, self.eos_coef)
         # logging copy WITHOUT the autograd graph: keeping the graph-carrying table until the next call would pin the
         # step's saved activations and AccumulateGrad nodes (and their creation streams) across iterations.  The one
@@ -116,8 +116,8 @@ class SetCriterion(nn.Module):
                 for i in range(NL - 1):
                     t[i, col] = float(self.weight_dict.get(f'{name}_{i}', 0.0))
             w = self._wtab = t.to(losses.device)
-        if ops.FUSED_HEADS:   # one tiny launch each way instead of a multiply + a reduction (and their three backward kernels)
-            return ops.WeightedTotalFn.apply(losses, w)
+        if layers.FUSED_HEADS:   # one tiny launch each way instead of a multiply + a reduction (and their three backward kernels)
+            return layers.WeightedTotalFn.apply(losses, w)
         return (losses * w).sum()
 
     def last_indices(self):

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import _lib, ops
+from .. import _lib, layers
 
 
 class PackedTargets:
@@ -192,7 +192,7 @@ class _DeviceMatcher(nn.Module):
             raise RuntimeError('svol_amd matchers run on the MI355X only (no CPU fallback)')
         B, N = bx.shape[:2]
         packed = self.pack(targets, 1, B, N, lg.device)
-        match = ops.match_all(lg.float().contiguous().view(1, B, N, 2), bx.float().contiguous().view(1, B, N, 4),
+        match = layers.match_all(lg.float().contiguous().view(1, B, N, 2), bx.float().contiguous().view(1, B, N, 4),
                               packed, self.cost_bbox, self.cost_giou, self.cost_class)
         packed.check_status()
         return packed.indices_from_match(match, 0)

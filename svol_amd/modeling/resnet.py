@@ -30,7 +30,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops, wgrad
+from .. import ops, params, wgrad
 from ..ingest import FrameIngest, is_raw_frames
 
 _DTYPES = {'bf16': torch.bfloat16, 'fp32': torch.float32, torch.bfloat16: torch.bfloat16, torch.float32: torch.float32}
@@ -114,7 +114,7 @@ class _ConvBnFn(torch.autograd.Function):
         z, Ho, Wo = ops.conv_nhwc(x, w16, None, ops.ACT_NONE, n, H, W, C, kh, kw, stride, pad)
         y, mean, rstd = _bn_forward(z, bn, gamma, beta, identity, relu, sync)
         ctx.geom, ctx.relu, ctx.has_id, ctx.out_hw, ctx.sync = geom, relu, identity is not None, (Ho, Wo), sync
-        ctx.sink = ops._claim(weight, ctx.needs_input_grad[1])
+        ctx.sink = params.claim(weight, ctx.needs_input_grad[1])
         ctx.save_for_backward(x, weight, w16, z, y if relu else None, mean, rstd, gamma.detach())
         return y
 
@@ -166,7 +166,7 @@ class _StemFn(torch.autograd.Function):
         z = ops.gemm_nt(cols, w16)
         y, mean, rstd = _bn_forward(z, bn, gamma, beta, None, True, sync)
         ctx.sync = sync
-        ctx.sink = ops._claim(weight, ctx.needs_input_grad[1])
+        ctx.sink = params.claim(weight, ctx.needs_input_grad[1])
         # the stem's im2col matrix is KEPT for the weight gradient (1 GB at 256 frames of 224 x 224 — 0.4 % of this part's HBM; building
         # it again from the NCHW fp32 pixels costs 0.6 ms) — unless the stem's weight takes no gradient
         ctx.save_for_backward(cols if ctx.needs_input_grad[1] else None, weight, z, y, mean, rstd, gamma.detach())

@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
+from .. import layers
 from .position_encoding import build_position_encoding
 from .svanet import MLP, _DTYPES
 from .svanet_variants import _DetrHead, _proj_stack
@@ -50,7 +50,7 @@ class SketchDETR(_DetrHead):
         dt = self.compute_dtype
         d = self.transformer.d_model
         bs, T, _ = src_video.shape
-        src = self._proj(self.input_video_proj, ops.cast_ag(src_video.float().reshape(bs * T, 1, -1), dt), 0)  # [B*T,1,d]
+        src = self._proj(self.input_video_proj, layers.cast_ag(src_video.float().reshape(bs * T, 1, -1), dt), 0)  # [B*T,1,d]
         mask_f = src_video_mask.to(torch.float32).reshape(bs * T, 1)
         pos = self.video_position_embed(mask_f, d, dt)                                                       # [B*T,1,d]
         query = self._sketch_queries(src_sketch, bs, dt)                                                     # [N,B,d]

@@ -10,7 +10,7 @@ import os
 import torch
 from torch import nn
 
-from .. import ops
+from .. import layers, ops, params
 from . import cross_modal_transformer as cmt
 from .cross_modal_transformer import build_cross_modal_transformer
 from .position_encoding import build_position_encoding
@@ -34,7 +34,7 @@ class MLP(nn.Module):
     def forward(self, x, last_act=ops.ACT_NONE):
         for i, layer in enumerate(self.layers):
             act = ops.ACT_RELU if i < self.num_layers - 1 else last_act
-            x = ops.linear(x, layer.weight, layer.bias, act)
+            x = layers.linear(x, layer.weight, layer.bias, act)
         return x
 
 
@@ -53,11 +53,11 @@ class LinearLayer(nn.Module):
     def forward(self, x, seed=0, out_f32=False, seed_dev=None):
         p = self.p if self.training else 0.0
         if self.layer_norm:
-            x = ops.layer_norm(x, self.LayerNorm.weight, self.LayerNorm.bias, p, seed, seed_dev)
+            x = layers.layer_norm(x, self.LayerNorm.weight, self.LayerNorm.bias, p, seed, seed_dev)
         elif p > 0.0:
             raise NotImplementedError('dropout without LayerNorm is not on the reference path')
         lin = self.net[1]
-        return ops.linear(x, lin.weight, lin.bias, ops.ACT_RELU if self.relu else ops.ACT_NONE, out_f32)
+        return layers.linear(x, lin.weight, lin.bias, ops.ACT_RELU if self.relu else ops.ACT_NONE, out_f32)
 
 
 class SVANet(nn.Module):
@@ -114,7 +114,7 @@ class SVANet(nn.Module):
         d = self.transformer.d_model
         overlap = INPUT_OVERLAP and cmt.OVERLAP_QUERY_STREAM and isinstance(self.transformer, cmt.CrossModalTransformer)
         if not overlap:
-            ops.weights.new_epoch()  # re-cast every fp32 master weight once per forward (see ops._WeightCache)
+            params.weights.new_epoch()  # re-cast every fp32 master weight once per forward (see params._WeightCache)
         if self.training:
             self._step += 1
         def mask_side(with_us):
@@ -122,7 +122,7 @@ class SVANet(nn.Module):
             vectors (B*d-sized algebra; their backward is 2 launches per step that used to close the backward on the main stream)"""
             mask_f = src_video_mask.to(torch.float32)
             pos_video = self.video_position_embed(mask_f, d, dt)
-            skch = self._proj(self.input_sketch_proj, ops.cast_ag(src_sketch.float(), dt), 1)
+            skch = self._proj(self.input_sketch_proj, layers.cast_ag(src_sketch.float(), dt), 1)
             skch = skch.reshape(skch.shape[0], -1)
             # key_padding_mask (True on pads) as an additive bias for the cross-attention kernel
             kbias = torch.zeros_like(mask_f).masked_fill_(mask_f == 0, float('-inf'))
@@ -138,9 +138,9 @@ class SVANet(nn.Module):
             side = cmt._side_stream(main.device)
             side.wait_stream(main)   # the optimizer's update, the last readers of the old copies, the caller's inputs
             with torch.cuda.stream(side):
-                ops.weights.new_epoch()
+                params.weights.new_epoch()
                 casts_done = side.record_event()
-            xv = ops.cast_ag(src_video.float(), dt)
+            xv = layers.cast_ag(src_video.float(), dt)
             with torch.cuda.stream(side):
                 pos_video, skch, kbias, us = mask_side(True)
             main.wait_event(casts_done)
@@ -149,15 +149,15 @@ class SVANet(nn.Module):
             for t in [pos_video, skch, kbias] + list(us or []):
                 t.record_stream(main)   # allocated on the query stream, read by the video half on this one
         else:
-            vid = self._proj(self.input_video_proj, ops.cast_ag(src_video.float(), dt), 0)
+            vid = self._proj(self.input_video_proj, layers.cast_ag(src_video.float(), dt), 0)
             pos_video, skch, kbias, us = mask_side(False)
         hs = (self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight, us) if us is not None else
               self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight))   # [NL,B,N,d] fp32
         # heads run in fp32 (tiny; keeps logits / box coordinates at full precision)
-        if ops.heads_fusable(hs, self.class_embed, self.bbox_embed):   # both heads, all layers, one launch (csrc/heads.hip)
-            outputs_class, outputs_coord = ops.heads(hs, self.class_embed, self.bbox_embed)
+        if layers.heads_fusable(hs, self.class_embed, self.bbox_embed):   # both heads, all layers, one launch (csrc/heads.hip)
+            outputs_class, outputs_coord = layers.heads(hs, self.class_embed, self.bbox_embed)
         else:
-            outputs_class = ops.linear(hs, self.class_embed.weight, self.class_embed.bias)
+            outputs_class = layers.linear(hs, self.class_embed.weight, self.class_embed.bias)
             outputs_coord = self.bbox_embed(hs, last_act=ops.ACT_SIGMOID)
         out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1]}
         if self.aux_loss:

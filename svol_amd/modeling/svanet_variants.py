@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
+from .. import layers, ops, params
 from .position_encoding import build_position_encoding
 from .svanet import MLP, LinearLayer, _DTYPES
 from .transformer import build_transformer
@@ -42,12 +42,12 @@ class _DetrHead(nn.Module):
         if not src_video.is_cuda:
             raise RuntimeError(f'svol_amd.{type(self).__name__} runs on the MI355X HIP kernels only; move the module and '
                                'its inputs to cuda (there is no CPU path — the CPU oracle lives under oracle/).')
-        ops.weights.new_epoch()
+        params.weights.new_epoch()
         if self.training:
             self._step += 1
 
     def _heads(self, hs):
-        outputs_class = ops.linear(hs, self.class_embed.weight, self.class_embed.bias)
+        outputs_class = layers.linear(hs, self.class_embed.weight, self.class_embed.bias)
         outputs_coord = self.bbox_embed(hs, last_act=ops.ACT_SIGMOID)
         out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1]}
         if self.aux_loss:
@@ -62,7 +62,7 @@ class _DetrHead(nn.Module):
         sk = src_sketch.float().repeat(1, nq, 1).permute(1, 0, 2)                 # [N,B,D]
         qw = self.query_embed.weight.unsqueeze(1).repeat(1, bs, 1)                # [N,B,d]
         query = torch.cat([qw, sk], dim=2).contiguous()                           # [N,B,d+D]
-        return self._proj(self.input_query_proj, ops.cast_ag(query, dt), 3)
+        return self._proj(self.input_query_proj, layers.cast_ag(query, dt), 3)
 
 
 class SVANet(_DetrHead):
@@ -104,12 +104,12 @@ class SVANet(_DetrHead):
         query = self.query_embed.weight
         if self.mode == 'concat_to_seq':
             sk = src_sketch.float().repeat(1, src_video.shape[1], 1)                      # needs Ls == 1, as the reference
-            src = self._proj(self.input_proj, ops.cast_ag(torch.cat([sk, src_video.float()], dim=2).contiguous(), dt), 2)
+            src = self._proj(self.input_proj, layers.cast_ag(torch.cat([sk, src_video.float()], dim=2).contiguous(), dt), 2)
             mask_f = vmask
             pos = self.video_position_embed(vmask, d, dt)
         elif self.mode == 'append_to_seq':
-            skch = self._proj(self.input_sketch_proj, ops.cast_ag(src_sketch.float(), dt), 1)
-            vid = self._proj(self.input_video_proj, ops.cast_ag(src_video.float(), dt), 0)
+            skch = self._proj(self.input_sketch_proj, layers.cast_ag(src_sketch.float(), dt), 1)
+            vid = self._proj(self.input_video_proj, layers.cast_ag(src_video.float(), dt), 0)
             smask = src_sketch_mask.to(torch.float32)
             pos_s = (self.sketch_position_embed(smask, d, dt) if self.use_sketch_pos
                      else torch.zeros(skch.shape, dtype=dt, device=skch.device))
@@ -117,7 +117,7 @@ class SVANet(_DetrHead):
             src = torch.cat([skch, vid], dim=1)
             mask_f = torch.cat([smask, vmask], dim=1)
         else:  # concat_to_qry
-            src = self._proj(self.input_video_proj, ops.cast_ag(src_video.float(), dt), 0)
+            src = self._proj(self.input_video_proj, layers.cast_ag(src_video.float(), dt), 0)
             mask_f = vmask
             pos = self.video_position_embed(vmask, d, dt)
             query = self._sketch_queries(src_sketch, src_video.shape[0], dt)

@@ -37,7 +37,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .. import ops
+from .. import layers, ops
 
 _DTYPES = {'bf16': torch.bfloat16, 'fp32': torch.float32, 'fp16': torch.float16, torch.float16: torch.float16, torch.bfloat16: torch.bfloat16,
            torch.float32: torch.float32}
@@ -91,22 +91,22 @@ class TransformerEncoderLayer(nn.Module):
 
     def _ffn(self, x32, x, norm, pos_out, seed=None):
         g, b = _n(norm) if norm is not None else (None, None)
-        return ops.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
+        return layers.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
                           pos_out, self.act, _drop(self, seed, 4, 5))
 
     def forward_post(self, state, pos, kbias, seed=None):
         """state = (x32, x, x + pos) -> same triple (transformer.py:175-194)."""
         x32, x, xpos = state
-        y32, y = ops.self_attn_ln(x32, x, xpos, *_mha(self.self_attn), *_n(self.norm1), None, self.nhead, kbias,
+        y32, y = layers.self_attn_ln(x32, x, xpos, *_mha(self.self_attn), *_n(self.norm1), None, self.nhead, kbias,
                                   _drop(self, seed, 0, 1))
         return self._ffn(y32, y, self.norm2, pos, seed)
 
     def forward_pre(self, x32, pos, kbias, seed=None):
         """x32 -> x32 (transformer.py:196-208)."""
         dt = pos.dtype
-        y, ypos = ops.ln_stream(x32, *_n(self.norm1), pos, dt)
-        s32 = ops.self_attn_ln(x32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, kbias, _drop(self, seed, 0, 1))
-        y2 = ops.ln_stream(s32, *_n(self.norm2), None, dt)
+        y, ypos = layers.ln_stream(x32, *_n(self.norm1), pos, dt)
+        s32 = layers.self_attn_ln(x32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, kbias, _drop(self, seed, 0, 1))
+        y2 = layers.ln_stream(s32, *_n(self.norm2), None, dt)
         return self._ffn(s32, y2, None, None, seed)
 
     def forward(self, state, pos, kbias, seed=None):
@@ -131,15 +131,15 @@ class TransformerDecoderLayer(nn.Module):
 
     def _ffn(self, x32, x, norm, pos_out, seed=None):
         g, b = _n(norm) if norm is not None else (None, None)
-        return ops.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
+        return layers.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
                           pos_out, self.act, _drop(self, seed, 4, 5))
 
     def forward_post(self, state, mem, mempos, qpos, kbias, need_weights, seed=None):
         """state = (t32, t, t + query_pos) -> (same triple, att | None)   (transformer.py:229-250)."""
         t32, t, tpos = state
-        a32, a, apos = ops.self_attn_ln(t32, t, tpos, *_mha(self.self_attn), *_n(self.norm1), qpos, self.nhead, None,
+        a32, a, apos = layers.self_attn_ln(t32, t, tpos, *_mha(self.self_attn), *_n(self.norm1), qpos, self.nhead, None,
                                         _drop(self, seed, 0, 1))
-        r = ops.cross_attn_ln(a32, a, apos, mempos, mem, *_mha(self.multihead_attn), *_n(self.norm2), None, self.nhead,
+        r = layers.cross_attn_ln(a32, a, apos, mempos, mem, *_mha(self.multihead_attn), *_n(self.norm2), None, self.nhead,
                               kbias, need_weights, _drop(self, seed, 2, 3))
         c32, c = r[0], r[1]
         att = r[2] if need_weights else None
@@ -148,13 +148,13 @@ class TransformerDecoderLayer(nn.Module):
     def forward_pre(self, t32, mem, mempos, qpos, kbias, need_weights, seed=None):
         """t32 -> (t32, att | None)   (transformer.py:252-283)."""
         dt = mem.dtype
-        y, ypos = ops.ln_stream(t32, *_n(self.norm1), qpos, dt)
-        s32 = ops.self_attn_ln(t32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, None, _drop(self, seed, 0, 1))
-        y2, y2pos = ops.ln_stream(s32, *_n(self.norm2), qpos, dt)
-        r = ops.cross_attn_ln(s32, y2, y2pos, mempos, mem, *_mha(self.multihead_attn), None, None, None, self.nhead,
+        y, ypos = layers.ln_stream(t32, *_n(self.norm1), qpos, dt)
+        s32 = layers.self_attn_ln(t32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, None, _drop(self, seed, 0, 1))
+        y2, y2pos = layers.ln_stream(s32, *_n(self.norm2), qpos, dt)
+        r = layers.cross_attn_ln(s32, y2, y2pos, mempos, mem, *_mha(self.multihead_attn), None, None, None, self.nhead,
                               kbias, need_weights, _drop(self, seed, 2, 3))
         c32, att = (r[0], r[1]) if need_weights else (r, None)
-        y3 = ops.ln_stream(c32, *_n(self.norm3), None, dt)
+        y3 = layers.ln_stream(c32, *_n(self.norm3), None, dt)
         return self._ffn(c32, y3, None, None, seed), att
 
     def forward(self, state, mem, mempos, qpos, kbias, need_weights=False, seed=None):
@@ -188,15 +188,15 @@ class TransformerEncoder(nn.Module):
             for layer in self.layers:
                 x32 = layer(x32, pos, kbias, seed)
             if self.norm is not None:  # the builder gives the pre-norm encoder a closing norm (:26)
-                return ops.ln_stream(x32, *_n(self.norm), pos, dt, True)
-            x = ops.cast_ag(x32, dt)
+                return layers.ln_stream(x32, *_n(self.norm), pos, dt, True)
+            x = layers.cast_ag(x32, dt)
             return x32, x, x + pos
-        x = ops.cast_ag(src32, dt)
+        x = layers.cast_ag(src32, dt)
         state = (src32, x, x + pos)  # layer 0's q = k = src + pos (:183); later layers get it from the norm2 epilogue
         for layer in self.layers:
             state = layer(state, pos, kbias, seed)
         if self.norm is not None:
-            return ops.ln_stream(state[0], *_n(self.norm), pos, dt, True)
+            return layers.ln_stream(state[0], *_n(self.norm), pos, dt, True)
         return state
 
 
@@ -225,13 +225,13 @@ class TransformerDecoder(nn.Module):
             state, att = layer(state, mem, mempos, qpos, kbias, need_weights and self.return_intermediate, seed)
             if self.return_intermediate:
                 o32 = state if pre else state[0]
-                inter.append(ops.ln_stream(o32, *_n(self.norm), None, torch.float32) if self.norm is not None else o32)
+                inter.append(layers.ln_stream(o32, *_n(self.norm), None, torch.float32) if self.norm is not None else o32)
                 atts.append(att)
         if self.return_intermediate:
             return torch.stack(inter), (torch.stack(atts) if need_weights else None)
         o32 = state if pre else state[0]
         if self.norm is not None:
-            o32 = ops.ln_stream(o32, *_n(self.norm), None, torch.float32)
+            o32 = layers.ln_stream(o32, *_n(self.norm), None, torch.float32)
         return o32.unsqueeze(0), None
 
 
@@ -277,7 +277,7 @@ class Transformer(nn.Module):
                                'lives under oracle/)')
         dt = self.compute_dtype
         src32 = src if src.dtype == torch.float32 else src.float()
-        pos = pos_embed if pos_embed.dtype == dt else ops.cast_ag(pos_embed.float().contiguous(), dt)
+        pos = pos_embed if pos_embed.dtype == dt else layers.cast_ag(pos_embed.float().contiguous(), dt)
         kbias = None
         if mask is not None:
             kbias = torch.zeros(mask.shape, dtype=torch.float32, device=src.device).masked_fill_(mask.bool(), float('-inf'))
@@ -285,7 +285,7 @@ class Transformer(nn.Module):
             qpos = query_embed.transpose(0, 1)
         else:
             qpos = query_embed
-        qpos = ops.cast_ag(qpos.float().contiguous(), dt)
+        qpos = layers.cast_ag(qpos.float().contiguous(), dt)
         seed = None
         if self.training:
             self._drop_step += 1

@@ -1,10 +1,11 @@
 """Host-side operators of the SVOL hot path: thin tensor wrappers over the C-ABI
-(libsvol_hip.so) and the ``torch.autograd.Function`` s that compose them.
+(libsvol_hip.so), no autograd.  The ``torch.autograd.Function`` s that compose them are in
+``layers``, the weight cache and the gradient sinks in ``params``; both import this module,
+which imports neither.
 
-PyTorch here is plumbing only: device memory, the current HIP stream and the
-autograd tape.  Every arithmetic op on the hot path is a hand-written gfx950
-kernel behind ``include/svol_hip.h``; there is no CPU or eager fallback — a
-non-CUDA tensor or a missing library raises.
+PyTorch here is plumbing only: device memory and the current HIP stream.  Every arithmetic
+op on the hot path is a hand-written gfx950 kernel behind ``include/svol_hip.h``; there is
+no CPU or eager fallback — a non-CUDA tensor or a missing library raises.
 """
 from __future__ import annotations
 
@@ -155,7 +156,7 @@ def gemm_nt(A, B, bias=None, act=ACT_NONE, residual=None, want_pre=False, out=No
 
 
 def gemm_nt_split(A, W_hilo, bias=None, out=None):
-    """out[M,N] (bf16) = A[M,K] @ (W_hi + W_lo)[N,K]^T + bias with W_hilo [N, 2K] = [hi | lo] (weights.get_split): one
+    """out[M,N] (bf16) = A[M,K] @ (W_hi + W_lo)[N,K]^T + bias with W_hilo [N, 2K] = [hi | lo] (the weight cache's get_split): one
     K-concatenated product, [A | A] is never materialised."""
     assert A.dim() == 2 and W_hilo.dim() == 2 and A.stride(1) == 1 and W_hilo.stride(1) == 1 and A.dtype == torch.bfloat16
     M, K = A.shape
@@ -601,920 +602,3 @@ def attn_weights_mean(q, k, lse2, B, H, Lq, Lk, dh, kbias=None, premul=0.0):
                                            B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _dt(q), _stream())
     _lib.check(rc, 'svol_attn_weights_mean')
     return att
-
-
-# ----------------------------------------------------------------------------
-# parameter cache: fp32 master weights -> compute-dtype copies (W and W^T), refreshed when the
-# optimizer bumps the tensor version.  One cast per weight per step.
-# ----------------------------------------------------------------------------
-class _WeightCache:
-    """fp32 master weight -> compute-dtype copies (W and W^T) in persistent buffers.
-
-    Every weight is (re)cast once per EPOCH — the model advances the epoch at the start of every forward —
-    because tensor version counters cannot be trusted to see optimizer updates (``torch.optim.AdamW(fused=True)``
-    rewrites parameters without bumping ``_version`` on ROCm).  The first time a weight is seen it is cast on the
-    spot and registered; from then on ``new_epoch()`` refreshes ALL registered weights of a (device, dtype) with
-    ONE ``svol_cast_transpose_multi`` launch driven by a device-side descriptor table (64 launches -> 1 per step
-    at the benchmark size).  With ``static=True`` (frozen weights, e.g. serving) nothing is refreshed."""
-
-    def __init__(self):
-        self.epoch = 0
-        self.static = False
-        self._sets = {}  # (device, dtype) -> {'items': [(weakref(param), entry)], 'table': tensor|None, 'tiles': int}
-
-    class _Entry:
-        __slots__ = ('wc', 'wt', 'ws', 'ptr', 'epoch', 'version', 'shape')
-
-    def new_epoch(self):
-        wgrad.forward_starts()
-        if self.static:
-            return
-        self.epoch += 1
-        for key, st in self._sets.items():
-            self._refresh(key, st)
-
-    def _refresh(self, key, st):
-        dev, dtype = key
-        if dtype not in _DT:
-            return
-        def alive(r, e):
-            w = r()
-            if w is None:
-                return False
-            if e.ws is not None:   # split entry: keyed by (row0, rows), ptr = address of the first row
-                return any(v is e for v in getattr(w, '_svol_split', {}).values())
-            return getattr(w, '_svol_cache', {}).get(dtype) is e and w.data_ptr() == e.ptr
-        live = [(r, e) for (r, e) in st['items'] if alive(r, e)]
-        if len(live) != len(st['items']) or st['table'] is None:
-            st['items'] = live
-            st['table'] = None
-            if not live:
-                return
-            recs = []
-            t0 = 0
-            for r, e in live:
-                R, C = e.shape
-                tc = (C + 31) // 32
-                # src, dst, dstT, dstS (8 bytes each) ; R, C, tiles_c, tile_begin (int32)
-                if e.ws is not None:   # split copy of a row range of the weight (get_split): its own record
-                    recs.append((e.ptr, 0, 0, e.ws.data_ptr(), R, C, tc, t0))
-                else:
-                    recs.append((e.ptr, 0 if dtype == torch.float32 else e.wc.data_ptr(), e.wt.data_ptr(), 0, R, C, tc, t0))
-                t0 += ((R + 31) // 32) * tc
-            import struct
-            blob = b''.join(struct.pack('<QQQQiiii', *rec) for rec in recs)
-            st['table'] = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            st['tiles'] = t0
-            st['gen'] = st.get('gen', 0) + 1
-        _lib.check(_lib.lib().svol_cast_transpose_multi(_ptr(st['table']), len(st['items']), st['tiles'], _DT[dtype],
-                                                        _stream()), 'svol_cast_transpose_multi')
-        # The copies were allocated on the stream of their first use (the query half's weights: the side stream) and are
-        # rewritten HERE, on the caller's stream.  Tell the allocator, or a copy whose owner dies (a model dropped between two
-        # tests, a re-built module) goes back to its own stream's pool while this launch is still queued and the refresh lands
-        # in whoever got the block next (seen as a 1-in-15 garbage forward in the test suite, never with one long-lived model)
-        if dev.type == 'cuda':
-            cur = _current_stream_obj()
-            done = st.setdefault('recorded', set())
-            key_ = (cur.cuda_stream, st.get('gen', 0))
-            if key_ not in done:
-                done.clear()
-                done.add(key_)
-                for r, e in st['items']:
-                    if e.ws is not None:
-                        e.ws.record_stream(cur)
-                        continue
-                    if e.wc is not None and e.wc.dtype != torch.float32:
-                        e.wc.record_stream(cur)
-                    e.wt.record_stream(cur)
-        for r, e in st['items']:
-            e.epoch = self.epoch
-            e.version = r()._version
-
-    def get(self, w: torch.Tensor, dtype: torch.dtype):
-        cache = getattr(w, '_svol_cache', None)
-        if cache is None:
-            cache = {}
-            try:
-                w._svol_cache = cache
-            except Exception:  # pragma: no cover  (non-leaf views etc.: just do not cache)
-                pass
-        e = cache.get(dtype)
-        if e is not None and e.ptr == w.data_ptr() and e.version == w._version and (self.static or e.epoch == self.epoch):
-            return e.wc, e.wt
-        wd = w.detach()
-        assert wd.dtype == torch.float32 and wd.dim() == 2 and wd.is_contiguous()
-        fresh = e is None or e.ptr != w.data_ptr() or tuple(w.shape) != e.shape
-        if fresh:
-            e = self._Entry()
-            e.ws = None
-            e.shape, e.ptr = tuple(w.shape), w.data_ptr()
-            R, C = e.shape
-            e.wc = wd if dtype == torch.float32 else torch.empty((R, C), dtype=dtype, device=w.device)
-            e.wt = torch.empty((C, R), dtype=dtype, device=w.device)
-        R, C = e.shape
-        _lib.check(_lib.lib().svol_cast_transpose(_ptr(wd), 0 if dtype == torch.float32 else _ptr(e.wc), _ptr(e.wt),
-                                                  _DT[dtype], R, C, _stream()), 'svol_cast_transpose')
-        e.epoch, e.version = self.epoch, w._version
-        if fresh:
-            cache[dtype] = e
-            st = self._sets.setdefault((w.device, dtype), {'items': [], 'table': None, 'tiles': 0})
-            try:
-                import weakref
-                st['items'].append((weakref.ref(w), e))
-                st['table'] = None
-            except TypeError:  # pragma: no cover
-                pass
-        return e.wc, e.wt
-
-    def get_split(self, w: torch.Tensor, row0: int, rows: int):
-        """bf16 split copy [rows, 2C] = [hi | lo] of rows [row0, row0 + rows) of the fp32 master weight `w` (svol_cast_split):
-        the operand of gemm_nt_split.  Refreshed once per epoch by the same multi-weight launch as the plain copies."""
-        cache = getattr(w, '_svol_split', None)
-        if cache is None:
-            cache = {}
-            try:
-                w._svol_split = cache
-            except Exception:  # pragma: no cover
-                pass
-        C = w.shape[1]
-        ptr = w.data_ptr() + row0 * C * 4
-        e = cache.get((row0, rows))
-        if e is not None and e.ptr == ptr and e.version == w._version and (self.static or e.epoch == self.epoch):
-            return e.ws
-        wd = w.detach()
-        assert wd.dtype == torch.float32 and wd.dim() == 2 and wd.is_contiguous()
-        fresh = e is None or e.ptr != ptr
-        if fresh:
-            e = self._Entry()
-            e.wc = e.wt = None
-            e.shape, e.ptr = (rows, C), ptr
-            e.ws = torch.empty((rows, 2 * C), dtype=torch.bfloat16, device=w.device)
-        _lib.check(_lib.lib().svol_cast_split(ptr, C, _ptr(e.ws), rows, C, _stream()), 'svol_cast_split')
-        e.epoch, e.version = self.epoch, w._version
-        if fresh:
-            cache[(row0, rows)] = e
-            st = self._sets.setdefault((w.device, torch.bfloat16), {'items': [], 'table': None, 'tiles': 0})
-            try:
-                import weakref
-                st['items'].append((weakref.ref(w), e))
-                st['table'] = None
-            except TypeError:  # pragma: no cover
-                pass
-        return e.ws
-
-
-weights = _WeightCache()
-
-
-# ----------------------------------------------------------------------------
-# gradient sinks: when svol_amd.parallel.BucketedGradAllReduce owns the gradients (param.grad is a view into
-# a flat fp32 bucket that is zeroed once per step), the weight-/bias-/LayerNorm-gradient kernels accumulate
-# STRAIGHT into that view and the Function returns None for the parameter — no per-parameter memset, no
-# AccumulateGrad add.  The parameter's post-accumulate-grad hook (the reducer's bucket countdown) still fires:
-# autograd runs the AccumulateGrad node with an undefined gradient after the producing Function has finished.
-# ----------------------------------------------------------------------------
-class GradSink:
-    """view: the parameter's slice of a flat gradient bucket.  owner / bucket: who to tell that the gradient is complete when the
-    producing Function keeps the parameter OUT of the autograd graph (svol_amd.blocks: no AccumulateGrad node, no hook) —
-    ``owner.params_done(bucket, n)``."""
-    __slots__ = ('view', 'owner', 'bucket')
-
-    def __init__(self, view, owner=None, bucket=-1):
-        self.view, self.owner, self.bucket = view, owner, bucket
-
-
-def _claim(p, needed=True):
-    """forward: the sink of parameter `p` if its gradient can be written in place, else None."""
-    s = getattr(p, '_svol_sink', None) if (needed and p is not None) else None
-    g = p.grad if s is not None else None
-    if g is None or g.data_ptr() != s.view.data_ptr():
-        return None
-    return s
-
-
-def _tgt(sink, shape, device):
-    return sink.view if sink is not None else torch.zeros(shape, dtype=torch.float32, device=device)
-
-
-# ----------------------------------------------------------------------------
-# autograd Functions
-# ----------------------------------------------------------------------------
-def _pos_grad(dypos, pos_shape, D):
-    """gradient of a broadcast positional operand (the learnable query embedding): sum over the batch."""
-    rows = 1
-    for n in pos_shape[:-1]:
-        rows *= n
-    g = colsum(dypos.reshape(-1, rows * D).contiguous())
-    return cast(g.view(pos_shape), dypos.dtype)
-
-
-class LayerNormFn(torch.autograd.Function):
-    """y = dropout(LN(x)), compute dtype in / out (input projections, svanet.py:168-178)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, p, seed, seed_dev):
-        shp = x.shape
-        x2 = x.reshape(-1, shp[-1])
-        _, y, _, mean, rstd = layernorm_fwd(x2, gamma, beta, x.dtype, None, p, seed, seed_dev=seed_dev)
-        ctx.save_for_backward(x2, gamma, mean, rstd, seed_dev)
-        ctx.p, ctx.seed, ctx.shp = p, seed, shp
-        ctx.sinks = (_claim(gamma, ctx.needs_input_grad[1]), _claim(beta, ctx.needs_input_grad[2]))
-        return y.view(shp)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, gamma, mean, rstd, seed_dev = ctx.saved_tensors
-        sg, sb = ctx.sinks
-        _, dx, dg, db = layernorm_bwd(None, dy, None, x2, gamma, mean, rstd, x2.dtype, ctx.p, ctx.seed, seed_dev=seed_dev,
-                                      dg_out=sg.view if sg else None, db_out=sb.view if sb else None)
-        return dx.view(ctx.shp), None if sg else dg, None if sb else db, None, None, None
-
-
-def layer_norm(x, gamma, beta, p=0.0, seed=0, seed_dev=None):
-    return LayerNormFn.apply(x, gamma, beta, p, seed, seed_dev)
-
-
-class LinearFn(torch.autograd.Function):
-    """y = act(x W^T + b) (nn.Linear + F.relu / sigmoid).  out_f32: y is emitted in fp32 (it starts the
-    fp32 residual stream); its gradient then arrives in fp32 and is cast once."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, act, out_f32):
-        if act == ACT_GELU:
-            raise _lib.SvolHipError('LinearFn: GELU is only available fused in MLPLNFn')
-        shp = x.shape
-        x2 = x.reshape(-1, shp[-1])
-        Wc, WcT = weights.get(W, x.dtype)
-        y = gemm_nt(x2, Wc, b, act, out_f32=out_f32)
-        ctx.save_for_backward(x2, y if act != ACT_NONE else None)
-        ctx.WcT, ctx.act, ctx.shp, ctx.has_b = WcT, act, shp, b is not None
-        ctx.need_dx = ctx.needs_input_grad[0]
-        epc = 4 if x.dtype == torch.float32 else 8
-        ok = W.shape[0] % epc == 0
-        ctx.sinks = (_claim(W, ok and ctx.needs_input_grad[1]), _claim(b, ok and ctx.needs_input_grad[2]))
-        return y.view(*shp[:-1], W.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, y = ctx.saved_tensors
-        N = dy.shape[-1]
-        d = dy.reshape(-1, N)
-        if not d.is_contiguous():
-            d = d.contiguous()
-        if d.dtype != x2.dtype:
-            d = cast(d, x2.dtype)
-        if ctx.act != ACT_NONE:
-            d = act_bwd(d, y, ctx.act)
-        # out-features that are not a multiple of the 16-byte chunk (2-class / 4-coordinate heads):
-        # zero-pad the contraction / column dimension
-        epc = 4 if d.dtype == torch.float32 else 8
-        WcT = ctx.WcT
-        Np = (N + epc - 1) // epc * epc
-        if N % epc:
-            dp = torch.zeros((d.shape[0], Np), dtype=d.dtype, device=d.device)
-            dp[:, :N] = d
-            wp = torch.zeros((WcT.shape[0], Np), dtype=WcT.dtype, device=WcT.device)
-            wp[:, :N] = WcT
-            d, WcT = dp, wp
-        # db = column sums of d, fused into the dW GEMM; without gradient sinks dW and db share one zeroed buffer
-        K_ = x2.shape[1]
-        sW, sb = ctx.sinks
-        if sW is not None and (sb is not None or not ctx.has_b):
-            gemm_tn_sink(d, x2, out=sW.view, colsum=sb.view if sb else None)
-            dW = db = None
-        else:
-            buf = torch.zeros((Np * K_ + Np,), dtype=torch.float32, device=d.device)
-            dWp, dbp = buf[:Np * K_].view(Np, K_), buf[Np * K_:]
-            gemm_tn(d, x2, out=dWp, colsum=dbp if ctx.has_b else None)
-            dW = dWp[:N]
-            db = dbp[:N] if ctx.has_b else None
-            if sW is not None:
-                sW.view.add_(dW)
-                dW = None
-            if sb is not None:
-                sb.view.add_(db)
-                db = None
-        dx = gemm_nt(d, WcT).view(ctx.shp) if ctx.need_dx else None
-        return dx, dW, db, None, None
-
-
-def linear(x, W, b=None, act=ACT_NONE, out_f32=False):
-    return LinearFn.apply(x, W, b, act, out_f32)
-
-
-# ---- residual-stream blocks ------------------------------------------------------------------
-# Every block maps the stream triple (x32 fp32 residual value, x compute-dtype copy, xpos = x + pos)
-# to the next triple; the pre-norm sum s = x32 + f(x) stays fp32 and never leaves the block.
-def _ln_out(s32, gamma, beta, pos_out, dt):
-    y32, y, ypos, mean, rstd = layernorm_fwd(s32, gamma, beta, dt, pos_out, want32=True)
-    return y32, y, ypos, mean, rstd
-
-
-def _res_grad(ds32, dt, cs_out):
-    """blocks without a post-norm (pre-norm layers): the incoming fp32 stream gradient IS the gradient of the
-    pre-norm sum; cast it for the GEMMs and take its column sums (bias gradient of the Linear that fed the sum)."""
-    D = ds32.shape[-1]
-    ds32 = ds32.reshape(-1, D)
-    if not ds32.is_contiguous():
-        ds32 = ds32.contiguous()
-    g = cast(ds32, dt)
-    return ds32, g, colsum(g, out=cs_out)
-
-
-class MLPLNFn(torch.autograd.Function):
-    """LN(x32 + fc2(act(fc1(x))))  — cross_modal_transformer.py:142-143,157-158 + MLP :163-179 (GELU); the FFN of the
-    enc/dec Transformer (ReLU, transformer.py:191-193,245-247).  gamma None: no norm, the fp32 sum is the output
-    (pre-norm layers, transformer.py:205-207: x is then LN(x32), not a copy of x32)."""
-
-    @staticmethod
-    def forward(ctx, x32, x, W1, b1, W2, b2, gamma, beta, pos_out, act=ACT_GELU, drop=None, wc=None):
-        """drop = (p, seed_hidden, seed_residual): training-mode dropout of the enc/dec FFN — linear2(dropout(act(linear1 x))) and
-        x + dropout2(.) (transformer.py:168,171,238-240).  wc = (W1, W1^T, W2, W2^T) in the compute dtype, cast by the caller
-        (a module that runs before the forward that advances ``weights``' epoch); None: from ``weights``."""
-        ctx.set_materialize_grads(False)
-        if drop is not None and drop[0] <= 0.0:
-            drop = None
-        ctx.drop = drop
-        shp = x.shape
-        D = shp[-1]
-        dt = x.dtype
-        x2, x32_2 = x.reshape(-1, D), x32.reshape(-1, D)
-        if wc is not None:
-            W1c, W1T, W2c, W2T = wc
-        else:
-            W1c, W1T = weights.get(W1, dt)
-            W2c, W2T = weights.get(W2, dt)
-        if act == ACT_GELU:
-            hid, aux = gemm_nt(x2, W1c, b1, ACT_GELU, want_pre=True)   # aux = pre-activation
-        elif act == ACT_RELU:
-            hid = aux = gemm_nt(x2, W1c, b1, ACT_RELU)                 # relu' = [hid > 0]
-        else:
-            raise _lib.SvolHipError('MLPLNFn: activation must be GELU or ReLU')
-        if drop is not None:
-            dropout(hid, drop[0], drop[1], out=hid)   # (ReLU: aux IS hid — kept entries stay positive, dropped ones get relu' = 0, as the mask wants)
-            s32 = dropout_add(gemm_nt(hid, W2c, b2, ACT_NONE, out_f32=True), x32_2 if x32_2.is_contiguous() else x32_2.contiguous(),
-                              drop[0], drop[2])
-        else:
-            s32 = gemm_nt(hid, W2c, b2, ACT_NONE, residual=x32_2, out_f32=True)
-        ctx.W1T, ctx.W2T, ctx.shp, ctx.act, ctx.has_ln = W1T, W2T, shp, act, gamma is not None
-        ctx.pos_shape = pos_out.shape if pos_out is not None else None
-        nig = ctx.needs_input_grad
-        ctx.sinks = tuple(_claim(p_, nig[i]) for i, p_ in ((2, W1), (3, b1), (4, W2), (5, b2), (6, gamma), (7, beta)))
-        if gamma is None:
-            ctx.save_for_backward(x2, aux, hid, None, None, None, None)
-            return s32.view(shp)
-        y32, y, ypos, mean, rstd = _ln_out(s32, gamma, beta, pos_out, dt)
-        ctx.save_for_backward(x2, aux, hid, s32, gamma, mean, rstd)
-        if pos_out is not None:
-            return y32.view(shp), y.view(shp), ypos.view(shp)
-        return y32.view(shp), y.view(shp)
-
-    @staticmethod
-    def backward(ctx, dy32, dy=None, dypos=None):
-        x2, aux, hid, s32, gamma, mean, rstd = ctx.saved_tensors
-        dt = x2.dtype
-        D = x2.shape[1]
-        dpos = None
-        if ctx.pos_shape is not None and ctx.needs_input_grad[8] and dypos is not None:
-            dpos = _pos_grad(dypos, ctx.pos_shape, D)
-        sW1, sb1, sW2, sb2, sg, sbt = ctx.sinks
-        vw = lambda s_: s_.view if s_ is not None else None
-        drop = ctx.drop
-        if drop is not None:   # the residual branch's gradient passes the residual dropout's mask before it meets any GEMM
-            if ctx.has_ln:
-                ds32, ds, dg, dbt = layernorm_bwd(dy32, dy, dypos, s32, gamma, mean, rstd, dt, want32=True, dg_out=vw(sg),
-                                                  db_out=vw(sbt))
-            else:
-                ds32 = dy32.reshape(-1, D)
-                ds32 = ds32 if ds32.is_contiguous() else ds32.contiguous()
-                ds = torch.empty((ds32.shape[0], D), dtype=dt, device=ds32.device)   # (never ds32 itself: that is the stream's gradient)
-                dg = dbt = None
-                ds = dropout(cast(ds32, dt), drop[0], drop[2], out=ds)
-            if ctx.has_ln:
-                dropout(ds, drop[0], drop[2], out=ds)
-            db2 = colsum(ds, out=vw(sb2))
-        elif ctx.has_ln:
-            ds32, ds, dg, dbt, db2 = layernorm_bwd(dy32, dy, dypos, s32, gamma, mean, rstd, dt, want32=True,
-                                                   want_colsum=True, dg_out=vw(sg), db_out=vw(sbt), cs_out=vw(sb2))
-        else:
-            ds32, ds, db2 = _res_grad(dy32, dt, vw(sb2))
-            dg = dbt = None
-        F_ = hid.shape[1]
-        if sW1 is not None and sW2 is not None:
-            dW1, dW2 = sW1.view, sW2.view
-        else:
-            wbuf = torch.zeros((2 * D * F_,), dtype=torch.float32, device=ds.device)  # one memset for dW1 | dW2
-            dW1, dW2 = wbuf[:D * F_].view(F_, D), wbuf[D * F_:].view(D, F_)
-        tn = gemm_tn_sink if (sW1 is not None and sW2 is not None) else (lambda A_, B_, out: gemm_tn(A_, B_, out=out))
-        tn(ds, hid, out=dW2)
-        # (ds W2) * act'(aux) and its column sums, one kernel
-        if drop is not None:   # ... then the hidden dropout's mask, then the column sums
-            dpre, _ = gemm_nt_dact(ds, ctx.W2T, aux, ctx.act, want_colsum=False)
-            dropout(dpre, drop[0], drop[1], out=dpre)
-            db1 = colsum(dpre, out=vw(sb1))
-        else:
-            dpre, db1 = gemm_nt_dact(ds, ctx.W2T, aux, ctx.act, colsum_out=vw(sb1))
-        tn(dpre, x2, out=dW1)
-        dx = gemm_nt(dpre, ctx.W1T)
-        if (sW1 is None) != (sW2 is None):  # only one of the two has a sink: add the other by hand
-            for s_, g_ in ((sW1, dW1), (sW2, dW2)):
-                if s_ is not None:
-                    s_.view.add_(g_)
-        n_ = lambda s_, g_: None if s_ is not None else g_
-        return (ds32.view(ctx.shp), dx.view(ctx.shp), n_(sW1, dW1), n_(sb1, db1), n_(sW2, dW2), n_(sb2, db2), n_(sg, dg),
-                n_(sbt, dbt), dpos, None, None, None)
-
-
-# bf16 mode: the VALUE projections of every attention block multiply by split weights W_hi + W_lo (two bf16 operands = 16
-# mantissa bits of the fp32 master weight, one K-concatenated GEMM).  Rounding W_v to bf16 shifts every token's value the same way,
-# which attention over thousands of keys and LayerNorm do not average out: at the benchmark depth (6 layers, L = 6272) the V weights
-# of the query -> video attention (4.3e-3 rms) and of the video self-attention (2.7e-3) were 95 % of the 6.8e-3 rms logit error, the
-# q / k / MLP weights together 1.1e-3 (profiles/round3_bf16_output_error.md).  Forward only: gradients take the plain bf16 copy.
-# SVOL_NO_SPLIT_V=1 restores single-bf16 V weights (A/B; changes results).
-SPLIT_V = os.environ.get('SVOL_NO_SPLIT_V') is None
-
-
-class AttnLNFn(torch.autograd.Function):
-    """LN(xq32 + out_proj(MHA(q = Wq xq_pos, k = Wk xk_pos, v = Wv xv))) with packed in_proj
-    (nn.MultiheadAttention + post-norm, cross_modal_transformer.py:137-141,145-149,151-156; transformer.py:183-189,
-    237-250).  ``self_attn``: xk_pos is xq_pos and xv is xq (one packed projection buffer).  gamma None: no norm, the
-    fp32 sum is the output (pre-norm layers, transformer.py:198-203: xq is then LN(xq32)).  ``need_weights``: also
-    return the head-averaged attention weights [B,Lq,Lk] fp32 (no gradient flows into them)."""
-
-    @staticmethod
-    def forward(ctx, xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, self_attn,
-                need_weights=False, drop=None):
-        """drop = (p, seed_attention, seed_residual): training-mode dropout of the enc/dec attention blocks — on the attention
-        probabilities (nn.MultiheadAttention(dropout=p)) and on the block output before the residual add (dropout1 / dropout2,
-        transformer.py:158-177,216-247).  The returned attention weights stay those of the undropped softmax."""
-        ctx.set_materialize_grads(False)
-        if drop is not None and drop[0] <= 0.0:
-            drop = None
-        ctx.drop = drop
-        B, Lq, d = xq.shape
-        dt = xq.dtype
-        Lk = Lq if self_attn else xv.shape[1]
-        dh = d // H
-        # MIXED cross-attention (the bf16 model's query -> video attention): the few object queries travel in fp32
-        # (xq / xq_pos fp32: q-projection, out-projection, residual and norm in exact fp32 GEMMs — a few hundred rows),
-        # the L video tokens in bf16 (K / V projections and the attention core on the MFMA bf16 path).  q and O cross
-        # the boundary through one rounding each.
-        mixed = (not self_attn) and dt == torch.float32 and xv.dtype != torch.float32
-        dkv = xv.dtype if mixed else dt
-        Wc, WcT = weights.get(W_in, dkv)
-        Woc, WoT = weights.get(W_o, dt)
-        # bf16: the projection GEMM emits q already multiplied by d_h^-1/2 * log2(e) (rounded once, in the fp32
-        # epilogue), which lets the attention kernels exponentiate raw MFMA results
-        premul = (LOG2E / math.sqrt(dh)) if dkv != torch.float32 else 0.0
-        qscale = _qscale(d, premul, xq.device) if premul else None
-        a_qp = xq_pos.reshape(B * Lq, d)
-        a_q = xq.reshape(B * Lq, d)
-        a_kp = a_qp if self_attn else xk_pos.reshape(B * Lk, d)
-        a_v = a_q if self_attn else xv.reshape(B * Lk, d)
-        Wq32T = None
-        # bf16: the V projection uses SPLIT weights (hi + lo, 16 mantissa bits; svol_gemm_nt_split) — see SPLIT_V
-        Wv_hilo = weights.get_split(W_in, 2 * d, d) if (SPLIT_V and dkv == torch.bfloat16 and d % 32 == 0) else None
-        if self_attn:
-            qkv = torch.empty((B * Lq, 3 * d), dtype=dt, device=xq.device)
-            gemm_nt(a_qp, Wc[:2 * d], b_in[:2 * d], out=qkv[:, :2 * d], colscale=qscale)
-            if Wv_hilo is not None:
-                gemm_nt_split(a_q, Wv_hilo, b_in[2 * d:], out=qkv[:, 2 * d:])
-            else:
-                gemm_nt(a_q, Wc[2 * d:], b_in[2 * d:], out=qkv[:, 2 * d:])
-            q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-        else:
-            if mixed:
-                W32, W32T = weights.get(W_in, torch.float32)
-                Wq32T = W32T[:, :d]
-                q = cast(gemm_nt(a_qp, W32[:d], b_in[:d], colscale=qscale[:d]), dkv)
-            else:
-                q = gemm_nt(a_qp, Wc[:d], b_in[:d], colscale=qscale[:d] if qscale is not None else None)
-            kv = torch.empty((B * Lk, 2 * d), dtype=dkv, device=xq.device)
-            gemm_nt(a_kp, Wc[d:2 * d], b_in[d:2 * d], out=kv[:, :d])
-            if Wv_hilo is not None:
-                gemm_nt_split(a_v, Wv_hilo, b_in[2 * d:], out=kv[:, d:])
-            else:
-                gemm_nt(a_v, Wc[2 * d:], b_in[2 * d:], out=kv[:, d:])
-            k, v = kv[:, :d], kv[:, d:]
-        o, lse2 = attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul, drop=(drop[0], drop[1]) if drop is not None else None)
-        att = attn_weights_mean(q, k, lse2, B, H, Lq, Lk, dh, kbias, premul) if need_weights else None
-        if drop is not None:
-            r32 = xq32.reshape(B * Lq, d)
-            s32 = dropout_add(gemm_nt(cast(o, dt) if mixed else o, Woc, b_o, out_f32=True), r32 if r32.is_contiguous() else r32.contiguous(),
-                              drop[0], drop[2])
-        else:
-            s32 = gemm_nt(cast(o, dt) if mixed else o, Woc, b_o, residual=xq32.reshape(B * Lq, d), out_f32=True)
-        ctx.WcT, ctx.WoT, ctx.dims, ctx.self_attn, ctx.premul = WcT, WoT, (B, H, Lq, Lk, dh, d), self_attn, premul
-        ctx.mixed, ctx.Wq32T = mixed, Wq32T
-        ctx.pos_shape = pos_out.shape if pos_out is not None else None
-        ctx.has_ln = gamma is not None
-        nig = ctx.needs_input_grad
-        ctx.sinks = tuple(_claim(p_, nig[i]) for i, p_ in ((5, W_in), (6, b_in), (7, W_o), (8, b_o), (9, gamma),
-                                                           (10, beta)))
-        if any(s_ is None for s_ in ctx.sinks[:6 if ctx.has_ln else 4]):  # all or nothing
-            ctx.sinks = None
-        shp = (B, Lq, d)
-        if att is not None:
-            ctx.mark_non_differentiable(att)
-        tail = (att,) if att is not None else ()
-        if gamma is None:
-            ctx.save_for_backward(a_qp, a_q, a_kp, a_v, q, k, v, o, lse2, kbias, None, None, None, None)
-            return (s32.view(shp),) + tail if tail else s32.view(shp)
-        y32, y, ypos, mean, rstd = _ln_out(s32, gamma, beta, pos_out, dt)
-        ctx.save_for_backward(a_qp, a_q, a_kp, a_v, q, k, v, o, lse2, kbias, s32, gamma, mean, rstd)
-        if pos_out is not None:
-            return (y32.view(shp), y.view(shp), ypos.view(shp)) + tail
-        return (y32.view(shp), y.view(shp)) + tail
-
-    @staticmethod
-    def backward(ctx, dy32, *rest):
-        a_qp, a_q, a_kp, a_v, q, k, v, o, lse2, kbias, s32, gamma, mean, rstd = ctx.saved_tensors
-        B, H, Lq, Lk, dh, d = ctx.dims
-        dt = a_q.dtype
-        WcT, WoT = ctx.WcT, ctx.WoT  # WcT: [d, 3d] ; WoT: [d, d]
-        dy = rest[0] if ctx.has_ln and len(rest) > 0 else None
-        dypos = rest[1] if ctx.has_ln and ctx.pos_shape is not None and len(rest) > 1 else None
-        dpos = None
-        if ctx.pos_shape is not None and ctx.needs_input_grad[11] and dypos is not None:
-            dpos = _pos_grad(dypos, ctx.pos_shape, d)
-        sk = ctx.sinks
-        dg = dbt = None
-        drop = ctx.drop
-        if drop is not None:   # the block output's gradient passes the residual dropout's mask before out_proj's backward
-            if ctx.has_ln:
-                ds32, g, dg, dbt = layernorm_bwd(dy32, dy, dypos, s32, gamma, mean, rstd, dt, want32=True,
-                                                 dg_out=sk[4].view if sk is not None else None,
-                                                 db_out=sk[5].view if sk is not None else None)
-            else:
-                ds32 = dy32.reshape(-1, d)
-                ds32 = ds32 if ds32.is_contiguous() else ds32.contiguous()
-                g = dropout(cast(ds32, dt), drop[0], drop[2], out=torch.empty((ds32.shape[0], d), dtype=dt, device=ds32.device))
-            if ctx.has_ln:
-                dropout(g, drop[0], drop[2], out=g)
-            dbo = colsum(g, out=sk[3].view if sk is not None else None)
-            if sk is not None:
-                dW_in, db_in, dWo = sk[0].view, sk[1].view, sk[2].view
-        elif sk is not None:
-            dW_in, db_in, dWo = sk[0].view, sk[1].view, sk[2].view
-            if ctx.has_ln:
-                ds32, g, dg, dbt, dbo = layernorm_bwd(dy32, dy, dypos, s32, gamma, mean, rstd, dt, want32=True,
-                                                      want_colsum=True, dg_out=sk[4].view, db_out=sk[5].view,
-                                                      cs_out=sk[3].view)
-            else:
-                ds32, g, dbo = _res_grad(dy32, dt, sk[3].view)
-        else:
-            if ctx.has_ln:
-                ds32, g, dg, dbt, dbo = layernorm_bwd(dy32, dy, dypos, s32, gamma, mean, rstd, dt, want32=True,
-                                                      want_colsum=True)
-            else:
-                ds32, g, dbo = _res_grad(dy32, dt, None)
-        if sk is None:
-            gbuf = torch.zeros((3 * d * d + 3 * d + d * d,), dtype=torch.float32, device=g.device)  # one memset
-            dW_in, db_in = gbuf[:3 * d * d].view(3 * d, d), gbuf[3 * d * d:3 * d * d + 3 * d]
-            dWo = gbuf[3 * d * d + 3 * d:].view(d, d)
-        mixed = ctx.mixed
-        adrop = (drop[0], drop[1]) if drop is not None else None
-        tn = gemm_tn_sink if sk is not None else (lambda A_, B_, out, colsum=None: gemm_tn(A_, B_, out=out, colsum=colsum))
-        tn(g, cast(o, dt) if mixed else o, out=dWo)
-        do = gemm_nt(g, WoT)
-        if mixed:
-            do = cast(do, o.dtype)
-        shq = (B, Lq, d)
-        if ctx.self_attn:
-            dqkv = torch.empty((B * Lq, 3 * d), dtype=dt, device=g.device)
-            dq, dk, dv = dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]
-            attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias, ctx.premul, drop=adrop)
-            tn(dqkv[:, :2 * d], a_qp, out=dW_in[:2 * d], colsum=db_in[:2 * d])
-            tn(dv, a_q, out=dW_in[2 * d:], colsum=db_in[2 * d:])
-            dxq_pos = gemm_nt(dqkv[:, :2 * d], WcT[:, :2 * d])  # d(x + pos) = [dq dk] W_qk
-            dxq = gemm_nt(dv, WcT[:, 2 * d:])                    # d(x) through V
-            if sk is not None:
-                dW_in = db_in = dWo = dbo = dg = dbt = None
-            return (ds32.view(shq), dxq.view(shq), dxq_pos.view(shq), None, None, dW_in, db_in, dWo, dbo, dg, dbt,
-                    dpos, None, None, None, None, None)
-        dq = torch.empty((B * Lq, d), dtype=q.dtype, device=g.device)
-        dkv = torch.empty((B * Lk, 2 * d), dtype=k.dtype, device=g.device)
-        dk, dv = dkv[:, :d], dkv[:, d:]
-        attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias, ctx.premul, drop=adrop)
-        if mixed:
-            dq = cast(dq, dt)
-        tn(dq, a_qp, out=dW_in[:d], colsum=db_in[:d])
-        tn(dk, a_kp, out=dW_in[d:2 * d], colsum=db_in[d:2 * d])
-        tn(dv, a_v, out=dW_in[2 * d:], colsum=db_in[2 * d:])
-        dxq_pos = gemm_nt(dq, ctx.Wq32T if mixed else WcT[:, :d])
-        dxk_pos = gemm_nt(dk, WcT[:, d:2 * d])
-        dxv = gemm_nt(dv, WcT[:, 2 * d:])
-        shk = (B, Lk, d)
-        if sk is not None:
-            dW_in = db_in = dWo = dbo = dg = dbt = None
-        return (ds32.view(shq), None, dxq_pos.view(shq), dxk_pos.view(shk), dxv.view(shk), dW_in, db_in, dWo, dbo, dg,
-                dbt, dpos, None, None, None, None, None)
-
-
-class LNStreamFn(torch.autograd.Function):
-    """(y, y + pos) = LN(x32) in the compute dtype from the fp32 residual stream — the norm that OPENS a pre-norm
-    block (transformer.py:198-199, 205, 267-268, 274, 280) and the decoder's shared output norm."""
-
-    @staticmethod
-    def forward(ctx, x32, gamma, beta, pos, dtype, want32):
-        ctx.set_materialize_grads(False)
-        shp = x32.shape
-        D = shp[-1]
-        x2 = x32.reshape(-1, D)
-        y32, y, ypos, mean, rstd = layernorm_fwd(x2, gamma, beta, dtype, pos, want32=want32)
-        ctx.save_for_backward(x2, gamma, mean, rstd)
-        ctx.shp, ctx.dtype, ctx.has_pos, ctx.want32 = shp, dtype, pos is not None, want32
-        ctx.pos_shape = pos.shape if pos is not None else None
-        ctx.sinks = (_claim(gamma, ctx.needs_input_grad[1]), _claim(beta, ctx.needs_input_grad[2]))
-        out = ((y32.view(shp),) if want32 else ()) + (y.view(shp),) + ((ypos.view(shp),) if pos is not None else ())
-        return out if len(out) > 1 else out[0]
-
-    @staticmethod
-    def backward(ctx, *grads):
-        x2, gamma, mean, rstd = ctx.saved_tensors
-        g = list(grads)
-        dy32 = g.pop(0) if ctx.want32 else None
-        dy = g.pop(0)
-        dypos = g.pop(0) if ctx.has_pos else None
-        if dy32 is None and dy is None and dypos is None:
-            return None, None, None, None, None, None
-        sg, sb = ctx.sinks
-        dpos = None
-        if dypos is not None and ctx.needs_input_grad[3]:
-            dpos = _pos_grad(dypos, ctx.pos_shape, x2.shape[1])
-        dx32, _, dg, db = layernorm_bwd(dy32, dy, dypos, x2, gamma, mean, rstd, ctx.dtype, want32=True, want_t=False,
-                                        dg_out=sg.view if sg else None, db_out=sb.view if sb else None)
-        return dx32.view(ctx.shp), None if sg else dg, None if sb else db, dpos, None, None
-
-
-LOG2E = 1.4426950408889634
-_QSCALE = {}
-
-
-def _qscale(d, premul, device):
-    """per-column epilogue factor of the packed q|k projection: premul on the q columns, 1 on the k columns."""
-    key = (d, premul, str(device))
-    t = _QSCALE.get(key)
-    if t is None:
-        t = torch.ones((2 * d,), dtype=torch.float32, device=device)
-        t[:d] = premul
-        _QSCALE[key] = t
-    return t
-
-
-def mlp_ln(x32, x, W1, b1, W2, b2, gamma, beta, pos_out=None, act=ACT_GELU, drop=None):
-    return MLPLNFn.apply(x32, x, W1, b1, W2, b2, gamma, beta, pos_out, act, drop)
-
-
-def self_attn_ln(x32, x, x_pos, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias=None, drop=None):
-    return AttnLNFn.apply(x32, x, x_pos, None, None, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, True, False, drop)
-
-
-def cross_attn_ln(xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias,
-                  need_weights=False, drop=None):
-    return AttnLNFn.apply(xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, False,
-                          need_weights, drop)
-
-
-def ln_stream(x32, gamma, beta, pos, dtype, want32=False):
-    return LNStreamFn.apply(x32, gamma, beta, pos, dtype, want32)
-
-
-class GateFn(torch.autograd.Function):
-    """(mem32, mem, mem + pos) with mem = LN1(x * (1 + a)), a = head-mean softmax of the 1-query
-    sketch->video attention (cross_modal_transformer.py:122-127); u = per-(batch, head) folded
-    key projection [B,H,d] fp32.  x32 is the fp32 residual stream."""
-
-    @staticmethod
-    def forward(ctx, x32, pos, u, gamma, beta, H):
-        ctx.set_materialize_grads(False)
-        B, L, D = x32.shape
-        dt = pos.dtype
-        x2 = x32.reshape(B * L, D).contiguous()
-        assert x2.dtype == torch.float32
-        pos2 = pos.reshape(B * L, D).contiguous()
-        u = u.contiguous().float()
-        y32 = torch.empty((B * L, D), dtype=torch.float32, device=x2.device)
-        y = torch.empty((B * L, D), dtype=dt, device=x2.device)
-        ypos = torch.empty((B * L, D), dtype=dt, device=x2.device)
-        a = torch.empty((B * L,), dtype=torch.float32, device=x2.device)
-        mean = torch.empty_like(a)
-        rstd = torch.empty_like(a)
-        ws = torch.empty((B * H * (L + 2),), dtype=torch.float32, device=x2.device)
-        rc = _lib.lib().svol_gate_fwd(_ptr(x2), _ptr(pos2), _ptr(u), _ptr(gamma), _ptr(beta), _ptr(y32), _ptr(y),
-                                      _ptr(ypos), _ptr(a), _ptr(mean), _ptr(rstd), _ptr(ws), B, L, D, H, _DT[dt],
-                                      _stream())
-        _lib.check(rc, 'svol_gate_fwd')
-        ctx.save_for_backward(x2, pos2, u, gamma, a, mean, rstd, ws)
-        ctx.dims = (B, L, D, H)
-        ctx.sinks = (_claim(gamma, ctx.needs_input_grad[3]), _claim(beta, ctx.needs_input_grad[4]))
-        return y32.view(B, L, D), y.view(B, L, D), ypos.view(B, L, D)
-
-    @staticmethod
-    def backward(ctx, dy32, dy, dypos):
-        x2, pos2, u, gamma, a, mean, rstd, ws = ctx.saved_tensors
-        B, L, D, H = ctx.dims
-        cont = lambda t: None if t is None else t.reshape(B * L, D).contiguous()
-        dy32, dy, dypos = cont(dy32), cont(dy), cont(dypos)
-        dx32 = torch.empty_like(x2)
-        sg, sb = ctx.sinks
-        zb = torch.zeros((B * H * D + 2 * D,), dtype=torch.float32, device=x2.device)  # one memset: du | dgamma | dbeta
-        du = zb[:B * H * D].view(B, H, D)
-        dg = sg.view if sg else zb[B * H * D:B * H * D + D]
-        db = sb.view if sb else zb[B * H * D + D:]
-        ws2 = torch.empty((B * L + B * H,), dtype=torch.float32, device=x2.device)
-        rc = _lib.lib().svol_gate_bwd(_ptr(dy32), _ptr(dy), _ptr(dypos), _ptr(x2), _ptr(pos2), _ptr(u), _ptr(gamma),
-                                      _ptr(a), _ptr(mean), _ptr(rstd), _ptr(ws), _ptr(ws2), _ptr(dx32), _ptr(du),
-                                      _ptr(dg), _ptr(db), B, L, D, H, _DT[pos2.dtype], _stream())
-        _lib.check(rc, 'svol_gate_bwd')
-        return dx32.view(B, L, D), None, du, None if sg else dg, None if sb else db, None
-
-
-def gate(x32, pos, u, gamma, beta, H):
-    return GateFn.apply(x32, pos, u, gamma, beta, H)
-
-
-class CastFn(torch.autograd.Function):
-    """dtype change on the autograd tape (fp32 master parameter / feature -> compute dtype and back)."""
-
-    @staticmethod
-    def forward(ctx, x, dtype):
-        ctx.src = x.dtype
-        return cast(x, dtype)
-
-    @staticmethod
-    def backward(ctx, dy):
-        return cast(dy.contiguous(), ctx.src), None
-
-
-def cast_ag(x, dtype):
-    return x if x.dtype == dtype else CastFn.apply(x, dtype)
-
-
-# ---- the forward -> backward turn: heads, criterion glue (csrc/heads.hip) ------------------------------------------------------------
-FUSED_HEADS = os.environ.get('SVOL_NO_FUSED_HEADS') is None and os.environ.get('SVOL_DETERMINISTIC') is None
-
-
-def heads_fusable(hs, class_embed, bbox_embed):
-    """the one-launch heads take: fp32 decoder states of width D (multiple of 32, <= 512), Linear(D, 2) and a 3-layer MLP(D, D, 4)."""
-    if not FUSED_HEADS or hs.dtype != torch.float32 or not hs.is_cuda:
-        return False
-    D = hs.shape[-1]
-    ls = list(bbox_embed.layers)
-    return (D % 32 == 0 and D <= 512 and len(ls) == 3 and tuple(class_embed.weight.shape) == (2, D) and class_embed.bias is not None
-            and tuple(ls[0].weight.shape) == (D, D) and tuple(ls[1].weight.shape) == (D, D) and tuple(ls[2].weight.shape) == (4, D)
-            and all(l.bias is not None for l in ls) and all(t.dtype == torch.float32 for t in (class_embed.weight, ls[0].weight)))
-
-
-class HeadsFn(torch.autograd.Function):
-    """(pred_logits, pred_boxes) of ALL decoder layers from the stacked states hs [..., D]: class_embed = Linear(D, 2) and
-    bbox_embed = MLP(D, D, 4, 3) -> sigmoid (svanet.py:125-127) in ONE launch, exact fp32; the backward is one launch for dhs and the
-    2- / 4-row weight gradients, the two D x D weight gradients go to the weight-gradient stream."""
-
-    @staticmethod
-    def forward(ctx, hs, Wc, bc, W0, b0, W1, b1, W2, b2):
-        shp = hs.shape
-        D = shp[-1]
-        hs2 = hs.reshape(-1, D)
-        if not hs2.is_contiguous():
-            hs2 = hs2.contiguous()
-        R = hs2.shape[0]
-        dev = hs.device
-        logits = torch.empty((R, 2), dtype=torch.float32, device=dev)
-        boxes = torch.empty((R, 4), dtype=torch.float32, device=dev)
-        hid = torch.empty((2, R, D), dtype=torch.float32, device=dev)
-        rc = _lib.lib().svol_heads_fwd(_ptr(hs2), _ptr(Wc), _ptr(bc), _ptr(W0), _ptr(b0), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(logits),
-                                       _ptr(hid[0]), _ptr(hid[1]), _ptr(boxes), R, D, _stream())
-        _lib.check(rc, 'svol_heads_fwd')
-        ctx.save_for_backward(hs2, hid, boxes, Wc, W0, W1, W2)
-        ctx.shp = shp
-        ni = ctx.needs_input_grad
-        ctx.sinks = tuple(_claim(p_, ni[i + 1]) for i, p_ in enumerate((Wc, bc, W0, b0, W1, b1, W2, b2)))
-        return logits.view(*shp[:-1], 2), boxes.view(*shp[:-1], 4)
-
-    @staticmethod
-    def backward(ctx, dlogits, dboxes):
-        hs2, hid, boxes, Wc, W0, W1, W2 = ctx.saved_tensors
-        R, D = hs2.shape
-        dev = hs2.device
-        dlogits = torch.zeros((R, 2), dtype=torch.float32, device=dev) if dlogits is None else dlogits.reshape(R, 2).float().contiguous()
-        dboxes = torch.zeros((R, 4), dtype=torch.float32, device=dev) if dboxes is None else dboxes.reshape(R, 4).float().contiguous()
-        sWc, sbc, sW0, sb0, sW1, sb1, sW2, sb2 = ctx.sinks
-        g = torch.empty((3, R, D), dtype=torch.float32, device=dev)   # dhs, g_pre0, g_pre1
-        small = None
-        if not (sWc is not None and sbc is not None and sW2 is not None and sb2 is not None):
-            small = torch.zeros((6 * D + 6,), dtype=torch.float32, device=dev)
-        dWc = sWc.view if sWc is not None else small[:2 * D].view(2, D)
-        dbc = sbc.view if sbc is not None else small[6 * D:6 * D + 2]
-        dW2 = sW2.view if sW2 is not None else small[2 * D:6 * D].view(4, D)
-        db2 = sb2.view if sb2 is not None else small[6 * D + 2:]
-        rc = _lib.lib().svol_heads_bwd(_ptr(dlogits), _ptr(dboxes), _ptr(hs2), _ptr(hid[0]), _ptr(hid[1]), _ptr(boxes), _ptr(Wc), _ptr(W0),
-                                       _ptr(W1), _ptr(W2), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(dWc), _ptr(dbc), _ptr(dW2), _ptr(db2),
-                                       R, D, _stream())
-        _lib.check(rc, 'svol_heads_bwd')
-        ni = ctx.needs_input_grad
-        out = [g[0].view(ctx.shp) if ni[0] else None]
-        out += [None if sWc is not None else dWc, None if sbc is not None else dbc]
-        for gp, x, sW, sb, iw in ((g[1], hs2, sW0, sb0, 3), (g[2], hid[0], sW1, sb1, 5)):
-            if sW is not None and sb is not None:
-                gemm_tn_sink(gp, x, out=sW.view, colsum=sb.view)      # off the critical path (weight-gradient stream)
-                out += [None, None]
-            else:
-                buf = torch.zeros((D * D + D,), dtype=torch.float32, device=dev)
-                gemm_tn(gp, x, out=buf[:D * D].view(D, D), colsum=buf[D * D:])
-                dW_, db_ = buf[:D * D].view(D, D), buf[D * D:]
-                if sW is not None:
-                    sW.view.add_(dW_)
-                    dW_ = None
-                if sb is not None:
-                    sb.view.add_(db_)
-                    db_ = None
-                out += [dW_ if ni[iw] else None, db_ if ni[iw + 1] else None]
-        out += [None if sW2 is not None else dW2, None if sb2 is not None else db2]
-        return tuple(out)
-
-
-def heads(hs, class_embed, bbox_embed):
-    ls = bbox_embed.layers
-    return HeadsFn.apply(hs, class_embed.weight, class_embed.bias, ls[0].weight, ls[0].bias, ls[1].weight, ls[1].bias, ls[2].weight, ls[2].bias)
-
-
-class WeightedTotalFn(torch.autograd.Function):
-    """sum(losses * w) over the [layers, 4] loss table (train.py:227-228) as one tiny launch each way."""
-
-    @staticmethod
-    def forward(ctx, losses, w):
-        x = losses.contiguous()
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().svol_weighted_total(_ptr(x), _ptr(w), x.numel(), _ptr(out), _stream()), 'svol_weighted_total')
-        ctx.save_for_backward(w)
-        ctx.shape = losses.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (w,) = ctx.saved_tensors
-        d = dout.float().contiguous()
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=w.device)
-        _lib.check(_lib.lib().svol_weighted_total_bwd(_ptr(w), _ptr(d), w.numel(), _ptr(dx), _stream()), 'svol_weighted_total_bwd')
-        return dx, None
-
-
-class SetCriterionFn(torch.autograd.Function):
-    """All decoder layers' matching + losses in three launches (cost, LSAP, loss); no host sync.
-    logits [NL,B,N,2], boxes [NL,B,N,4] fp32 -> losses [NL,4] = (label, bbox, giou, class_error)."""
-
-    @staticmethod
-    def forward(ctx, logits, boxes, packed, w_bbox, w_giou, w_class, eos_coef):
-        NL = logits.shape[0]
-        rows = logits.shape[1] * logits.shape[2]
-        lg = logits.contiguous().float()
-        bx = boxes.contiguous().float()
-        match = match_all(lg, bx, packed, w_bbox, w_giou, w_class)
-        losses = torch.empty((NL, 4), dtype=torch.float32, device=lg.device)
-        g_label = torch.empty_like(lg)
-        g_bbox = torch.empty_like(bx)
-        g_giou = torch.empty_like(bx)
-        rc = _lib.lib().svol_set_loss(_ptr(lg), _ptr(bx), _ptr(packed.tgt_boxes), _ptr(match), _ptr(losses),
-                                      _ptr(g_label), _ptr(g_bbox), _ptr(g_giou), NL, rows, float(eos_coef),
-                                      _ptr(packed.rebase_vid_off), logits.shape[2], _ptr(packed.status),
-                                      _ptr(packed.box_status), packed.problems_per_layer, _stream())
-        _lib.check(rc, 'svol_set_loss')
-        ctx.save_for_backward(g_label, g_bbox, g_giou)
-        ctx.mark_non_differentiable(match)
-        return losses, match
-
-    @staticmethod
-    def backward(ctx, dl, _dmatch):
-        g_label, g_bbox, g_giou = ctx.saved_tensors
-        dl = dl.float()
-        if FUSED_HEADS and dl.is_contiguous():   # one launch instead of five elementwise ones (csrc/heads.hip)
-            dlog, dbox = torch.empty_like(g_label), torch.empty_like(g_bbox)
-            NL = g_label.shape[0]
-            rc = _lib.lib().svol_set_loss_bwd(_ptr(g_label), _ptr(g_bbox), _ptr(g_giou), _ptr(dl), _ptr(dlog), _ptr(dbox), NL,
-                                              g_label.numel() // (2 * NL), _stream())
-            _lib.check(rc, 'svol_set_loss_bwd')
-            return dlog, dbox, None, None, None, None, None
-        dlog = g_label * dl[:, 0].view(-1, 1, 1, 1)
-        dbox = g_bbox * dl[:, 1].view(-1, 1, 1, 1) + g_giou * dl[:, 2].view(-1, 1, 1, 1)
-        return dlog, dbox, None, None, None, None, None
-
-
-def match_all(lg, bx, packed, w_bbox, w_giou, w_class):
-    """cost blocks + batched LSAP for every problem in `packed`; returns match[R] int32
-    (global target row per prediction row, -1 = unmatched)."""
-    R = lg.shape[0] * lg.shape[1] * lg.shape[2]
-    cost = torch.empty((max(1, packed.cost_numel),), dtype=torch.float32, device=lg.device)
-    match = torch.empty((R,), dtype=torch.int32, device=lg.device)
-    L = _lib.lib()
-    rc = L.svol_match_cost(_ptr(lg), _ptr(bx), _ptr(packed.tgt_boxes), _ptr(packed.pred_off), _ptr(packed.pred_cnt),
-                           _ptr(packed.tgt_off), _ptr(packed.tgt_cnt), _ptr(packed.cost_off), _ptr(cost),
-                           packed.n_problems, float(w_bbox), float(w_giou), float(w_class), _ptr(packed.box_status),
-                           _stream())
-    _lib.check(rc, 'svol_match_cost')
-    rc = L.svol_lsap_batched(_ptr(cost), _ptr(packed.cost_off), _ptr(packed.pred_off), _ptr(packed.pred_cnt),
-                             _ptr(packed.tgt_off), _ptr(packed.tgt_cnt), _ptr(match), _ptr(packed.status),
-                             packed.n_problems, packed.max_dim, _stream())
-    _lib.check(rc, 'svol_lsap_batched')
-    packed.last_cost = cost
-    return match

@@ -28,8 +28,9 @@ from typing import Iterable, List, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops, wgrad   # (none loads the kernel library at import)
+from . import _lib, wgrad   # (none loads the kernel library at import)
 from .ops import _ptr, _stream
+from .params import GradSink
 
 _LATE = ('query_embed', 'input_', 'backbone', 'pos_embed', 'position_embedding')   # first used in forward = last in backward
 _GATE = ('sketch_video_cross_attn',)   # the gate-vector algebra of every layer runs ahead of the layer loop (cross_modal_transformer.py):
@@ -128,8 +129,8 @@ class BucketedGradAllReduce:
             for p in b['params']:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(bi)))
                 # the svol kernels accumulate weight / bias / LayerNorm gradients straight into the bucket view
-                # (svol_amd.ops "gradient sinks"); the hook above still fires for them
-                p._svol_sink = ops.GradSink(p.grad, self, bi)
+                # (svol_amd.params "gradient sinks"); the hook above still fires for them
+                p._svol_sink = GradSink(p.grad, self, bi)
 
     def _make_bucket(self, params):
         # every tensor starts on a 16-byte boundary (the kernels take 16-byte vector accesses on gradients and — FlatAdamW —

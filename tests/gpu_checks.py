@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from oracle import svol_oracle as O
-from svol_amd import ops
+from svol_amd import layers, ops, params
 from svol_amd import synthetic as syn
 from tests.dropout_twin import dropout_keep_numpy   # noqa: F401  (re-export: the twin lives in tests/dropout_twin.py)
 
@@ -150,7 +150,7 @@ def check_gemm_split():
         b = _rnd((N,), torch.float32, 43)
         Wd = W.to(DEV)
         Wd.requires_grad_(False)
-        hl = ops.weights.get_split(Wd, 2 * N, N)
+        hl = params.weights.get_split(Wd, 2 * N, N)
         wv = W[2 * N:]
         hi = wv.to(torch.bfloat16)
         lo = (wv - hi.float()).to(torch.bfloat16)
@@ -553,7 +553,7 @@ def check_gate():
             xd = x.to(DEV).requires_grad_(True)
             ud = u.to(DEV).requires_grad_(True)
             gd, bd = g.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
-            y32, y, ypos = ops.gate(xd, pos.to(DEV), ud, gd, bd, H)
+            y32, y, ypos = layers.gate(xd, pos.to(DEV), ud, gd, bd, H)
             x64, u64 = x.double().requires_grad_(True), u.double().requires_grad_(True)
             g64, b64 = g.double().requires_grad_(True), b.double().requires_grad_(True)
             yr, ypr = _gate_ref(x64, pos.double(), u64, g64, b64, H)
@@ -586,7 +586,7 @@ def check_gate():
             b = 0.1 * _rnd((D,), torch.float32, 54)
             dy32 = _rnd((B, L, D), torch.float32, 55)
             xd, ud = x.to(DEV).requires_grad_(True), u.to(DEV).requires_grad_(True)
-            y32, y, ypos = ops.gate(xd, pos.to(DEV), ud, g.to(DEV), b.to(DEV), H)
+            y32, y, ypos = layers.gate(xd, pos.to(DEV), ud, g.to(DEV), b.to(DEV), H)
             x64, u64 = x.double().requires_grad_(True), u.double().requires_grad_(True)
             yr, _ = _gate_ref(x64, pos.double(), u64, g.double(), b.double(), H)
             # how much the output moves when the gate is switched off: the sensitivity this case exists for
@@ -623,7 +623,7 @@ def check_gate_against_mha():
             sk = _rnd((B, D), torch.float32, 71)
             x, pos = _rnd((B, L, D), torch.float32, 72), _rnd((B, L, D), dt, 73)
             u = layer.gate_vectors(sk.to(DEV))
-            y32, _, _ = ops.gate(x.to(DEV), pos.to(DEV), u, layer.norm1.weight, layer.norm1.bias, H)
+            y32, _, _ = layers.gate(x.to(DEV), pos.to(DEV), u, layer.norm1.weight, layer.norm1.bias, H)
             a_dev = y32.grad_fn.saved_tensors[4].double().cpu().view(B, L)
             W, bb = m.in_proj_weight.detach().double().cpu(), m.in_proj_bias.detach().double().cpu()
             dh = D // H
@@ -800,12 +800,12 @@ def check_heads():
             ce, be = nn.Linear(D, 2), MLP(D, D, 4, 3)
             ce.cuda(), be.cuda()
             hs = torch.randn(*shape, D, device=DEV, requires_grad=True)
-            assert ops.heads_fusable(hs, ce, be)
+            assert layers.heads_fusable(hs, ce, be)
             params = list(ce.parameters()) + list(be.parameters())
             if sinks:
                 red = parallel.BucketedGradAllReduce(params, bucket_bytes=1 << 20)
                 red.zero_grad()
-            lg, bx = ops.heads(hs, ce, be)
+            lg, bx = layers.heads(hs, ce, be)
             pl, pb = torch.randn_like(lg), torch.randn_like(bx)
             ((lg * pl).sum() + (bx * pb).sum()).backward()
             if sinks:
@@ -837,7 +837,7 @@ def check_heads():
     res['heads/set_loss_bwd/dboxes'] = (float((dbox - (gb * dl[:, 1].view(-1, 1, 1, 1) + gg * dl[:, 2].view(-1, 1, 1, 1))).abs().max()), 2e-6)
     x = torch.randn(6, 4, device=DEV, requires_grad=True)
     w = torch.rand(6, 4, device=DEV)
-    t = ops.WeightedTotalFn.apply(x, w)
+    t = layers.WeightedTotalFn.apply(x, w)
     (t * 3.0).backward()
     res['heads/weighted_total'] = (abs(float(t) - float((x.detach().double() * w.double()).sum())), 1e-5)
     res['heads/weighted_total_bwd'] = (float((x.grad - 3.0 * w).abs().max()), 1e-6)
@@ -892,7 +892,7 @@ def check_head_case(name, dtype, sinks=False):
     * outputs (pred_logits / pred_boxes, final and auxiliary layers — the outputs north_star names): ABSOLUTE
       |diff| <= 1e-3 fp32 / 1e-2 bf16 on EVERY case, including the two full-depth cfg2 goldens (6 layers, L = 6272) that are the
       (config, dtype) bench.py times.  Round 2 needed 2e-2 there (measured 1.27e-2): the bf16 rounding of the value-projection
-      WEIGHTS shifted every token coherently; since round 3 those products use split hi + lo weights (ops.SPLIT_V,
+      WEIGHTS shifted every token coherently; since round 3 those products use split hi + lo weights (params.SPLIT_V,
       profiles/round3_bf16_output_error.md).
     * Hungarian assignment: BIT-EXACT against the CPU oracle matcher (scipy restatement) run on the very
       outputs the product produced, every layer; and equal to the golden assignment whenever the outputs

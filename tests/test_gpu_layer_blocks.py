@@ -127,13 +127,13 @@ def make_inputs(c, seed=0):
 def device_run(layer, c, x, cot, keys=('m32', 'm', 'mpos', 'y32', 'y', 'ypos'), reducer=None):
     """video_half -> query_self -> query_cross as CrossModalTransformer.forward composes them; backward with the cotangents named
     in ``keys``.  Returns (outputs, input gradients, parameter gradients), read straight after backward()."""
-    from svol_amd import ops
+    from svol_amd import params
     dt, qdt = c['dtype'], _qdt(c['dtype'])
     if reducer is not None:
         reducer.zero_grad()
     else:
         layer.zero_grad(set_to_none=True)
-    ops.weights.new_epoch()
+    params.weights.new_epoch()
     mem32 = x['mem32'].clone().requires_grad_(True)
     skch = x['skch'].clone().requires_grad_(True)
     out32 = x['out32'].clone().requires_grad_(True)
@@ -311,7 +311,7 @@ def test_layer_blocks_match_fp64_slice_by_slice(name):
 
 @pytest.mark.parametrize('name', ['C', 'A'])
 def test_per_op_path_matches_fp64_and_the_block_forward_bit_for_bit(name):
-    """blocks.ENABLED = False: the per-op Functions (ops.GateFn / AttnLNFn / MLPLNFn) against fp64 at the same bars, and their forward
+    """blocks.ENABLED = False: the per-op Functions (layers.GateFn / AttnLNFn / MLPLNFn) against fp64 at the same bars, and their forward
     outputs bit-identical to the block programs' (blocks.py: the same kernels in the same order)."""
     c, dev_b, _, _ = run_case(name)
     _, dev_p, res, exact = run_case(name, per_op=True)
@@ -350,9 +350,9 @@ def test_last_layer_cotangents_match_fp64():
 
 def _query_half(layer, c, x, m, mpos, cot):
     """query_self -> query_cross on the given video tokens (leaves), cotangents on the query triple only."""
-    from svol_amd import ops
+    from svol_amd import params
     layer.zero_grad(set_to_none=True)
-    ops.weights.new_epoch()
+    params.weights.new_epoch()
     qdt = _qdt(c['dtype'])
     m = m.clone().requires_grad_(True)
     mpos = mpos.clone().requires_grad_(True)

@@ -6,7 +6,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from svol_amd import ops
+from svol_amd import layers, ops
 
 DEV = 'cuda'
 B, H, L, DH, D, F, NQ = 8, 8, 6272, 32, 256, 2048, 100
@@ -157,8 +157,8 @@ if 'gate' in which:
     u = torch.randn(B, H, D, device=DEV) * 0.05
     g, b_ = torch.ones(D, device=DEV), torch.zeros(D, device=DEV)
     x32.requires_grad_(True); u.requires_grad_(True)
-    y32, y, yp = ops.gate(x32, pos, u, g, b_, H)
-    t = timeit(lambda: ops.gate(x32, pos, u, g, b_, H))
+    y32, y, yp = layers.gate(x32, pos, u, g, b_, H)
+    t = timeit(lambda: layers.gate(x32, pos, u, g, b_, H))
     print(f'gate fwd: {t * 1e3:.1f} us')
     dy32, dy, dyp = torch.randn_like(y32), torch.randn_like(y), torch.randn_like(yp)
     def bw():

@@ -7,7 +7,7 @@ import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from svol_amd import ops, synthetic as syn
+from svol_amd import params, synthetic as syn
 from svol_amd.modeling.svanet import build_svanet
 
 dev = torch.device('cuda', 0)
@@ -25,7 +25,7 @@ kbias = torch.zeros(B, L, device=dev)
 def mk():
     o32 = torch.randn(B, N, d, device=dev).requires_grad_(True)
     return (o32, o32.to(qdt), (o32 + qpos).to(qdt))
-ops.weights.new_epoch()
+params.weights.new_epoch()
 def fwd():
     return layer.query_half(mk(), m, mpos, qpos, kbias)
 def fb():

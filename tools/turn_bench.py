@@ -8,7 +8,7 @@ import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from svol_amd import ops, synthetic as syn
+from svol_amd import layers, ops, params, synthetic as syn
 from svol_amd.modeling.loss import build_loss
 from svol_amd.modeling.svanet import build_svanet
 
@@ -19,7 +19,7 @@ torch.manual_seed(1)
 model = build_svanet(args).to(dev).train()
 crit = build_loss(args).to(dev).train()
 tg = syn.synth_targets(B, T, seed=1)
-ops.weights.new_epoch()
+params.weights.new_epoch()
 outs = [torch.randn(B, N, d, device=dev).requires_grad_(True) for _ in range(NL)]
 
 
@@ -31,10 +31,10 @@ def phases():
         torch.cuda._sleep(int(float(os.environ['TURN_AHEAD']) * 2.0e6))   # (~ms at ~2 GHz)
     ev[0].record()
     hs = torch.stack(outs)
-    if ops.heads_fusable(hs, model.class_embed, model.bbox_embed):   # (SVOL_NO_FUSED_HEADS=1: the per-Linear path)
-        lg, bx = ops.heads(hs, model.class_embed, model.bbox_embed)
+    if layers.heads_fusable(hs, model.class_embed, model.bbox_embed):   # (SVOL_NO_FUSED_HEADS=1: the per-Linear path)
+        lg, bx = layers.heads(hs, model.class_embed, model.bbox_embed)
     else:
-        lg = ops.linear(hs, model.class_embed.weight, model.class_embed.bias)
+        lg = layers.linear(hs, model.class_embed.weight, model.class_embed.bias)
         bx = model.bbox_embed(hs, last_act=ops.ACT_SIGMOID)
     ev[1].record()
     out = {'pred_logits': lg[-1], 'pred_boxes': bx[-1], 'aux_outputs': [{'pred_logits': a, 'pred_boxes': b} for a, b in zip(lg[:-1], bx[:-1])],
