@@ -621,6 +621,29 @@ int svol_attn_small_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, 
                         const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                         int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
 
+/* ---- Sketch-ViT classification fine-tuning (preprocess/sketch_vit_finetune.py:79-85,140-143): the loss reads the [CLS] row of each
+ * image only, so the LAST trained block runs for that row alone (csrc/sketch_cls.hip).
+ * svol_attn_cls_fwd: the [CLS] query of HF ViTSelfAttention in that block (sketch_vit_finetune.py:82 through :141's `outputs[:, 0, :]`):
+ *   o [n, H*dh] bf16 = softmax(q k^T * scale) v with ONE query row per image, q [n, H*dh], k / v [n*L, >= H*dh] views (column slices of a
+ *   packed buffer work), lse2 [n, H] fp32 in the log2 units of svol_attn_small_fwd_lse.  bf16 operands, fp32 arithmetic throughout (P is
+ *   never rounded), dh in {32, 64}, 1 <= L <= 256; keys at index >= L are never read.  Pointers 16-byte aligned, leading dimensions
+ *   multiples of 8; SVOL_E_INVALID / SVOL_E_UNSUPPORTED before any launch otherwise. */
+int svol_attn_cls_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2,
+                      int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* svol_attn_cls_bwd: its autograd (loss.backward(), sketch_vit_finetune.py:142): dq [n, H*dh], dk / dv [n*L, H*dh] views (bf16) from q, k,
+ *   v, o, dout [n, H*dh] and lse2.  One wave owns every output of its (image, head): no atomics, bit-reproducible; rows >= n*L are never
+ *   written.  At L = 1 dq = dk = 0 and dv = dout exactly.  Limits and refusals as the forward.  o is checked like the other operands
+ *   but not read: delta = dout . o is formed as sum_j P_j (dout . v_j) in fp32, free of the rounding of the stored o. */
+int svol_attn_cls_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                      const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                      int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* svol_softmax_xent: nn.CrossEntropyLoss() and its gradient (sketch_vit_finetune.py:107,141-142) on fp32 logits [n, C] (leading
+ *   dimension ld), int64 targets [n], 1 <= C <= 1024 (more: SVOL_E_UNSUPPORTED): loss [1] = the mean over rows, dlogits [n, C] (lddl) =
+ *   (softmax - onehot) / n, correct [1] = the number of rows whose argmax is their target.  The sum over rows has a fixed order (same
+ *   bits every run).  A target outside [0, C) is never used as an index: it makes loss and its row of dlogits NaN. */
+int svol_softmax_xent(const float* logits, int64_t ld, const int64_t* targets, float* loss, float* dlogits, int64_t lddl, int32_t* correct,
+                      int64_t n, int64_t C, void* stream);
+
 
 /* ---- composite block programs (round 3: the host off the critical path) ---------------------------------------------
  * One C call enqueues a whole block of a CrossModalTransformerLayer (cross_modal_transformer.py:105-160) — the same kernels,

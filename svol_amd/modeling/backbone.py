@@ -52,6 +52,18 @@ def vit_base_config(**over) -> SimpleNamespace:
     return SimpleNamespace(**a)
 
 
+# transformers 4.x parameter names -> the 5.x names the modules here carry
+HF_RENAMES = (('encoder.layer.', 'layers.'), ('attention.attention.query', 'attention.q_proj'),
+              ('attention.attention.key', 'attention.k_proj'), ('attention.attention.value', 'attention.v_proj'),
+              ('attention.output.dense', 'attention.o_proj'), ('intermediate.dense', 'mlp.fc1'), ('output.dense', 'mlp.fc2'))
+
+
+def hf_rename(k: str) -> str:
+    for a, b in HF_RENAMES:
+        k = k.replace(a, b)
+    return k
+
+
 class _Attention(nn.Module):
     def __init__(self, d):
         super().__init__()
@@ -229,18 +241,13 @@ class ViTExtractor(nn.Module):
 
     def load_hf_state_dict(self, sd):
         """state dict of transformers.ViTModel, 5.x names or the 4.x ``encoder.layer.N.attention.attention.query`` style."""
-        ren = (('encoder.layer.', 'layers.'), ('attention.attention.query', 'attention.q_proj'),
-               ('attention.attention.key', 'attention.k_proj'), ('attention.attention.value', 'attention.v_proj'),
-               ('attention.output.dense', 'attention.o_proj'), ('intermediate.dense', 'mlp.fc1'), ('output.dense', 'mlp.fc2'))
         out = {}
         for k, v in sd.items():
             if k.startswith('vit.'):
                 k = k[4:]
             if k.startswith('pooler.'):
                 continue
-            for a, b in ren:
-                k = k.replace(a, b)
-            out[k] = v
+            out[hf_rename(k)] = v
         self._wcache.clear()
         return self.load_state_dict(out, strict=True)
 
@@ -272,41 +279,58 @@ class ViTExtractor(nn.Module):
     def _forward_train(self, pixel_values, return_pre_norm):
         """autograd through the trained part (module docstring); the frozen prefix runs as in _forward_frozen, without autograd.
         The bf16 copies of the trained weights are cast here, every call; the frozen path's copies of them are dropped."""
-        cfg = self.cfg
-        dt = torch.bfloat16
+        n, d = pixel_values.shape[0], self.cfg.hidden_size
+        x32, L = self._stream_train(pixel_values)
+        for lyr in self.layers[self._first_trained():]:
+            x32 = self._layer_train(lyr, x32, n, L)
+        last, _ = layers.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, torch.bfloat16, True)
+        if return_pre_norm:
+            return last.view(n, L, d), x32.view(n, L, d)
+        return last.view(n, L, d)
+
+    def _stream_train(self, pixel_values):
+        """the fp32 stream in front of the first trained layer -> (x32 [n*L, d], L): the embedding Function when everything trains,
+        else the frozen embeddings and layers without autograd.  Drops the frozen path's bf16 copies of the trained weights."""
         n = pixel_values.shape[0]
-        p, d, H = cfg.patch_size, cfg.hidden_size, cfg.num_attention_heads
-        first = self._first_trained()
         for t in self.parameters():
             if t.requires_grad:
                 self._wcache.pop(id(t), None)
         if self.train_layers is None:
             emb = self.embeddings
             x32 = _ViTEmbedFn.apply(pixel_values, emb.patch_embeddings.projection.weight, emb.patch_embeddings.projection.bias,
-                                    emb.cls_token, emb.position_embeddings, p)
-            L = x32.shape[0] // n
-        else:
-            with torch.no_grad():
-                x32, L = self._embed_frozen(pixel_values)
-                for lyr in self.layers[:first]:
-                    x32 = self._layer_frozen(lyr, x32, n, L)
-        for lyr in self.layers[first:]:
-            a = lyr.attention
-            wqkv, wqkvT = ops.cast_transpose(torch.cat([a.q_proj.weight.detach(), a.k_proj.weight.detach(), a.v_proj.weight.detach()]), dt)
-            woc, woT = ops.cast_transpose(a.o_proj.weight.detach(), dt)
-            y = layers.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, dt, False)
-            x32 = _ViTAttnFn.apply(x32, y, a.q_proj.weight, a.q_proj.bias, a.k_proj.weight, a.k_proj.bias, a.v_proj.weight,
-                                   a.v_proj.bias, a.o_proj.weight, a.o_proj.bias, (wqkv, wqkvT, woc, woT), (n, L, H))
-            y = layers.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
-            m = lyr.mlp
-            w1c, w1T = ops.cast_transpose(m.fc1.weight.detach(), dt)
-            w2c, w2T = ops.cast_transpose(m.fc2.weight.detach(), dt)
-            x32 = layers.MLPLNFn.apply(x32, y, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, None, None, ops.ACT_GELU, None,
-                                    (w1c, w1T, w2c, w2T))
-        last, _ = layers.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, dt, True)
-        if return_pre_norm:
-            return last.view(n, L, d), x32.view(n, L, d)
-        return last.view(n, L, d)
+                                    emb.cls_token, emb.position_embeddings, self.cfg.patch_size)
+            return x32, x32.shape[0] // n
+        with torch.no_grad():
+            x32, L = self._embed_frozen(pixel_values)
+            for lyr in self.layers[:self._first_trained()]:
+                x32 = self._layer_frozen(lyr, x32, n, L)
+        return x32, L
+
+    @staticmethod
+    def _attn_weights(a):
+        """(W_qkv [3d, d], W_qkv^T, W_o, W_o^T) bf16 of a trained layer's attention, cast now"""
+        dt = torch.bfloat16
+        wqkv, wqkvT = ops.cast_transpose(torch.cat([a.q_proj.weight.detach(), a.k_proj.weight.detach(), a.v_proj.weight.detach()]), dt)
+        woc, woT = ops.cast_transpose(a.o_proj.weight.detach(), dt)
+        return wqkv, wqkvT, woc, woT
+
+    def _mlp_train(self, lyr, x32):
+        """x32 + fc2(gelu(fc1(LN_after(x32)))) with autograd, on however many rows x32 has"""
+        dt = torch.bfloat16
+        y = layers.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
+        m = lyr.mlp
+        w1c, w1T = ops.cast_transpose(m.fc1.weight.detach(), dt)
+        w2c, w2T = ops.cast_transpose(m.fc2.weight.detach(), dt)
+        return layers.MLPLNFn.apply(x32, y, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, None, None, ops.ACT_GELU, None,
+                                    (w1c, w1T, w2c, w2T))   # (gamma = None: no norm, the fp32 sum is the output)
+
+    def _layer_train(self, lyr, x32, n, L):
+        """one trained layer on all tokens (module docstring)"""
+        a = lyr.attention
+        y = layers.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, torch.bfloat16, False)
+        x32 = _ViTAttnFn.apply(x32, y, a.q_proj.weight, a.q_proj.bias, a.k_proj.weight, a.k_proj.bias, a.v_proj.weight,
+                               a.v_proj.bias, a.o_proj.weight, a.o_proj.bias, self._attn_weights(a), (n, L, self.cfg.num_attention_heads))
+        return self._mlp_train(lyr, x32)
 
     def _embed_frozen(self, pixel_values):
         """-> (fp32 stream [n*L, d], L)"""

@@ -387,6 +387,38 @@ def attn_small_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
                'svol_attn_small_bwd')
 
 
+def attn_cls_fwd(q, k, v, n, H, L, dh):
+    """one query row per image against all L <= 256 keys (bf16 operands, fp32 arithmetic): q [n, H*dh], k / v 2-D [n*L, >= H*dh]
+    views (column slices allowed) -> (o [n, H*dh] bf16, lse2 [n, H] fp32, log2 units)."""
+    o = torch.empty((n, H * dh), dtype=q.dtype, device=q.device)
+    lse2 = torch.empty((n, H), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().svol_attn_cls_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                            _ptr(lse2), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()), 'svol_attn_cls_fwd')
+    return o, lse2
+
+
+def attn_cls_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
+    """gradients of attn_cls_fwd into dq [n, H*dh] and dk / dv [n*L, H*dh] (2-D bf16 views, column slices allowed)."""
+    _lib.check(_lib.lib().svol_attn_cls_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                            _ptr(do), do.stride(0), _ptr(lse2), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0),
+                                            _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
+               'svol_attn_cls_bwd')
+
+
+def softmax_xent(logits, targets):
+    """nn.CrossEntropyLoss() of fp32 logits [n, C] (a row-strided view is fine) and int64 targets [n] -> (loss [1] fp32 = the mean over
+    rows, dlogits [n, C] = (softmax - onehot) / n, correct [1] int32 = top-1 hits).  C <= 1024."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32 and targets.dtype == torch.int64
+    n, C = logits.shape
+    targets = targets.contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    correct = torch.empty((1,), dtype=torch.int32, device=logits.device)
+    dlogits = torch.empty((n, C), dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.lib().svol_softmax_xent(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(loss), _ptr(dlogits), dlogits.stride(0),
+                                            _ptr(correct), n, C, _stream()), 'svol_softmax_xent')
+    return loss, dlogits, correct
+
+
 def im2col(x, N, H, W, C, kh, kw, stride, pad, dtype, strides=None, ldcols=None):
     """x: image batch addressed by element `strides` (sn, sh, sw, sc) — default NHWC contiguous — -> (cols [N*Ho*Wo, ldcols]
     in `dtype`, Ho, Wo); column order (ky, kx, c), zero padding outside the image and in columns >= kh*kw*C."""

@@ -279,6 +279,17 @@ def synth_vit_state_dict(cfg, seed: int = 1) -> "OrderedDict[str, torch.Tensor]"
     return sd
 
 
+def synth_classifier(cfg, num_labels: int = 19, seed: int = 1) -> "OrderedDict[str, torch.Tensor]":
+    """state dict of ``transformers.ViTForImageClassification`` (``vit.*`` = synth_vit_state_dict, then ``classifier.*``): the model
+    preprocess/sketch_vit_finetune.py:95-98 fine-tunes.  The classifier weight is drawn at 1 / sqrt(d) like the other Linear maps."""
+    sd = OrderedDict(('vit.' + k, v) for k, v in synth_vit_state_dict(cfg, seed).items())
+    r = _rs('vit_classifier', seed)
+    d = cfg.hidden_size
+    sd['classifier.weight'] = torch.from_numpy((r.standard_normal((num_labels, d)) / np.sqrt(d)).astype(np.float32))
+    sd['classifier.bias'] = torch.from_numpy((0.05 * r.standard_normal((num_labels,))).astype(np.float32))
+    return sd
+
+
 def synth_images(n: int, cfg, seed: int = 1) -> torch.Tensor:
     """pixel_values [n, C, H, W] fp32 as the HF feature extractor hands them over (already normalised)."""
     r = _rs('images', seed)

@@ -88,3 +88,23 @@ def load_checkpoint(path, model, optimizer=None, lr_scheduler=None, resume_all: 
             lr_scheduler.load_state_dict(ckpt['lr_scheduler'])
         info['start_iter'] = ckpt['iter'] + 1
     return ckpt, info
+
+
+def save_sketch_vit_checkpoint(path, model, optimizer, epoch: int):
+    """preprocess/sketch_vit_finetune.py:150-158: ``{'model', 'optimizer', 'epoch'}`` with the model under the keys of the script's
+    ``SketchViT`` wrapper (``SketchViTClassifier.reference_state_dict``), so that the script's ``--resume`` (:264-266) loads the file."""
+    ckpt = {'model': OrderedDict((k, v.detach().cpu()) for k, v in model.reference_state_dict().items()),
+            'optimizer': optimizer.state_dict() if optimizer is not None else None, 'epoch': int(epoch)}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(ckpt, path)
+    return path
+
+
+def load_sketch_vit_checkpoint(path, model, optimizer=None, map_location='cpu'):
+    """sketch_vit_finetune.py:264-266 -> the checkpoint; the model takes ``checkpoint['model']`` (wrapper keys: the number of trained
+    layers comes from them), the optimizer its state when one is given and the file holds one."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=True)
+    model.load_reference_state_dict(ckpt['model'])
+    if optimizer is not None and ckpt.get('optimizer') is not None:
+        optimizer.load_state_dict(ckpt['optimizer'])
+    return ckpt
