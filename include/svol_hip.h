@@ -518,7 +518,8 @@ int svol_ingest_resize(const uint8_t* src, int64_t n, int64_t H, int64_t W, int6
 /* ---- ViT-B/16 feature extractor pieces (the Hugging Face ViTModel the reference's ViT backbone calls,
  * lib/modeling/backbone.py:30,48; inference only) ----------------------------------------------------------------
  * svol_patchify: pixel_values [n,C,H,W] fp32 -> out [n*(H/p)*(W/p), C*p*p] (dtype), the im2col of the stride-p patch
- *   convolution in the conv weight's (c, ky, kx) order: the patch embedding is then svol_gemm_nt with W [d, C*p*p]. */
+ *   convolution in the conv weight's (c, ky, kx) order: the patch embedding is then svol_gemm_nt with W [d, C*p*p].
+ *   dtype SVOL_F32, SVOL_BF16 or SVOL_F16 (here and in svol_vit_embed): the fp32 value rounded once. */
 int svol_patchify(const float* pixel_values, void* out, int64_t n, int64_t C, int64_t H, int64_t W, int64_t p, int dtype,
                   void* stream);
 /* tokens[img, 0] = cls + pos[0]; tokens[img, 1+j] = patch_proj[img*P + j] + pos[1+j]  (patch_proj, cls, pos fp32).
@@ -620,6 +621,17 @@ int svol_attn_small_fwd_lse(const void* q, int64_t ldq, const void* k, int64_t l
 int svol_attn_small_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                         const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                         int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* The three entry points above with a second operand type: dtype SVOL_BF16 runs the same kernels and gives the same bits as the entries
+ * without the suffix, dtype SVOL_F16 runs their fp16 instances (v_mfma_f32_32x32x16_f16; P and dS are rounded to fp16 before their
+ * products, o / dq / dk / dv are fp16).  Same argument lists, same limits and refusals otherwise.  (The entries without the suffix keep
+ * returning SVOL_E_UNSUPPORTED for SVOL_F16.)  New symbols only: the ABI version is unchanged. */
+int svol_attn_small_fwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                            int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+int svol_attn_small_fwd_lse_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                                float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+int svol_attn_small_bwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                            const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                            int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
 
 /* ---- Sketch-ViT classification fine-tuning (preprocess/sketch_vit_finetune.py:79-85,140-143): the loss reads the [CLS] row of each
  * image only, so the LAST trained block runs for that row alone (csrc/sketch_cls.hip).
@@ -637,6 +649,13 @@ int svol_attn_cls_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, co
 int svol_attn_cls_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                       const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                       int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* svol_attn_cls_fwd_h16 / svol_attn_cls_bwd_h16: the two entry points above, which also take dtype SVOL_F16 (fp16 operands and outputs, the
+ *   same fp32 arithmetic); with SVOL_BF16 the same kernels and bits as the entries without the suffix, which keep refusing SVOL_F16. */
+int svol_attn_cls_fwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2,
+                          int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+int svol_attn_cls_bwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                          const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                          int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
 /* svol_softmax_xent: nn.CrossEntropyLoss() and its gradient (sketch_vit_finetune.py:107,141-142) on fp32 logits [n, C] (leading
  *   dimension ld), int64 targets [n], 1 <= C <= 1024 (more: SVOL_E_UNSUPPORTED): loss [1] = the mean over rows, dlogits [n, C] (lddl) =
  *   (softmax - onehot) / n, correct [1] = the number of rows whose argmax is their target.  The sum over rows has a fixed order (same

@@ -90,6 +90,14 @@ SIGNATURES = {
     'svol_attn_cls_fwd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _f32, _int, _p],
     'svol_attn_cls_bwd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64,
                           _i64, _f32, _int, _p],
+    # the same five with SVOL_F16 accepted besides SVOL_BF16
+    'svol_attn_small_fwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _f32, _int, _p],
+    'svol_attn_small_fwd_lse_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _f32, _int, _p],
+    'svol_attn_small_bwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64,
+                                _i64, _f32, _int, _p],
+    'svol_attn_cls_fwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _f32, _int, _p],
+    'svol_attn_cls_bwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64,
+                              _i64, _f32, _int, _p],
     'svol_softmax_xent': [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _p],
     'svol_posenc_sine': [_p, _p, _i64, _i64, _i64, _int, _p],
     'svol_attn_ws_bytes': [_i64, _i64, _i64, _i64, _i64],

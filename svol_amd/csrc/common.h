@@ -87,6 +87,8 @@ template <> struct H16<bf16_t> {
     static __device__ __forceinline__ f32x4 mfma16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ v4 read_tr(lds_v4_ptr p) { return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p); }
+    // four fp32 -> four operands (scalar casts: hipcc pairs them into v_cvt_pk_bf16_f32 by itself)
+    static __device__ __forceinline__ v4 cvt4(f32x4 x) { return v4{(bf16_t)x[0], (bf16_t)x[1], (bf16_t)x[2], (bf16_t)x[3]}; }
 };
 template <> struct H16<f16_t> {
     typedef f16x8 v8;
@@ -95,6 +97,8 @@ template <> struct H16<f16_t> {
     static __device__ __forceinline__ f32x4 mfma16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ v4 read_tr(lds_v4_ptr p) { return svol_ds_read_tr16_f16(p); }
+    // (the vector conversion: two v_cvt_pk_f16_f32; scalar casts became 4 x v_cvt_f16_f32 + 2 x v_pack, see cvt_pk_h16)
+    static __device__ __forceinline__ v4 cvt4(f32x4 x) { return __builtin_convertvector(x, f16x4); }
 };
 
 #define SVOL_CHECK_LAUNCH()                                   \

@@ -3,7 +3,7 @@
 // cross-entropy over <= 1024 classes.
 //
 //   svol_attn_cls_fwd   o = softmax(q k^T * scale) v for one query row per image: q [n, H dh], k / v [n L, >= H dh] views, bf16
-//                       operands, every product and sum in fp32 (a VALU kernel: one query has no MFMA shape; P is never rounded).
+//                       (or, through svol_attn_cls_*_h16, fp16) operands, every product and sum in fp32 (a VALU kernel: one query has no MFMA shape; P is never rounded).
 //                       One wave per (image, head), four per workgroup.  Phase 1, lane = key (<= 4 keys per lane, 16-byte loads of
 //                       the K row against q broadcast from LDS): t_j = s_j c, maximum and sum by wave reduction.  Phase 2, lane =
 //                       channel: P from LDS, V rows read coalesced; at dh = 32 the two half-waves take alternate keys.
@@ -28,9 +28,12 @@ constexpr int CLS_WAVES = 4;     // (image, head) pairs of a workgroup
 constexpr int CLS_LMAX = 256;
 constexpr int CLS_KPL = CLS_LMAX / 64;   // keys per lane
 
+// T = bf16_t or f16_t, the operand type.  Every operand is widened to fp32 as it is read and P, dS, delta stay fp32; T is met again only
+// at the stores of o, dq, dk and dv.  No constant here is rounded to T (the -inf of an empty key slot lives in an fp32 register).
+template <typename T>
 struct ClsArgs {
-    const bf16_t *q, *k, *v, *dout;
-    bf16_t *out, *dq, *dk, *dv;
+    const T *q, *k, *v, *dout;
+    T *out, *dq, *dk, *dv;
     float* lse2;         // [n, H]: written by the forward, read by the backward
     int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
     int64_t pairs;       // n * H
@@ -39,12 +42,12 @@ struct ClsArgs {
 };
 
 // sum_c vec[c] * row[c] over DH channels, one fma chain in channel order: the ONE dot product of both kernels
-template <int DH>
-__device__ __forceinline__ float row_dot(const float* vec, const bf16_t* row) {
+template <typename T, int DH>
+__device__ __forceinline__ float row_dot(const float* vec, const T* row) {
     float acc = 0.f;
 #pragma unroll
     for (int c = 0; c < DH / 8; ++c) {
-        const bf16x8 b = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(row + c * 8));
+        const auto b = __builtin_bit_cast(typename H16<T>::v8, *reinterpret_cast<const uint4*>(row + c * 8));
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc = __builtin_fmaf((float)b[e], vec[c * 8 + e], acc);
     }
@@ -52,8 +55,8 @@ __device__ __forceinline__ float row_dot(const float* vec, const bf16_t* row) {
 }
 
 // sum_j w[j] * rows[j][channel of this lane] over j < L (lane = channel; dh = 32: the half-waves take alternate rows)
-template <int DH>
-__device__ __forceinline__ float weighted_rows(const float* w, const bf16_t* rows, int64_t ld, int L, int lane) {
+template <typename T, int DH>
+__device__ __forceinline__ float weighted_rows(const float* w, const T* rows, int64_t ld, int L, int lane) {
     float acc = 0.f;
     if constexpr (DH == 64) {
 #pragma unroll 4
@@ -67,8 +70,8 @@ __device__ __forceinline__ float weighted_rows(const float* w, const bf16_t* row
     return acc;
 }
 
-template <int DH>
-__global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_fwd_kernel(ClsArgs p) {
+template <typename T, int DH>
+__global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_fwd_kernel(ClsArgs<T> p) {
     __shared__ float sQ[CLS_WAVES][64];
     __shared__ float sP[CLS_WAVES][CLS_LMAX];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -76,9 +79,9 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_fwd_kernel(ClsArgs p)
     const bool valid = pair < p.pairs;      // the tail of the last workgroup: its waves only keep the barriers company
     const int64_t img = valid ? pair / p.H : 0;
     const int hh = valid ? (int)(pair % p.H) : 0;
-    const bf16_t* K = p.k + img * p.L * p.ldk + hh * DH;
-    const bf16_t* V = p.v + img * p.L * p.ldv + hh * DH;
-    if (valid && lane < DH) sQ[wave][lane] = (float)p.q[img * p.ldq + hh * DH + lane];
+    const T* K = p.k + img * p.L * p.ldk + hh * DH;
+    const T* V = p.v + img * p.L * p.ldv + hh * DH;
+    if (valid && lane < DH) sQ[wave][lane] = to_f32(p.q[img * p.ldq + hh * DH + lane]);
     __syncthreads();
     float l = 0.f, tm = 0.f;
     if (valid) {
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_fwd_kernel(ClsArgs p)
         for (int i = 0; i < CLS_KPL; ++i) {
             const int j = lane + 64 * i;
             t[i] = -INFINITY;
-            if (j < p.L) t[i] = row_dot<DH>(sQ[wave], K + (int64_t)j * p.ldk) * p.scale_log2e;
+            if (j < p.L) t[i] = row_dot<T, DH>(sQ[wave], K + (int64_t)j * p.ldk) * p.scale_log2e;
             tm = fmaxf(tm, t[i]);
         }
         tm = wave_max(tm);
@@ -103,14 +106,14 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_fwd_kernel(ClsArgs p)
     }
     __syncthreads();
     if (valid) {
-        const float acc = weighted_rows<DH>(sP[wave], V, p.ldv, p.L, lane);
-        if (lane < DH) p.out[img * p.ldo + hh * DH + lane] = (bf16_t)(acc / l);
+        const float acc = weighted_rows<T, DH>(sP[wave], V, p.ldv, p.L, lane);
+        if (lane < DH) p.out[img * p.ldo + hh * DH + lane] = from_f32<T>(acc / l);
         if (lane == 0) p.lse2[pair] = tm + log2f(l);
     }
 }
 
-template <int DH>
-__global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_bwd_kernel(ClsArgs p) {
+template <typename T, int DH>
+__global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_bwd_kernel(ClsArgs<T> p) {
     __shared__ float sQ[CLS_WAVES][64];
     __shared__ float sD[CLS_WAVES][64];
     __shared__ float sS[CLS_WAVES][CLS_LMAX];
@@ -120,11 +123,11 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_bwd_kernel(ClsArgs p)
     const int64_t img = valid ? pair / p.H : 0;
     const int hh = valid ? (int)(pair % p.H) : 0;
     const int64_t row0 = img * p.L;
-    const bf16_t* K = p.k + row0 * p.ldk + hh * DH;
-    const bf16_t* V = p.v + row0 * p.ldv + hh * DH;
+    const T* K = p.k + row0 * p.ldk + hh * DH;
+    const T* V = p.v + row0 * p.ldv + hh * DH;
     if (valid && lane < DH) {
-        sQ[wave][lane] = (float)p.q[img * p.ldq + hh * DH + lane];
-        sD[wave][lane] = (float)p.dout[img * p.lddo + hh * DH + lane];
+        sQ[wave][lane] = to_f32(p.q[img * p.ldq + hh * DH + lane]);
+        sD[wave][lane] = to_f32(p.dout[img * p.lddo + hh * DH + lane]);
     }
     __syncthreads();
     if (valid) {
@@ -136,9 +139,9 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_bwd_kernel(ClsArgs p)
             const int j = lane + 64 * i;
             pj[i] = dp[i] = 0.f;
             if (j < p.L) {
-                const float t = row_dot<DH>(sQ[wave], K + (int64_t)j * p.ldk) * p.scale_log2e;
+                const float t = row_dot<T, DH>(sQ[wave], K + (int64_t)j * p.ldk) * p.scale_log2e;
                 pj[i] = __builtin_amdgcn_exp2f(t - lse);
-                dp[i] = row_dot<DH>(sD[wave], V + (int64_t)j * p.ldv);
+                dp[i] = row_dot<T, DH>(sD[wave], V + (int64_t)j * p.ldv);
             }
             part = __builtin_fmaf(pj[i], dp[i], part);
         }
@@ -150,26 +153,28 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void attn_cls_bwd_kernel(ClsArgs p)
                 const float ds = pj[i] * (dp[i] - delta);
                 sS[wave][j] = ds;
                 const float dsc = ds * p.scale;
-                bf16_t* dk = p.dk + (row0 + j) * p.lddk + hh * DH;
-                bf16_t* dv = p.dv + (row0 + j) * p.lddv + hh * DH;
+                T* dk = p.dk + (row0 + j) * p.lddk + hh * DH;
+                T* dv = p.dv + (row0 + j) * p.lddv + hh * DH;
 #pragma unroll
                 for (int c = 0; c < DH / 8; ++c) {
-                    bf16x8 a, b;
+                    f32x4 a[2], b[2];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        a[e] = (bf16_t)(dsc * sQ[wave][c * 8 + e]);
-                        b[e] = (bf16_t)(pj[i] * sD[wave][c * 8 + e]);
+                        a[e >> 2][e & 3] = dsc * sQ[wave][c * 8 + e];
+                        b[e >> 2][e & 3] = pj[i] * sD[wave][c * 8 + e];
                     }
-                    *reinterpret_cast<bf16x8*>(dk + c * 8) = a;
-                    *reinterpret_cast<bf16x8*>(dv + c * 8) = b;
+                    *reinterpret_cast<typename H16<T>::v8*>(dk + c * 8) =
+                        __builtin_shufflevector(H16<T>::cvt4(a[0]), H16<T>::cvt4(a[1]), 0, 1, 2, 3, 4, 5, 6, 7);
+                    *reinterpret_cast<typename H16<T>::v8*>(dv + c * 8) =
+                        __builtin_shufflevector(H16<T>::cvt4(b[0]), H16<T>::cvt4(b[1]), 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             }
         }
     }
     __syncthreads();
     if (valid) {
-        const float acc = weighted_rows<DH>(sS[wave], K, p.ldk, p.L, lane);
-        if (lane < DH) p.dq[img * p.lddq + hh * DH + lane] = (bf16_t)(acc * p.scale);
+        const float acc = weighted_rows<T, DH>(sS[wave], K, p.ldk, p.L, lane);
+        if (lane < DH) p.dq[img * p.lddq + hh * DH + lane] = from_f32<T>(acc * p.scale);
     }
 }
 
@@ -239,12 +244,13 @@ __global__ __launch_bounds__(64 * XE_WAVES) void softmax_xent_kernel(const float
     }
 }
 
+// h16: the *_h16 entry points, which take SVOL_F16 besides SVOL_BF16 (the entries without the suffix keep refusing it)
 int cls_check(const void* const* ptrs16, int n16, const int64_t* lds, int nld, const float* lse2, int64_t n, int64_t H, int64_t L, int64_t dh,
-              int dtype) {
+              int dtype, bool h16) {
     for (int i = 0; i < n16; ++i)
         if (!ptrs16[i]) return SVOL_E_INVALID;
     if (!lse2 || n <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
-    if (dtype != SVOL_BF16 || (dh != 32 && dh != 64) || L > CLS_LMAX || n > (1ll << 24) || H > 4096) return SVOL_E_UNSUPPORTED;
+    if (!(dtype == SVOL_BF16 || (h16 && dtype == SVOL_F16)) || (dh != 32 && dh != 64) || L > CLS_LMAX || n > (1ll << 24) || H > 4096) return SVOL_E_UNSUPPORTED;
     for (int i = 0; i < nld; ++i)
         if (lds[i] % 8 || lds[i] < H * dh) return SVOL_E_UNSUPPORTED;
     for (int i = 0; i < n16; ++i)
@@ -253,46 +259,84 @@ int cls_check(const void* const* ptrs16, int n16, const int64_t* lds, int nld, c
     return SVOL_OK;
 }
 
+template <typename T>
+int cls_fwd_go(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2, int64_t n,
+               int64_t H, int64_t L, int64_t dh, float scale, void* stream) {
+    ClsArgs<T> p{};
+    p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.out = (T*)o, p.lse2 = lse2;
+    p.ldq = ldq, p.ldk = ldk, p.ldv = ldv, p.ldo = ldo;
+    p.pairs = n * H, p.H = (int)H, p.L = (int)L, p.scale = scale, p.scale_log2e = scale * LOG2E;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((p.pairs + CLS_WAVES - 1) / CLS_WAVES));
+    if (dh == 64) hipLaunchKernelGGL((attn_cls_fwd_kernel<T, 64>), grid, dim3(64 * CLS_WAVES), 0, s, p);
+    else hipLaunchKernelGGL((attn_cls_fwd_kernel<T, 32>), grid, dim3(64 * CLS_WAVES), 0, s, p);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+int cls_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2, int64_t n,
+            int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream, bool h16) {
+    const void* ptrs[] = {q, k, v, o};
+    const int64_t lds[] = {ldq, ldk, ldv, ldo};
+    const int rc = cls_check(ptrs, 4, lds, 4, lse2, n, H, L, dh, dtype, h16);
+    if (rc != SVOL_OK) return rc;
+    if (dtype == SVOL_F16) return cls_fwd_go<f16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n, H, L, dh, scale, stream);
+    return cls_fwd_go<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n, H, L, dh, scale, stream);
+}
+
+template <typename T>
+int cls_bwd_go(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t ldo, const void* dout, int64_t lddo,
+               const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t n, int64_t H, int64_t L,
+               int64_t dh, float scale, void* stream) {
+    ClsArgs<T> p{};
+    p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.dout = (const T*)dout;
+    p.dq = (T*)dq, p.dk = (T*)dk, p.dv = (T*)dv, p.lse2 = const_cast<float*>(lse2);
+    p.ldq = ldq, p.ldk = ldk, p.ldv = ldv, p.ldo = ldo, p.lddo = lddo, p.lddq = lddq, p.lddk = lddk, p.lddv = lddv;
+    p.pairs = n * H, p.H = (int)H, p.L = (int)L, p.scale = scale, p.scale_log2e = scale * LOG2E;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((p.pairs + CLS_WAVES - 1) / CLS_WAVES));
+    if (dh == 64) hipLaunchKernelGGL((attn_cls_bwd_kernel<T, 64>), grid, dim3(64 * CLS_WAVES), 0, s, p);
+    else hipLaunchKernelGGL((attn_cls_bwd_kernel<T, 32>), grid, dim3(64 * CLS_WAVES), 0, s, p);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+int cls_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo, const void* dout,
+            int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t n, int64_t H,
+            int64_t L, int64_t dh, float scale, int dtype, void* stream, bool h16) {
+    const void* ptrs[] = {q, k, v, o, dout, dq, dk, dv};
+    const int64_t lds[] = {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv};
+    const int rc = cls_check(ptrs, 8, lds, 8, lse2, n, H, L, dh, dtype, h16);
+    if (rc != SVOL_OK) return rc;
+    if (dtype == SVOL_F16)
+        return cls_bwd_go<f16_t>(q, ldq, k, ldk, v, ldv, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n, H, L, dh, scale, stream);
+    return cls_bwd_go<bf16_t>(q, ldq, k, ldk, v, ldv, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n, H, L, dh, scale, stream);
+}
+
 }  // namespace
 
 extern "C" {
 
 int svol_attn_cls_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2,
                       int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    const void* ptrs[] = {q, k, v, o};
-    const int64_t lds[] = {ldq, ldk, ldv, ldo};
-    const int rc = cls_check(ptrs, 4, lds, 4, lse2, n, H, L, dh, dtype);
-    if (rc != SVOL_OK) return rc;
-    ClsArgs p{};
-    p.q = (const bf16_t*)q, p.k = (const bf16_t*)k, p.v = (const bf16_t*)v, p.out = (bf16_t*)o, p.lse2 = lse2;
-    p.ldq = ldq, p.ldk = ldk, p.ldv = ldv, p.ldo = ldo;
-    p.pairs = n * H, p.H = (int)H, p.L = (int)L, p.scale = scale, p.scale_log2e = scale * LOG2E;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((p.pairs + CLS_WAVES - 1) / CLS_WAVES));
-    if (dh == 64) hipLaunchKernelGGL(attn_cls_fwd_kernel<64>, grid, dim3(64 * CLS_WAVES), 0, s, p);
-    else hipLaunchKernelGGL(attn_cls_fwd_kernel<32>, grid, dim3(64 * CLS_WAVES), 0, s, p);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
+    return cls_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n, H, L, dh, scale, dtype, stream, false);
 }
 
 int svol_attn_cls_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                       const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                       int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    const void* ptrs[] = {q, k, v, o, dout, dq, dk, dv};
-    const int64_t lds[] = {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv};
-    const int rc = cls_check(ptrs, 8, lds, 8, lse2, n, H, L, dh, dtype);
-    if (rc != SVOL_OK) return rc;
-    ClsArgs p{};
-    p.q = (const bf16_t*)q, p.k = (const bf16_t*)k, p.v = (const bf16_t*)v, p.dout = (const bf16_t*)dout;
-    p.dq = (bf16_t*)dq, p.dk = (bf16_t*)dk, p.dv = (bf16_t*)dv, p.lse2 = const_cast<float*>(lse2);
-    p.ldq = ldq, p.ldk = ldk, p.ldv = ldv, p.ldo = ldo, p.lddo = lddo, p.lddq = lddq, p.lddk = lddk, p.lddv = lddv;
-    p.pairs = n * H, p.H = (int)H, p.L = (int)L, p.scale = scale, p.scale_log2e = scale * LOG2E;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((p.pairs + CLS_WAVES - 1) / CLS_WAVES));
-    if (dh == 64) hipLaunchKernelGGL(attn_cls_bwd_kernel<64>, grid, dim3(64 * CLS_WAVES), 0, s, p);
-    else hipLaunchKernelGGL(attn_cls_bwd_kernel<32>, grid, dim3(64 * CLS_WAVES), 0, s, p);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
+    return cls_bwd(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n, H, L, dh, scale, dtype, stream, false);
+}
+
+int svol_attn_cls_fwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2,
+                          int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    return cls_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n, H, L, dh, scale, dtype, stream, true);
+}
+
+int svol_attn_cls_bwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                          const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                          int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    return cls_bwd(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n, H, L, dh, scale, dtype, stream, true);
 }
 
 int svol_softmax_xent(const float* logits, int64_t ld, const int64_t* targets, float* loss, float* dlogits, int64_t lddl, int32_t* correct,

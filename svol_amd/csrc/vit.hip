@@ -5,7 +5,8 @@
 //                        conv weight's own (c, ky, kx) order) so that the patch embedding is ONE MFMA GEMM
 //   svol_vit_embed       tokens = [cls; patch_proj] + position embeddings, fp32 residual stream + compute-dtype copy
 //   svol_attn_small_fwd  softmax(Q K^T / sqrt(d_h)) V for SHORT sequences (L <= 256: 197 tokens per image), d_h = 32 or
-//                        64, bf16.  One workgroup per (image, head): K and V sit in LDS once (row-major images with
+//                        64, bf16 or fp16 operands (the kernels are templates on the operand type; the fp16 instances sit behind
+//                        the *_h16 entry points).  One workgroup per (image, head): K and V sit in LDS once (row-major images with
 //                        XOR-swizzled 16-byte chunks, V read back through ds_read_b64_tr_b16), a wave owns 32 queries
 //                        at a time with the WHOLE score row of its query in registers (<= 8 accumulator tiles), so the
 //                        softmax is a plain two-pass one — no running maximum, no rescale; swapped products keep the
@@ -62,20 +63,23 @@ __global__ void vit_embed_kernel(const float* __restrict__ proj, const float* __
 }
 
 // ---- short-sequence attention -------------------------------------------------------------------------------------
+// T = bf16_t or f16_t, the operand type (H16<T> of common.h: the MFMA, the transposed LDS read, the packed conversion).  Nothing between
+// the two products is rounded to T but P <= 1 and dS = P (dP - delta), |dS| <= 2 max |dP|; the padded key lanes of the backward's
+// key-stationary phase hold P = exp2(0 - lse2), inf as a bf16 operand from lse2 <= -128 and as an fp16 operand from lse2 <= -16: a B
+// column that only reaches the output column of the same padded key, which is never stored.
+template <typename T>
 struct SmallArgs {
-    const bf16_t *q, *k, *v;
-    bf16_t* o;
+    const T *q, *k, *v;
+    T* o;
     int64_t ldq, ldk, ldv, ldo;
     int H, L, nkb;  // nkb = ceil(L / 32) <= 8
     float scale_log2e;
     float* lse2;    // [n_seq, H, L] log2-sum-exp of the scaled scores (LSE instantiation only)
 };
-typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
-
 // image: row-major, DH bf16 per row (DH*2 bytes = DH/8 chunks of 16 bytes), chunk index XOR-ed with the row
 // 16 bytes from global memory, or zeros (a branch, not a select between the source and a zero local: that select puts the
 // local on the scratch stack and turns every staging load into a flat load)
-__device__ __forceinline__ uint4 ld16_or_zero(const bf16_t* src, bool valid) {
+template <typename T> __device__ __forceinline__ uint4 ld16_or_zero(const T* src, bool valid) {
     uint4 v = make_uint4(0, 0, 0, 0);
     if (valid) v = *reinterpret_cast<const uint4*>(src);
     return v;
@@ -86,8 +90,39 @@ template <int DH> __device__ __forceinline__ int img_off(int row, int ch) {
     return row * (DH * 2) + (((ch ^ (row >> (DH == 32 ? 2 : 0))) & (CPR - 1)) << 4);
 }
 
-template <int DH, bool LSE>
-__global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
+template <typename T> __device__ __forceinline__ typename H16<T>::v8 as_v8(const uint4& x) { return __builtin_bit_cast(typename H16<T>::v8, x); }
+
+// A operand [row = column db*32 + (lane & 31) of the image][k = image rows r0 + 8(j>>2) + 4h + (j&3)]: per 16-lane group, lane 4q+pp
+// supplies the address of image row q (of 4), columns 4pp..4pp+3 of its 16-column group
+template <typename T, int DH> __device__ __forceinline__ typename H16<T>::v8 tr_frag(const char* img, int r0, int db, int lane) {
+    typedef typename H16<T>::lds_v4_ptr lds_ptr;
+    const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, pp = i16 & 3, hb = g >> 1;
+    const int col = db * 32 + 16 * (g & 1) + 4 * pp;
+    const int r1 = r0 + 4 * hb + q4;
+    const auto lo = H16<T>::read_tr((lds_ptr)(img + img_off<DH>(r1, col >> 3) + (col & 7) * 2));
+    const auto hi = H16<T>::read_tr((lds_ptr)(img + img_off<DH>(r1 + 8, col >> 3) + (col & 7) * 2));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// registers 8s .. 8s + 7 of an accumulator as a B fragment
+template <typename T> __device__ __forceinline__ typename H16<T>::v8 acc_frag(const f32x16& x, int s) {
+    const auto lo = H16<T>::cvt4(f32x4{x[8 * s], x[8 * s + 1], x[8 * s + 2], x[8 * s + 3]});
+    const auto hi = H16<T>::cvt4(f32x4{x[8 * s + 4], x[8 * s + 5], x[8 * s + 6], x[8 * s + 7]});
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// rows of a [*, DH] output from an accumulator with the row on the lane and the columns in the registers
+template <typename T, int DB> __device__ __forceinline__ void store_rows(T* out, const f32x16 (&acc)[DB], float mul, int h) {
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<typename H16<T>::v4*>(out + db * 32 + 8 * g + 4 * h) =
+                H16<T>::cvt4(f32x4{acc[db][4 * g] * mul, acc[db][4 * g + 1] * mul, acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul});
+}
+
+template <typename T, int DH, bool LSE>
+__global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs<T> p) {
     constexpr int CPR = DH / 8, KS = DH / 16, DB = DH / 32;
     constexpr int LMAX = 256;
     __shared__ __attribute__((aligned(16))) char smem[2 * LMAX * DH * 2];
@@ -96,9 +131,9 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int seq = blockIdx.y, hh = blockIdx.x;
-    const bf16_t* Q = p.q + (int64_t)seq * p.L * p.ldq + hh * DH;
-    const bf16_t* K = p.k + (int64_t)seq * p.L * p.ldk + hh * DH;
-    const bf16_t* V = p.v + (int64_t)seq * p.L * p.ldv + hh * DH;
+    const T* Q = p.q + (int64_t)seq * p.L * p.ldq + hh * DH;
+    const T* K = p.k + (int64_t)seq * p.L * p.ldk + hh * DH;
+    const T* V = p.v + (int64_t)seq * p.L * p.ldv + hh * DH;
     const int Lp = p.nkb * 32;
     // stage K and V (zero rows past L)
     for (int c = tid; c < Lp * CPR; c += 256) {
@@ -125,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     const uint4 kf = *reinterpret_cast<const uint4*>(sK + img_off<DH>(kb * 32 + r, ks * 2 + h));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
+                    acc = H16<T>::mfma32(as_v8<T>(kf), as_v8<T>(qf[ks]), acc);
                 }
                 S[kb] = acc;
             }
@@ -168,38 +203,16 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
             if (kb < p.nkb) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    bf16x8 pb;
+                    const auto pb = acc_frag<T>(S[kb], s);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) pb[j] = (bf16_t)S[kb][8 * s + j];
-#pragma unroll
-                    for (int db = 0; db < DB; ++db) {
-                        // transposed fragment of V: lane (r -> column d = db*32 + r); per 16-lane group, lane 4q+pp supplies
-                        // the address of key row q (of 4), columns 4pp..4pp+3 of its 16-column group
-                        const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, pp = i16 & 3, hb = g >> 1;
-                        const int col = db * 32 + 16 * (g & 1) + 4 * pp;  // first of 4 columns this lane addresses
-                        const int r1 = kb * 32 + 16 * s + 4 * hb + q4;
-                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (lds_bf16x4_ptr)(sV + img_off<DH>(r1, col >> 3) + (col & 7) * 2));
-                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (lds_bf16x4_ptr)(sV + img_off<DH>(r1 + 8, col >> 3) + (col & 7) * 2));
-                        const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        O[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb, O[db], 0, 0, 0);
-                    }
+                    for (int db = 0; db < DB; ++db)   // transposed fragment of V: lane (r -> column d = db*32 + r)
+                        O[db] = H16<T>::mfma32(tr_frag<T, DH>(sV, kb * 32 + 16 * s, db, lane), pb, O[db]);
                 }
             }
         }
         if (qvalid) {
             const float inv = 1.f / l;
-            bf16_t* out = p.o + ((int64_t)seq * p.L + qrow) * p.ldo + hh * DH;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bf16x4 v4;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(O[db][4 * g + e] * inv);
-                    *reinterpret_cast<bf16x4*>(out + db * 32 + 8 * g + 4 * h) = v4;
-                }
+            store_rows<T, DB>(p.o + ((int64_t)seq * p.L + qrow) * p.ldo + hh * DH, O, inv, h);
             // lse2 = log2 sum_j exp2(s_j * scale_log2e) = m * scale_log2e + log2(l): P = exp2(s * scale_log2e - lse2)
             if constexpr (LSE)
                 if (h == 0) p.lse2[((int64_t)seq * p.H + hh) * p.L + qrow] = -mc + log2f(l);
@@ -219,10 +232,11 @@ __global__ __launch_bounds__(256, 2) void attn_small_kernel(SmallArgs p) {
 //                     dQ^T += K^T dS^T
 // Outputs are stored like the forward's O (lane = row, 4 consecutive columns per store); rows >= L are never written, padded
 // keys and queries get P = 0.
+template <typename T>
 struct SmallBwdArgs {
-    const bf16_t *q, *k, *v, *o, *dout;
+    const T *q, *k, *v, *o, *dout;
     const float* lse2;
-    bf16_t *dq, *dk, *dv;
+    T *dq, *dk, *dv;
     int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
     int H, L, nkb;
     float scale, scale_log2e;
@@ -232,39 +246,8 @@ template <int DH> __device__ __forceinline__ uint4 row_frag(const char* img, int
     return *reinterpret_cast<const uint4*>(img + img_off<DH>(row, ch));
 }
 
-// A operand [row = column db*32 + (lane & 31) of the image][k = image rows r0 + 8(j>>2) + 4h + (j&3)], the transposed read
-// of the forward's V fragment
-template <int DH> __device__ __forceinline__ bf16x8 tr_frag(const char* img, int r0, int db, int lane) {
-    const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, pp = i16 & 3, hb = g >> 1;
-    const int col = db * 32 + 16 * (g & 1) + 4 * pp;
-    const int r1 = r0 + 4 * hb + q4;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(img + img_off<DH>(r1, col >> 3) + (col & 7) * 2));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(img + img_off<DH>(r1 + 8, col >> 3) + (col & 7) * 2));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& x, int s) {
-    bf16x8 b;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (bf16_t)x[8 * s + j];
-    return b;
-}
-
-// rows of a [*, DH] bf16 output from an accumulator with the row on the lane and the columns in the registers
-template <int DB> __device__ __forceinline__ void store_rows(bf16_t* out, const f32x16 (&acc)[DB], float mul, int h) {
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            bf16x4 v4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(acc[db][4 * g + e] * mul);
-            *reinterpret_cast<bf16x4*>(out + db * 32 + 8 * g + 4 * h) = v4;
-        }
-}
-
-template <int DH>
-__global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) {
+template <typename T, int DH>
+__device__ __forceinline__ void attn_small_bwd_body(const SmallBwdArgs<T>& p) {
     constexpr int CPR = DH / 8, KS = DH / 16, DB = DH / 32;
     constexpr int LMAX = 256, IMG = LMAX * DH * 2;
     __shared__ __attribute__((aligned(16))) char smem[4 * IMG];
@@ -278,11 +261,11 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
     const int r = lane & 31, h = lane >> 5;
     const int seq = blockIdx.y, hh = blockIdx.x;
     const int64_t row0 = (int64_t)seq * p.L;
-    const bf16_t* Q = p.q + row0 * p.ldq + hh * DH;
-    const bf16_t* K = p.k + row0 * p.ldk + hh * DH;
-    const bf16_t* V = p.v + row0 * p.ldv + hh * DH;
-    const bf16_t* O = p.o + row0 * p.ldo + hh * DH;
-    const bf16_t* dO = p.dout + row0 * p.lddo + hh * DH;
+    const T* Q = p.q + row0 * p.ldq + hh * DH;
+    const T* K = p.k + row0 * p.ldk + hh * DH;
+    const T* V = p.v + row0 * p.ldv + hh * DH;
+    const T* O = p.o + row0 * p.ldo + hh * DH;
+    const T* dO = p.dout + row0 * p.lddo + hh * DH;
     const float* lse = p.lse2 + ((int64_t)seq * p.H + hh) * p.L;
     const int Lp = p.nkb * 32;
     // this wave's O rows (block `wave`: nkb <= 8 waves have one) as MFMA B fragments, in flight while the images are staged
@@ -315,7 +298,7 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const uint4 da = row_frag<DH>(sD, orow, ks * 2 + h);
-            D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, da), __builtin_bit_cast(bf16x8, ob[ks]), D, 0, 0, 0);
+            D = H16<T>::mfma32(as_v8<T>(da), as_v8<T>(ob[ks]), D);
         }
         const int idx = 4 * (r >> 3) + (r & 3);
         float dl = 0.f;
@@ -348,8 +331,8 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
             for (int ks = 0; ks < KS; ++ks) {
                 const uint4 qa = row_frag<DH>(sQ, qb * 32 + r, ks * 2 + h);
                 const uint4 da = row_frag<DH>(sD, qb * 32 + r, ks * 2 + h);
-                S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa), __builtin_bit_cast(bf16x8, kf[ks]), S, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, da), __builtin_bit_cast(bf16x8, vf[ks]), dP, 0, 0, 0);
+                S = H16<T>::mfma32(as_v8<T>(qa), as_v8<T>(kf[ks]), S);
+                dP = H16<T>::mfma32(as_v8<T>(da), as_v8<T>(vf[ks]), dP);
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -366,18 +349,18 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
             // dV^T[d][key] += dO^T[d][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const bf16x8 pb = acc_frag(S, s), sb = acc_frag(dP, s);
+                const auto pb = acc_frag<T>(S, s), sb = acc_frag<T>(dP, s);
 #pragma unroll
                 for (int db = 0; db < DB; ++db) {
-                    dVt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sD, qb * 32 + 16 * s, db, lane), pb, dVt[db], 0, 0, 0);
-                    dKt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sQ, qb * 32 + 16 * s, db, lane), sb, dKt[db], 0, 0, 0);
+                    dVt[db] = H16<T>::mfma32(tr_frag<T, DH>(sD, qb * 32 + 16 * s, db, lane), pb, dVt[db]);
+                    dKt[db] = H16<T>::mfma32(tr_frag<T, DH>(sQ, qb * 32 + 16 * s, db, lane), sb, dKt[db]);
                 }
             }
         }
         const int key = kb * 32 + r;
         if (key < p.L) {
-            store_rows<DB>(p.dv + (row0 + key) * p.lddv + hh * DH, dVt, 1.f, h);
-            store_rows<DB>(p.dk + (row0 + key) * p.lddk + hh * DH, dKt, p.scale, h);
+            store_rows<T, DB>(p.dv + (row0 + key) * p.lddv + hh * DH, dVt, 1.f, h);
+            store_rows<T, DB>(p.dk + (row0 + key) * p.lddk + hh * DH, dKt, p.scale, h);
         }
     }
     // ---- query-stationary: dQ of this wave's 32 queries
@@ -404,8 +387,8 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
             for (int ks = 0; ks < KS; ++ks) {
                 const uint4 ka = row_frag<DH>(sK, kb * 32 + r, ks * 2 + h);
                 const uint4 va = row_frag<DH>(sV, kb * 32 + r, ks * 2 + h);
-                S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ka), __builtin_bit_cast(bf16x8, qf[ks]), S, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, va), __builtin_bit_cast(bf16x8, df[ks]), dP, 0, 0, 0);
+                S = H16<T>::mfma32(as_v8<T>(ka), as_v8<T>(qf[ks]), S);
+                dP = H16<T>::mfma32(as_v8<T>(va), as_v8<T>(df[ks]), dP);
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -416,35 +399,84 @@ __global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs p) 
             // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const bf16x8 sb = acc_frag(dP, s);
+                const auto sb = acc_frag<T>(dP, s);
 #pragma unroll
                 for (int db = 0; db < DB; ++db)
-                    dQt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<DH>(sK, kb * 32 + 16 * s, db, lane), sb, dQt[db], 0, 0, 0);
+                    dQt[db] = H16<T>::mfma32(tr_frag<T, DH>(sK, kb * 32 + 16 * s, db, lane), sb, dQt[db]);
             }
         }
-        if (qrow < p.L) store_rows<DB>(p.dq + (row0 + qrow) * p.lddq + hh * DH, dQt, p.scale, h);
+        if (qrow < p.L) store_rows<T, DB>(p.dq + (row0 + qrow) * p.lddq + hh * DH, dQt, p.scale, h);
     }
 }
 
+// the two instances of the body as kernels.  The fp16 one carries a name of its own: tests/test_vit_train_cli.py counts the kernels called
+// attn_small_bwd_kernel in this file's code object (d_h = 32 and 64) and holds every kernel here to no scratch and no spill.
+template <int DH>
+__global__ __launch_bounds__(512, 1) void attn_small_bwd_kernel(SmallBwdArgs<bf16_t> p) { attn_small_bwd_body<bf16_t, DH>(p); }
+template <int DH>
+__global__ __launch_bounds__(512, 1) void attn_small_bwd_f16_kernel(SmallBwdArgs<f16_t> p) { attn_small_bwd_body<f16_t, DH>(p); }
+
 }  // namespace
 
-static int attn_small_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
-                             float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    if (!q || !k || !v || !o || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
-    if (dtype != SVOL_BF16 || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(o) & 7))
-        return SVOL_E_UNSUPPORTED;
-    SmallArgs p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo, (int)H, (int)L,
-                (int)((L + 31) / 32), scale * LOG2E, lse2};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+template <typename T>
+static void attn_small_fwd_go(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                              float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, hipStream_t s) {
+    SmallArgs<T> p{(const T*)q, (const T*)k, (const T*)v, (T*)o, ldq, ldk, ldv, ldo, (int)H, (int)L, (int)((L + 31) / 32), scale * LOG2E, lse2};
     const dim3 grid((unsigned)H, (unsigned)n_seq);
     if (lse2) {
-        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<64, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((attn_small_kernel<32, true>), grid, dim3(256), 0, s, p);
+        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<T, 64, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((attn_small_kernel<T, 32, true>), grid, dim3(256), 0, s, p);
     } else {
-        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<64, false>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((attn_small_kernel<32, false>), grid, dim3(256), 0, s, p);
+        if (dh == 64) hipLaunchKernelGGL((attn_small_kernel<T, 64, false>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((attn_small_kernel<T, 32, false>), grid, dim3(256), 0, s, p);
     }
+}
+
+// h16: the *_h16 entry points, which take SVOL_F16 besides SVOL_BF16 (the entries without the suffix keep refusing it)
+static int attn_small_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                             float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream, bool h16) {
+    if (!q || !k || !v || !o || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
+    if (!(dtype == SVOL_BF16 || (h16 && dtype == SVOL_F16)) || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(o) & 7))
+        return SVOL_E_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == SVOL_F16) attn_small_fwd_go<f16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, s);
+    else attn_small_fwd_go<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, s);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+static void launch_small_bwd(const SmallBwdArgs<bf16_t>& p, int64_t dh, dim3 grid, hipStream_t s) {
+    if (dh == 64) hipLaunchKernelGGL(attn_small_bwd_kernel<64>, grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL(attn_small_bwd_kernel<32>, grid, dim3(512), 0, s, p);
+}
+static void launch_small_bwd(const SmallBwdArgs<f16_t>& p, int64_t dh, dim3 grid, hipStream_t s) {
+    if (dh == 64) hipLaunchKernelGGL(attn_small_bwd_f16_kernel<64>, grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL(attn_small_bwd_f16_kernel<32>, grid, dim3(512), 0, s, p);
+}
+
+template <typename T>
+static void attn_small_bwd_go(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                              const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                              int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, hipStream_t s) {
+    SmallBwdArgs<T> p{(const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dout, lse2, (T*)dq, (T*)dk, (T*)dv,
+                      ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, (int)H, (int)L, (int)((L + 31) / 32), scale, scale * LOG2E};
+    launch_small_bwd(p, dh, dim3((unsigned)H, (unsigned)n_seq), s);
+}
+
+static int attn_small_bwd_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                                 const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                                 int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream, bool h16) {
+    if (!q || !k || !v || !o || !dout || !lse2 || !dq || !dk || !dv || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
+    if (!(dtype == SVOL_BF16 || (h16 && dtype == SVOL_F16)) || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
+        !aligned16(dout) || (reinterpret_cast<uintptr_t>(lse2) & 3))
+        return SVOL_E_UNSUPPORTED;
+    if (lddq % 4 || lddk % 4 || lddv % 4 || ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 7))
+        return SVOL_E_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == SVOL_F16) attn_small_bwd_go<f16_t>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n_seq, H, L, dh, scale, s);
+    else attn_small_bwd_go<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n_seq, H, L, dh, scale, s);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
@@ -461,6 +493,7 @@ int svol_patchify(const float* pixel_values, void* out, int64_t n, int64_t C, in
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == SVOL_BF16) hipLaunchKernelGGL(patchify_kernel<bf16_t>, grid, dim3(256), 0, s, pixel_values, (bf16_t*)out, (int)n, (int)C, (int)H, (int)W, (int)p);
+    else if (dtype == SVOL_F16) hipLaunchKernelGGL(patchify_kernel<f16_t>, grid, dim3(256), 0, s, pixel_values, (f16_t*)out, (int)n, (int)C, (int)H, (int)W, (int)p);
     else if (dtype == SVOL_F32) hipLaunchKernelGGL(patchify_kernel<float>, grid, dim3(256), 0, s, pixel_values, (float*)out, (int)n, (int)C, (int)H, (int)W, (int)p);
     else return SVOL_E_INVALID;
     SVOL_CHECK_LAUNCH();
@@ -475,6 +508,7 @@ int svol_vit_embed(const float* patch_proj, const float* cls_token, const float*
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == SVOL_BF16) hipLaunchKernelGGL(vit_embed_kernel<bf16_t>, grid, dim3(256), 0, s, patch_proj, cls_token, pos_embed, x32, (bf16_t*)x, n, (int)P, (int)D);
+    else if (dtype == SVOL_F16) hipLaunchKernelGGL(vit_embed_kernel<f16_t>, grid, dim3(256), 0, s, patch_proj, cls_token, pos_embed, x32, (f16_t*)x, n, (int)P, (int)D);
     else if (dtype == SVOL_F32) hipLaunchKernelGGL(vit_embed_kernel<float>, grid, dim3(256), 0, s, patch_proj, cls_token, pos_embed, x32, (float*)x, n, (int)P, (int)D);
     else return SVOL_E_INVALID;
     SVOL_CHECK_LAUNCH();
@@ -484,34 +518,38 @@ int svol_vit_embed(const float* patch_proj, const float* cls_token, const float*
 
 int svol_attn_small_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                         int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, n_seq, H, L, dh, scale, dtype, stream);
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, n_seq, H, L, dh, scale, dtype, stream, false);
 }
 
 int svol_attn_small_fwd_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                             float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
     if (!lse2) return SVOL_E_INVALID;
-    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, dtype, stream);
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, dtype, stream, false);
 }
 
 int svol_attn_small_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                         const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                         int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
-    if (!q || !k || !v || !o || !dout || !lse2 || !dq || !dk || !dv || n_seq <= 0 || H <= 0 || L <= 0) return SVOL_E_INVALID;
-    if (dtype != SVOL_BF16 || (dh != 32 && dh != 64) || L > 256 || n_seq > 65535) return SVOL_E_UNSUPPORTED;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
-        !aligned16(dout) || (reinterpret_cast<uintptr_t>(lse2) & 3))
-        return SVOL_E_UNSUPPORTED;
-    if (lddq % 4 || lddk % 4 || lddv % 4 || ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 7))
-        return SVOL_E_UNSUPPORTED;
-    SmallBwdArgs p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse2,
-                   (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, (int)H, (int)L,
-                   (int)((L + 31) / 32), scale, scale * LOG2E};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)H, (unsigned)n_seq);
-    if (dh == 64) hipLaunchKernelGGL(attn_small_bwd_kernel<64>, grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL(attn_small_bwd_kernel<32>, grid, dim3(512), 0, s, p);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
+    return attn_small_bwd_launch(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n_seq, H, L, dh, scale, dtype,
+                                 stream, false);
+}
+
+int svol_attn_small_fwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                            int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, n_seq, H, L, dh, scale, dtype, stream, true);
+}
+
+int svol_attn_small_fwd_lse_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                                float* lse2, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    if (!lse2) return SVOL_E_INVALID;
+    return attn_small_launch(q, ldq, k, ldk, v, ldv, o, ldo, lse2, n_seq, H, L, dh, scale, dtype, stream, true);
+}
+
+int svol_attn_small_bwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                            const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                            int64_t lddv, int64_t n_seq, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream) {
+    return attn_small_bwd_launch(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse2, dq, lddq, dk, lddk, dv, lddv, n_seq, H, L, dh, scale, dtype,
+                                 stream, true);
 }
 
 }  // extern "C"

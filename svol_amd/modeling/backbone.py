@@ -12,8 +12,12 @@ add_pooling_layer=False)`` (5.x naming: ``embeddings.patch_embeddings.projection
     12 x { LN -> q|k|v GEMMs -> short-sequence attention (197 tokens, 12 heads, d_h = 64) -> out-proj GEMM + fp32 residual
            -> LN -> fc1 GEMM + erf-GELU -> fc2 GEMM + fp32 residual } -> LN
 
-bf16 MFMA operands, fp32 residual stream, inference only (the extractor is frozen in the reference: its features
-are normally pre-extracted, preprocess/sketch_vit_feature_extractor.py).  ``ViTBackbone.forward`` returns what the head
+16-bit MFMA operands — ``compute_dtype='bf16'`` (the default) or ``'fp16'``, the reference's own mixed precision (apex amp) —, fp32
+residual stream, frozen by default (the extractor is frozen in the reference: its features are normally pre-extracted,
+preprocess/sketch_vit_feature_extractor.py).  The 16-bit stores are the patch rows, the LayerNorm outputs, q / k / v, the attention
+output and gelu(fc1); the weights are cast to the same type.  fp16 rounds 8 x finer than bf16 and holds 65504 at most: the synthetic
+weights of the tests stay far inside it, the activation ranges under the pretrained in21k weights have not been measured.  ``'fp32'``
+raises: the short-sequence attention kernels have no fp32 form.  ``ViTBackbone.forward`` returns what the head
 consumes at BASELINE configs[3]: the sketch's [CLS] state [B,1,768] and ALL 196 patch tokens of every frame
 [B, T*196, 768].
 LayerNorm uses the kernels' eps = 1e-5 where HF uses 1e-12: a relative change of 5e-6 at unit variance, three orders
@@ -24,13 +28,13 @@ of build_model(args) to AdamW) or fine-tunes (preprocess/sketch_vit_finetune.py:
 K layers and the final LayerNorm, the embeddings and the first 12 - K layers stay frozen and run without autograd).  Same kernels
 and the same forward bits as the frozen path, one autograd Function per piece:
 
-    _ViTEmbedFn   patchify + patch GEMM + [CLS] / position embeddings; backward dW, db = gemm_tn over the saved bf16 patch rows,
+    _ViTEmbedFn   patchify + patch GEMM + [CLS] / position embeddings; backward dW, db = gemm_tn over the saved 16-bit patch rows,
                   dpos = colsum of the stream gradient viewed [n, (P+1)*d], dcls = its first row
     per layer     LNStreamFn(layernorm_before) -> _ViTAttnFn (q|k|v GEMMs, svol_attn_small_fwd_lse, out-proj + fp32 residual;
                   backward svol_attn_small_bwd into one packed dQKV, dx = dQKV [W_q; W_k; W_v] in one NT GEMM)
                   -> LNStreamFn(layernorm_after) -> MLPLNFn(gamma=None, GELU)
     final norm    LNStreamFn
-The trainable path casts its own bf16 weights at the start of every training forward: params.weights is refreshed by the head's
+The trainable path casts its own 16-bit weights at the start of every training forward: params.weights is refreshed by the head's
 forward, which runs AFTER the backbone, and fused AdamW on ROCm does not bump ``_version``.
 """
 from __future__ import annotations
@@ -101,13 +105,16 @@ class _Embeddings(nn.Module):
         self.patch_embeddings = _PatchEmbeddings(cfg)
 
 
-def _patch_rows(pixel_values, p):
-    """[n, C, H, W] fp32 -> (bf16 patch rows [n*P, C*p*p], P)."""
+_DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16}
+
+
+def _patch_rows(pixel_values, p, dt=torch.bfloat16):
+    """[n, C, H, W] fp32 -> (patch rows [n*P, C*p*p] of dtype dt, P)."""
     n, C, Hh, Ww = pixel_values.shape
     P = (Hh // p) * (Ww // p)
     pix = pixel_values.float().contiguous()
-    patches = torch.empty((n * P, C * p * p), dtype=torch.bfloat16, device=pix.device)
-    _lib.check(_lib.lib().svol_patchify(_ptr(pix), _ptr(patches), n, C, Hh, Ww, p, _DT[torch.bfloat16], _stream()), 'svol_patchify')
+    patches = torch.empty((n * P, C * p * p), dtype=dt, device=pix.device)
+    _lib.check(_lib.lib().svol_patchify(_ptr(pix), _ptr(patches), n, C, Hh, Ww, p, _DT[dt], _stream()), 'svol_patchify')
     return patches, P
 
 
@@ -122,11 +129,11 @@ class _ViTEmbedFn(torch.autograd.Function):
     """patchify -> patch GEMM (+ bias, fp32 out) -> [CLS] + position embeddings: the fp32 stream [n*(P+1), d].  No pixel gradient."""
 
     @staticmethod
-    def forward(ctx, pixel_values, W, b, cls, pos, p):
+    def forward(ctx, pixel_values, W, b, cls, pos, p, dt=torch.bfloat16):
         n = pixel_values.shape[0]
         d = W.shape[0]
-        patches, P = _patch_rows(pixel_values, p)
-        Wc = ops.cast(W.detach().reshape(d, -1).contiguous(), torch.bfloat16)
+        patches, P = _patch_rows(pixel_values, p, dt)
+        Wc = ops.cast(W.detach().reshape(d, -1).contiguous(), dt)
         proj = ops.gemm_nt(patches, Wc, b, out_f32=True)
         x32 = _embed(proj, cls, pos, n, P, d)
         ctx.save_for_backward(patches)
@@ -144,7 +151,7 @@ class _ViTEmbedFn(torch.autograd.Function):
         dx32 = dx32 if dx32.is_contiguous() else dx32.contiguous()
         dW = db = dcls = dpos = None
         if nig[1] or nig[2]:
-            dproj = ops.cast(dx32.view(n, P + 1, d)[:, 1:].reshape(n * P, d), torch.bfloat16)
+            dproj = ops.cast(dx32.view(n, P + 1, d)[:, 1:].reshape(n * P, d), patches.dtype)
             grads = params.GradGroup(((sW, (d, patches.shape[1])), (sb, (d,))), dproj.device)
             grads.tn(dproj, patches, 0, 1)
             dW, db = grads.finish()
@@ -160,12 +167,13 @@ class _ViTEmbedFn(torch.autograd.Function):
                 sp.view.view(-1).add_(g)
             elif nig[4]:
                 dpos = g.view(1, P + 1, d)
-        return None, dW, db, dcls, dpos, None
+        return None, dW, db, dcls, dpos, None, None
 
 
 class _ViTAttnFn(torch.autograd.Function):
     """x32 + o_proj(attention(q_proj(y), k_proj(y), v_proj(y))): the attention half of a pre-norm ViT layer (y = LN_before(x32),
-    bf16).  wc = (W_qkv [3d, d], W_qkv^T [d, 3d], W_o, W_o^T) bf16, cast by the caller this forward."""
+    bf16 or fp16: the dtype of everything 16-bit here).  wc = (W_qkv [3d, d], W_qkv^T [d, 3d], W_o, W_o^T) of y's dtype, cast by the caller
+    this forward."""
 
     @staticmethod
     def forward(ctx, x32, y, Wq, bq, Wk, bk, Wv, bv, Wo, bo, wc, dims):
@@ -174,7 +182,7 @@ class _ViTAttnFn(torch.autograd.Function):
         dh = d // H
         Wqkv, WqkvT, Woc, WoT = wc
         dev = y.device
-        qkv = torch.empty((n * L, 3 * d), dtype=torch.bfloat16, device=dev)
+        qkv = torch.empty((n * L, 3 * d), dtype=y.dtype, device=dev)
         for j, b in enumerate((bq, bk, bv)):
             ops.gemm_nt(y, Wqkv[j * d:(j + 1) * d], b, out=qkv[:, j * d:(j + 1) * d])
         o, lse2 = ops.attn_small_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], n, H, L, dh, want_lse=True)
@@ -191,13 +199,13 @@ class _ViTAttnFn(torch.autograd.Function):
         n, L, H = ctx.dims
         d = o.shape[1]
         dout32 = dout32 if dout32.is_contiguous() else dout32.contiguous()
-        ds = ops.cast(dout32, torch.bfloat16)
+        ds = ops.cast(dout32, y.dtype)
         sk = ctx.sinks
         grads = params.GradGroup(((sk[6], (d, d)), (sk[7], (d,))), ds.device)
         grads.tn(ds, o, 0, 1)
         dWo, dbo = grads.finish()
         do = ops.gemm_nt(ds, ctx.WoT)
-        dqkv = torch.empty((n * L, 3 * d), dtype=torch.bfloat16, device=y.device)
+        dqkv = torch.empty((n * L, 3 * d), dtype=y.dtype, device=y.device)
         ops.attn_small_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse2, n, H, L, d // H,
                            dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:])
         grads = params.GradGroup([(sk[2 * j], (d, d)) for j in range(3)] + [(sk[2 * j + 1], (d,)) for j in range(3)], y.device)
@@ -215,12 +223,15 @@ class _ViTAttnFn(torch.autograd.Function):
 class ViTExtractor(nn.Module):
     def __init__(self, cfg=None, compute_dtype='bf16', trainable=False, train_layers=None):
         """trainable=False: the frozen extractor (no parameter requires grad).  trainable=True: every parameter trains
-        (train.py:72), or with train_layers=K only the last K layers and the final LayerNorm (sketch_vit_finetune.py:43-69)."""
+        (train.py:72), or with train_layers=K only the last K layers and the final LayerNorm (sketch_vit_finetune.py:43-69).
+        compute_dtype: 'bf16' or 'fp16', the type of the MFMA operands and of every 16-bit activation (module docstring)."""
         super().__init__()
         cfg = cfg or vit_base_config()
-        if compute_dtype != 'bf16':
-            raise NotImplementedError('the short-sequence attention kernel is bf16 (fp32 residual stream)')
+        if compute_dtype not in _DTYPES:
+            raise NotImplementedError(f"the short-sequence attention kernels take bf16 or fp16 operands (fp32 residual stream), not '{compute_dtype}'")
         self.cfg = cfg
+        self.compute_dtype = compute_dtype
+        self.dtype = _DTYPES[compute_dtype]
         self.embeddings = _Embeddings(cfg)
         self.layers = nn.ModuleList([_Layer(cfg) for _ in range(cfg.num_hidden_layers)])
         self.layernorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
@@ -252,11 +263,12 @@ class ViTExtractor(nn.Module):
         return self.load_state_dict(out, strict=True)
 
     def _w(self, src):
-        """bf16 [out, in] copy of a frozen fp32 weight (refreshed if the parameter storage or version changed)."""
+        """[out, in] copy of a frozen fp32 weight in the extractor's dtype (refreshed if the parameter storage, its version or the dtype
+        changed)."""
         ent = self._wcache.get(id(src))
-        tag = (src.data_ptr(), src._version)
+        tag = (src.data_ptr(), src._version, self.dtype)
         if ent is None or ent[0] != tag:
-            ent = (tag, ops.cast(src.detach().reshape(src.shape[0], -1).contiguous(), torch.bfloat16))
+            ent = (tag, ops.cast(src.detach().reshape(src.shape[0], -1).contiguous(), self.dtype))
             self._wcache[id(src)] = ent
         return ent[1]
 
@@ -278,19 +290,19 @@ class ViTExtractor(nn.Module):
 
     def _forward_train(self, pixel_values, return_pre_norm):
         """autograd through the trained part (module docstring); the frozen prefix runs as in _forward_frozen, without autograd.
-        The bf16 copies of the trained weights are cast here, every call; the frozen path's copies of them are dropped."""
+        The 16-bit copies of the trained weights are cast here, every call; the frozen path's copies of them are dropped."""
         n, d = pixel_values.shape[0], self.cfg.hidden_size
         x32, L = self._stream_train(pixel_values)
         for lyr in self.layers[self._first_trained():]:
             x32 = self._layer_train(lyr, x32, n, L)
-        last, _ = layers.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, torch.bfloat16, True)
+        last, _ = layers.LNStreamFn.apply(x32, self.layernorm.weight, self.layernorm.bias, None, self.dtype, True)
         if return_pre_norm:
             return last.view(n, L, d), x32.view(n, L, d)
         return last.view(n, L, d)
 
     def _stream_train(self, pixel_values):
         """the fp32 stream in front of the first trained layer -> (x32 [n*L, d], L): the embedding Function when everything trains,
-        else the frozen embeddings and layers without autograd.  Drops the frozen path's bf16 copies of the trained weights."""
+        else the frozen embeddings and layers without autograd.  Drops the frozen path's 16-bit copies of the trained weights."""
         n = pixel_values.shape[0]
         for t in self.parameters():
             if t.requires_grad:
@@ -298,7 +310,7 @@ class ViTExtractor(nn.Module):
         if self.train_layers is None:
             emb = self.embeddings
             x32 = _ViTEmbedFn.apply(pixel_values, emb.patch_embeddings.projection.weight, emb.patch_embeddings.projection.bias,
-                                    emb.cls_token, emb.position_embeddings, self.cfg.patch_size)
+                                    emb.cls_token, emb.position_embeddings, self.cfg.patch_size, self.dtype)
             return x32, x32.shape[0] // n
         with torch.no_grad():
             x32, L = self._embed_frozen(pixel_values)
@@ -306,17 +318,16 @@ class ViTExtractor(nn.Module):
                 x32 = self._layer_frozen(lyr, x32, n, L)
         return x32, L
 
-    @staticmethod
-    def _attn_weights(a):
-        """(W_qkv [3d, d], W_qkv^T, W_o, W_o^T) bf16 of a trained layer's attention, cast now"""
-        dt = torch.bfloat16
+    def _attn_weights(self, a):
+        """(W_qkv [3d, d], W_qkv^T, W_o, W_o^T) of a trained layer's attention in the extractor's dtype, cast now"""
+        dt = self.dtype
         wqkv, wqkvT = ops.cast_transpose(torch.cat([a.q_proj.weight.detach(), a.k_proj.weight.detach(), a.v_proj.weight.detach()]), dt)
         woc, woT = ops.cast_transpose(a.o_proj.weight.detach(), dt)
         return wqkv, wqkvT, woc, woT
 
     def _mlp_train(self, lyr, x32):
         """x32 + fc2(gelu(fc1(LN_after(x32)))) with autograd, on however many rows x32 has"""
-        dt = torch.bfloat16
+        dt = self.dtype
         y = layers.LNStreamFn.apply(x32, lyr.layernorm_after.weight, lyr.layernorm_after.bias, None, dt, False)
         m = lyr.mlp
         w1c, w1T = ops.cast_transpose(m.fc1.weight.detach(), dt)
@@ -327,7 +338,7 @@ class ViTExtractor(nn.Module):
     def _layer_train(self, lyr, x32, n, L):
         """one trained layer on all tokens (module docstring)"""
         a = lyr.attention
-        y = layers.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, torch.bfloat16, False)
+        y = layers.LNStreamFn.apply(x32, lyr.layernorm_before.weight, lyr.layernorm_before.bias, None, self.dtype, False)
         x32 = _ViTAttnFn.apply(x32, y, a.q_proj.weight, a.q_proj.bias, a.k_proj.weight, a.k_proj.bias, a.v_proj.weight,
                                a.v_proj.bias, a.o_proj.weight, a.o_proj.bias, self._attn_weights(a), (n, L, self.cfg.num_attention_heads))
         return self._mlp_train(lyr, x32)
@@ -337,7 +348,7 @@ class ViTExtractor(nn.Module):
         cfg = self.cfg
         emb = self.embeddings
         n, d = pixel_values.shape[0], cfg.hidden_size
-        patches, P = _patch_rows(pixel_values, cfg.patch_size)
+        patches, P = _patch_rows(pixel_values, cfg.patch_size, self.dtype)
         proj = ops.gemm_nt(patches, self._w(emb.patch_embeddings.projection.weight), emb.patch_embeddings.projection.bias,
                            out_f32=True)
         del patches
@@ -345,7 +356,7 @@ class ViTExtractor(nn.Module):
 
     def _layer_frozen(self, lyr, x32, n, L):
         cfg = self.cfg
-        dt = torch.bfloat16
+        dt = self.dtype
         d, H = cfg.hidden_size, cfg.num_attention_heads
         dev = x32.device
         a = lyr.attention
@@ -364,7 +375,7 @@ class ViTExtractor(nn.Module):
         x32, L = self._embed_frozen(pixel_values)
         for lyr in self.layers:
             x32 = self._layer_frozen(lyr, x32, n, L)
-        last, _, _, _, _ = ops.layernorm_fwd(x32, self.layernorm.weight, self.layernorm.bias, torch.bfloat16, want32=True, want_t=False)
+        last, _, _, _, _ = ops.layernorm_fwd(x32, self.layernorm.weight, self.layernorm.bias, self.dtype, want32=True, want_t=False)
         if return_pre_norm:
             return last.view(n, L, d), x32.view(n, L, d)
         return last.view(n, L, d)

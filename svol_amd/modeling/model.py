@@ -6,7 +6,9 @@ prefixes.  The online extractors also take RAW frames — uint8 ``[B,T,H,W,3]`` 
 resize and normalise them on the device (svol_amd/ingest.py; ``args.pixel_preset`` overrides the backbone's preset).  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
 ``--backbone vit`` runs the ViT-B/16 extractor of ``backbone.py`` on the device for every frame and the sketch
 (SURVEY.md §8 f1), frozen unless ``args.train_backbone`` is 1 (``--finetune_layers K``: only the last K layers and the final
-LayerNorm train, as preprocess/sketch_vit_finetune.py does).  Its default stays frozen, unlike the ResNet's: the reference's
+LayerNorm train, as preprocess/sketch_vit_finetune.py does).  ``--compute_dtype fp16`` gives both ViT extractors fp16 operands, in the
+frozen and the trainable path alike; a bf16 or fp32 head keeps the bf16 extractors (the short-sequence attention kernels have no fp32
+form).  Its default stays frozen, unlike the ResNet's: the reference's
 ViT backbone cannot run as shipped (``device`` is undefined in ViTBackbone.forward, backbone.py:30), so no reference run
 trains it, and existing users of ``--backbone vit`` keep the frozen extractors; ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4), frozen by default,
 trained with the head when ``args.train_backbone`` is set (what the reference's train.py does).
@@ -47,8 +49,10 @@ def build_backbone(args):
         # docstring: why the default differs from the ResNet's)
         tb = bool(getattr(args, 'train_backbone', None) or False)
         tl = getattr(args, 'finetune_layers', None) if tb else None
-        return ViTBackbone(ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl),
-                           ViTExtractor(vit_base_config(), trainable=tb, train_layers=tl), pixel_preset=getattr(args, 'pixel_preset', None))
+        cd = 'fp16' if getattr(args, 'compute_dtype', 'bf16') == 'fp16' else 'bf16'   # (module docstring)
+        return ViTBackbone(ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
+                           ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
+                           pixel_preset=getattr(args, 'pixel_preset', None))
     if 'resnet' in args.backbone:  # backbone.py:133-152: ResNet-34 on the frames (7x7 tokens), ResNet-18 + avgpool on the sketch
         from .resnet import ResNetBackbone, resnet18, resnet34
         args.input_vid_dim = 512

@@ -14,7 +14,7 @@ state-dict keys of ``ViTForImageClassification`` (``vit.*``, ``classifier.*``). 
     cls_logits(pixel_values)  the TRAINING path.  The loss reads one row per image, so in the LAST block only the [CLS] query, its
                               out-projection, its MLP row and its LayerNorm row reach it; K and V are still needed for all tokens:
 
-        LN_before (all rows) -> K | V GEMMs (all rows), Q GEMM (n rows) -> svol_attn_cls_fwd (one query per (image, head), fp32
+        LN_before (all rows) -> K | V GEMMs (all rows), Q GEMM (n rows) -> svol_attn_cls_fwd[_h16] (one query per (image, head), fp32
         arithmetic) -> out-proj + fp32 residual (n rows) -> LN_after -> fc1 + GELU -> fc2 + residual (n rows) -> final LN (n rows)
         -> fp32 classifier GEMM
 
@@ -40,14 +40,15 @@ from .backbone import ViTExtractor, hf_rename, vit_base_config
 
 class _ViTClsAttnFn(torch.autograd.Function):
     """x32[cls rows] + o_proj(attention(q_proj(y[cls rows]), k_proj(y), v_proj(y))) -> [n, d] fp32: the attention half of the last
-    block for the [CLS] query alone (y = LN_before(x32) on all rows, bf16).  wc as _ViTAttnFn's."""
+    block for the [CLS] query alone (y = LN_before(x32) on all rows, bf16 or fp16: the dtype of everything 16-bit here).  wc as
+    _ViTAttnFn's."""
 
     @staticmethod
     def forward(ctx, x32, y, Wq, bq, Wk, bk, Wv, bv, Wo, bo, wc, dims):
         n, L, H = dims
         d = Wq.shape[0]
         Wqkv, WqkvT, Woc, WoT = wc
-        kv = torch.empty((n * L, 2 * d), dtype=torch.bfloat16, device=y.device)
+        kv = torch.empty((n * L, 2 * d), dtype=y.dtype, device=y.device)
         ops.gemm_nt(y, Wqkv[d:2 * d], bk, out=kv[:, :d])
         ops.gemm_nt(y, Wqkv[2 * d:], bv, out=kv[:, d:])
         q = ops.gemm_nt(y.view(n, L, d)[:, 0], Wqkv[:d], bq)
@@ -66,14 +67,14 @@ class _ViTClsAttnFn(torch.autograd.Function):
         d = o.shape[1]
         dev = y.device
         dout32 = dout32 if dout32.is_contiguous() else dout32.contiguous()
-        ds = ops.cast(dout32, torch.bfloat16)
+        ds = ops.cast(dout32, y.dtype)
         sk = ctx.sinks
         grads = params.GradGroup(((sk[6], (d, d)), (sk[7], (d,))), dev)
         grads.tn(ds, o, 0, 1)
         dWo, dbo = grads.finish()
         do = ops.gemm_nt(ds, ctx.WoT)
-        dq = torch.empty((n, d), dtype=torch.bfloat16, device=dev)
-        dkv = torch.empty((n * L, 2 * d), dtype=torch.bfloat16, device=dev)
+        dq = torch.empty((n, d), dtype=y.dtype, device=dev)
+        dkv = torch.empty((n * L, 2 * d), dtype=y.dtype, device=dev)
         ops.attn_cls_bwd(q, kv[:, :d], kv[:, d:], o, do, lse2, n, H, L, d // H, dq, dkv[:, :d], dkv[:, d:])
         ycls = y.view(n, L, d)[:, 0]
         grads = params.GradGroup(((sk[0], (d, d)), (sk[1], (d,))), dev)
@@ -147,16 +148,18 @@ class _XentFn(torch.autograd.Function):
 
 
 class SketchViTClassifier(nn.Module):
-    def __init__(self, cfg=None, num_labels=19, finetune_layers=1):
+    def __init__(self, cfg=None, num_labels=19, finetune_layers=1, compute_dtype='bf16'):
         """num_labels: 19 (sketchy), 21 (tu_berlin) or 24 (quickdraw) in the reference (sketch_vit_finetune.py:89-94);
-        finetune_layers = K >= 1: the last K layers, the final LayerNorm and the classifier train (:53-69)."""
+        finetune_layers = K >= 1: the last K layers, the final LayerNorm and the classifier train (:53-69);
+        compute_dtype: 'bf16' or 'fp16', the extractor's (ViTExtractor): both paths and extract_features run in it; the classifier GEMM
+        and the cross-entropy are fp32 either way.  fp16 training wants a scaled loss, as the head's (FlatAdamW.loss_scale)."""
         super().__init__()
         cfg = cfg or vit_base_config()
         if not 1 <= int(finetune_layers) <= cfg.num_hidden_layers:
             raise ValueError(f'finetune_layers must be in [1, {cfg.num_hidden_layers}], got {finetune_layers}')
         self.cfg = cfg
         self.num_labels = int(num_labels)
-        self.vit = ViTExtractor(cfg, trainable=True, train_layers=int(finetune_layers))
+        self.vit = ViTExtractor(cfg, compute_dtype=compute_dtype, trainable=True, train_layers=int(finetune_layers))
         self.classifier = nn.Linear(cfg.hidden_size, self.num_labels)
 
     @property
@@ -243,7 +246,7 @@ class SketchViTClassifier(nn.Module):
         if not pixel_values.is_cuda:
             raise RuntimeError('svol_amd SketchViTClassifier runs on the MI355X HIP kernels only (no CPU path)')
         vit = self.vit
-        dt = torch.bfloat16
+        dt = vit.dtype
         n = pixel_values.shape[0]
         x32, L = vit._stream_train(pixel_values)
         for lyr in vit.layers[vit._first_trained():-1]:

@@ -365,44 +365,54 @@ def attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, pre
     _lib.check(rc, 'svol_attn_bwd')
 
 
+def _h16_entry(name, t):
+    """the entry point of a short-sequence / one-query attention call: fp16 tensors go through the ``_h16`` twin (the entries without
+    the suffix refuse SVOL_F16), bf16 tensors keep the entry they always had"""
+    name = name + '_h16' if t.dtype == torch.float16 else name
+    return getattr(_lib.lib(), name), name
+
+
 def attn_small_fwd(q, k, v, n, H, L, dh, want_lse=False):
-    """short-sequence attention (L <= 256, bf16): q/k/v 2-D [n*L, >= H*dh] views (column slices allowed).
+    """short-sequence attention (L <= 256, bf16 or fp16): q/k/v 2-D [n*L, >= H*dh] views (column slices allowed).
     -> (o [n*L, H*dh], lse2 [n, H, L] fp32 with want_lse, else None)."""
     o = torch.empty((n * L, H * dh), dtype=q.dtype, device=q.device)
     args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0))
     tail = (n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream())
     if want_lse:
         lse2 = torch.empty((n, H, L), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().svol_attn_small_fwd_lse(*args, _ptr(lse2), *tail), 'svol_attn_small_fwd_lse')
+        fn, name = _h16_entry('svol_attn_small_fwd_lse', q)
+        _lib.check(fn(*args, _ptr(lse2), *tail), name)
         return o, lse2
-    _lib.check(_lib.lib().svol_attn_small_fwd(*args, *tail), 'svol_attn_small_fwd')
+    fn, name = _h16_entry('svol_attn_small_fwd', q)
+    _lib.check(fn(*args, *tail), name)
     return o, None
 
 
 def attn_small_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
-    """gradients of attn_small_fwd into dq / dk / dv (2-D bf16 views, column slices allowed)."""
-    _lib.check(_lib.lib().svol_attn_small_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                                              _ptr(do), do.stride(0), _ptr(lse2), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0),
-                                              _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
-               'svol_attn_small_bwd')
+    """gradients of attn_small_fwd into dq / dk / dv (2-D views of q's dtype, column slices allowed)."""
+    fn, name = _h16_entry('svol_attn_small_bwd', q)
+    _lib.check(fn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(do), do.stride(0), _ptr(lse2),
+                  _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
+               name)
 
 
 def attn_cls_fwd(q, k, v, n, H, L, dh):
-    """one query row per image against all L <= 256 keys (bf16 operands, fp32 arithmetic): q [n, H*dh], k / v 2-D [n*L, >= H*dh]
-    views (column slices allowed) -> (o [n, H*dh] bf16, lse2 [n, H] fp32, log2 units)."""
+    """one query row per image against all L <= 256 keys (bf16 or fp16 operands, fp32 arithmetic): q [n, H*dh], k / v 2-D [n*L, >= H*dh]
+    views (column slices allowed) -> (o [n, H*dh] of q's dtype, lse2 [n, H] fp32, log2 units)."""
     o = torch.empty((n, H * dh), dtype=q.dtype, device=q.device)
     lse2 = torch.empty((n, H), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.lib().svol_attn_cls_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                                            _ptr(lse2), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()), 'svol_attn_cls_fwd')
+    fn, name = _h16_entry('svol_attn_cls_fwd', q)
+    _lib.check(fn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(lse2), n, H, L, dh,
+                  1.0 / math.sqrt(dh), _dt(q), _stream()), name)
     return o, lse2
 
 
 def attn_cls_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
-    """gradients of attn_cls_fwd into dq [n, H*dh] and dk / dv [n*L, H*dh] (2-D bf16 views, column slices allowed)."""
-    _lib.check(_lib.lib().svol_attn_cls_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                                            _ptr(do), do.stride(0), _ptr(lse2), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0),
-                                            _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
-               'svol_attn_cls_bwd')
+    """gradients of attn_cls_fwd into dq [n, H*dh] and dk / dv [n*L, H*dh] (2-D views of q's dtype, column slices allowed)."""
+    fn, name = _h16_entry('svol_attn_cls_bwd', q)
+    _lib.check(fn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(do), do.stride(0), _ptr(lse2),
+                  _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), n, H, L, dh, 1.0 / math.sqrt(dh), _dt(q), _stream()),
+               name)
 
 
 def softmax_xent(logits, targets):

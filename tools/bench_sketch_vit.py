@@ -8,6 +8,9 @@ ViT-B/16, finetune_layers = 1, AdamW): ms per step and per phase (forward, loss,
                                                         (what a user could run before the classifier existed; --root selects the
                                                         tree whose svol_amd is imported, so a checkout of an older commit can be timed)
 
+--dtype {bf16,fp16}: the extractor's operand type (compute_dtype); fp16 multiplies the loss by --loss_scale (4096) and hands the same
+factor to FlatAdamW, which divides it out inside the update.
+
 Timing: --blocks blocks of --steps steps after --warmup steps; a block's step time is a host clock around the block, ending in a
 device synchronise; the phase times are device events inside the steps.  Reported: the median block, every block, and the shader clock
 the chip held under --steps more untimed steps (csrc/clock_probe.hip, bench.py's `sclk_ghz`).  One JSON line.
@@ -28,6 +31,8 @@ def main():
     ap.add_argument('--layers', type=int, default=12)
     ap.add_argument('--finetune_layers', type=int, default=1)
     ap.add_argument('--num_labels', type=int, default=19)
+    ap.add_argument('--dtype', choices=('bf16', 'fp16'), default='bf16')
+    ap.add_argument('--loss_scale', type=float, default=4096.0)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--blocks', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=5)
@@ -42,9 +47,11 @@ def main():
     cfg = syn.vit_config(num_hidden_layers=a.layers)
     x = syn.synth_images(a.n, cfg, seed=2).to(dev)
     targets = (torch.arange(a.n) % a.num_labels).to(dev)
+    kw = {} if a.dtype == 'bf16' else {'compute_dtype': a.dtype}   # (an older tree under --root has no such argument)
+    scale = a.loss_scale if a.dtype == 'fp16' else 1.0
     if a.path == 'extractor':
         from svol_amd.modeling.backbone import ViTExtractor
-        m = ViTExtractor(cfg, trainable=True, train_layers=a.finetune_layers)
+        m = ViTExtractor(cfg, trainable=True, train_layers=a.finetune_layers, **kw)
         m.load_state_dict(syn.synth_vit_state_dict(cfg, seed=1))
         m.to(dev).train()
         R = torch.randn(a.n, cfg.hidden_size, device=dev)
@@ -52,7 +59,7 @@ def main():
         lossfn = lambda t: (t * R).sum()               # noqa: E731
     else:
         from svol_amd.modeling.sketch_vit import SketchViTClassifier, _XentFn
-        m = SketchViTClassifier(cfg, a.num_labels, a.finetune_layers)
+        m = SketchViTClassifier(cfg, a.num_labels, a.finetune_layers, **kw)
         m.load_state_dict(syn.synth_classifier(cfg, a.num_labels, seed=1))
         m.to(dev).train()
         fwd = (lambda: m.cls_logits(x)) if a.path == 'cls' else (lambda: m(x)[2])
@@ -60,6 +67,7 @@ def main():
     params = [p for p in m.parameters() if p.requires_grad]
     red = parallel.BucketedGradAllReduce(parallel.arrival_order(m), ordered=True)
     opt = parallel.FlatAdamW(red, lr=1e-4, weight_decay=1e-4, params=params)
+    opt.loss_scale = scale
     marks = []
 
     def step(timed=False):
@@ -73,7 +81,7 @@ def main():
         loss = lossfn(out)
         if timed:
             ev[2].record()
-        loss.backward()
+        (loss * scale if scale != 1.0 else loss).backward()
         if timed:
             ev[3].record()
         red.finish()
@@ -96,7 +104,7 @@ def main():
         blocks.append((time.perf_counter() - t0) / a.steps * 1e3)
         phases.append([sum(ev[i].elapsed_time(ev[i + 1]) for ev in marks) / a.steps for i in range(4)])
     mid = sorted(range(a.blocks), key=lambda i: blocks[i])[a.blocks // 2]
-    res = {'path': a.path, 'n': a.n, 'layers': a.layers, 'finetune_layers': a.finetune_layers, 'steps': a.steps,
+    res = {'path': a.path, 'dtype': a.dtype, 'n': a.n, 'layers': a.layers, 'finetune_layers': a.finetune_layers, 'steps': a.steps,
            'ms_per_step': round(statistics.median(blocks), 4), 'ms_per_step_blocks': [round(b, 4) for b in blocks],
            'phase_ms': dict(zip(('forward', 'loss', 'backward', 'optimizer'), (round(v, 4) for v in phases[mid]))),
            'loss': round(float(loss), 5), 'sclk_ghz': shader_clock(torch, dev, step, a.steps)}
