@@ -436,7 +436,7 @@ def _vh_fwd_layout(B, L, D, H, F, e):
 def _vh_bwd_layout(B, L, D, H, F, e):
     M = B * L
     return [('DS32_3', M * D * 4), ('DS3', M * D * e), ('DPRE', M * F * e), ('DY2', M * D * e), ('DS32_2', M * D * 4), ('G2D', M * D * e),
-            ('DO', M * D * e), ('DQKV', M * 3 * D * e), ('DELTA', 3 * B * H * L * 4), ('DXQP', M * D * e), ('DXQ', M * D * e),
+            ('DO', M * D * e), ('DQKV', M * 3 * D * e), ('DELTA', 3 * B * H * L * 4), ('DXQ', M * D * e),
             ('GATE_WS2', (B * L + B * H) * 4), ('DX32', M * D * 4)]
 
 
@@ -609,11 +609,12 @@ def _qc_fwd_layout(B, N, L, D, H, F, e, qe):
             ('YPOS', R * D * qe)]
 
 
-def _qc_bwd_layout(B, N, L, D, H, F, e, qe):
+def _qc_bwd_layout(B, N, L, D, H, F, e, qe, merged):
+    """merged: no DMPOS slot — the program then writes dk W_k + dv W_v, ONE product over K = 2 D, into DMV"""
     R, M = B * N, B * L
     return [('DS32_6', R * D * 4), ('DS6', R * D * qe), ('DPRE', R * F * qe), ('DY5', R * D * qe), ('G5D', R * D * qe), ('DOAQ', R * D * qe),
             ('DOA', R * D * e), ('DQC', R * D * e), ('DQ', R * D * qe), ('DKV', M * 2 * D * e), ('DELTA', 3 * B * H * N * 4),
-            ('DO32', R * D * 4), ('DXQP', R * D * qe), ('DMPOS', M * D * e), ('DMV', M * D * e)]
+            ('DO32', R * D * 4), ('DXQP', R * D * qe)] + ([] if merged else [('DMPOS', M * D * e)]) + [('DMV', M * D * e)]
 
 
 class QueryCrossFn(torch.autograd.Function):
@@ -621,7 +622,9 @@ class QueryCrossFn(torch.autograd.Function):
     cross_modal_transformer.py:151-158."""
 
     @staticmethod
-    def forward(ctx, pl, o32, o, opos, mv, mpos, kbias, qpos, *params):
+    def forward(ctx, pl, o32, o, opos, mv, mpos, kbias, qpos, merged, *params):
+        """merged: mpos is mv + a constant (the video half's m + pos), so the backward returns the whole gradient through mv and
+        None for mpos — one dX product over [dk dv] instead of two video-sized ones, one 16-bit gradient fewer for LN3' to read."""
         B, N, D = o.shape
         L = mv.shape[1]
         layer = pl.layer()
@@ -632,11 +635,12 @@ class QueryCrossFn(torch.autograd.Function):
         assert o32_.dtype == torch.float32 and o_.dtype == qdt and opos_.dtype == qdt and qpos_.dtype == qdt
         assert mv_.dtype == dt and mpos_.dtype == dt and kb_.dtype == torch.float32
         wsb = ops.attn_ws_bytes(dt, B, H, N, L, D // H)
-        lay = _open(ctx, pl, QC, (B, N, L, D, H, F, dt, qdt), _dims(B, L, N, D, H, F, dt, qdt, wsb), len(params), o.device,
+        lay = _open(ctx, pl, QC, (B, N, L, D, H, F, dt, qdt, merged), _dims(B, L, N, D, H, F, dt, qdt, wsb), len(params), o.device,
                     lambda: _qc_fwd_layout(B, N, L, D, H, F, e, qe), lambda: [('ATTN_WS', max(wsb, 16))],
                     O32=o32_, O=o_, OPOS=opos_, MV=mv_, MPOS=mpos_, KBIAS=kb_, QPOS=qpos_)
         _call('svol_query_cross_fwd', ctx)
         ctx.shape = (B, N, L, D, H, F)
+        ctx.merged = merged
         ctx.save_for_backward(o32_, o_, opos_, mv_, mpos_, kb_, qpos)
         return (lay.view(ctx.arena, 'Y32', torch.float32, (B, N, D)), lay.view(ctx.arena, 'Y', qdt, (B, N, D)),
                 lay.view(ctx.arena, 'YPOS', qdt, (B, N, D)))
@@ -644,24 +648,28 @@ class QueryCrossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy32, dy, dypos):
         if dy32 is None and dy is None and dypos is None:
-            return _no_grads(ctx, 8)
+            return _no_grads(ctx, 9)
         B, N, L, D, H, F = ctx.shape
         o32_, o_, opos_, mv_, mpos_, kb_, qpos = ctx.saved_tensors
         dt, qdt = ctx.pl.dt, ctx.pl.qdt
         gq = _qpos_target(ctx, qpos, ctx.needs_input_grad[7], N, D)
-        lay, tmp, bufs, gs = _open_bwd(ctx, o_.device, lambda: _qc_bwd_layout(B, N, L, D, H, F, _ESZ[dt], _ESZ[qdt]),
+        lay, tmp, bufs, gs = _open_bwd(ctx, o_.device, lambda: _qc_bwd_layout(B, N, L, D, H, F, _ESZ[dt], _ESZ[qdt], ctx.merged),
                                        DY32=dy32, DY=dy, DYPOS=dypos)
         _call('svol_query_cross_bwd', ctx)
-        pg = _close_bwd(ctx, 'svol_query_cross_wgrad', bufs, [ctx.arena, tmp, opos_, mv_, mpos_], 8)
+        pg = _close_bwd(ctx, 'svol_query_cross_wgrad', bufs, [ctx.arena, tmp, opos_, mv_, mpos_], 9)
         vq = lambda n_, dt_: lay.view(tmp, n_, dt_, (B, N, D))
         vm = lambda n_: lay.view(tmp, n_, dt, (B, L, D))
-        return (None, vq('DO32', torch.float32), None, vq('DXQP', qdt), vm('DMV'), vm('DMPOS'), None, _qpos_grad(gq, qdt)) + pg
+        return (None, vq('DO32', torch.float32), None, vq('DXQP', qdt), vm('DMV'), None if ctx.merged else vm('DMPOS'), None,
+                _qpos_grad(gq, qdt), None) + pg
 
 
 def query_cross(layer, out, mv, mpos, kbias, qpos, dt, qdt):
     pl = plan(layer, QC, dt, qdt)
     o32, o, opos = out
-    return QueryCrossFn.apply(pl, o32, o, opos, mv, mpos, kbias, qpos, *pl.inputs(o32, opos, mv, mpos))
+    # both from one video half (m and m + pos, pos without a gradient): their gradients only ever meet as a sum
+    fn = mv.grad_fn
+    merged = fn is not None and fn is mpos.grad_fn and isinstance(fn, VideoHalfFn._backward_cls)
+    return QueryCrossFn.apply(pl, o32, o, opos, mv, mpos, kbias, qpos, merged, *pl.inputs(o32, opos, mv, mpos))
 
 
 def trace_dump() -> str:

@@ -255,10 +255,10 @@ int svol_video_half_bwd(const int64_t* dims, void* const* p, int phase, void* s)
             if (zrc) return zrc;
             record(P(EV_CLEAN_OUT), zs);
         }
-        // d(y + pos) = [dq dk] W_qk ; dy = dv W_v
-        RUN(nt(P(DQKV), 3 * D, P(W_IN_T), 3 * D, P(DXQP), D, nullptr, nullptr, M, D, 2 * D, dt, s));
-        RUN(nt(at(P(DQKV), 2 * D, dt), 3 * D, at(P(W_IN_T), 2 * D, dt), 3 * D, P(DXQ), D, nullptr, nullptr, M, D, D, dt, s));
-        RUN(svol_gate_bwd(f32(P(DS32_2)), P(DXQ), P(DXQP), f32(P(X32)), P(POS), f32(P(U)), f32(P(G1)), f32(P(A)), f32(P(MEAN1)),
+        // pos has no gradient here, so d(y + pos) = [dq dk] W_qk and dy = dv W_v only ever meet as their sum: dy1 = [dq dk dv] W_in,
+        // ONE product over K = 3 D (the sum is rounded to the compute type once; the DXQP slot is not used)
+        RUN(nt(P(DQKV), 3 * D, P(W_IN_T), 3 * D, P(DXQ), D, nullptr, nullptr, M, D, 3 * D, dt, s));
+        RUN(svol_gate_bwd(f32(P(DS32_2)), P(DXQ), nullptr, f32(P(X32)), P(POS), f32(P(U)), f32(P(G1)), f32(P(A)), f32(P(MEAN1)),
                           f32(P(RSTD1)), f32(P(GATE_WS)), f32(P(GATE_WS2)), f32(P(DX32)), f32(P(DU)), f32(P(DG1)), f32(P(DBT1)), d.B, d.L,
                           D, d.H, dt, s));
     }
@@ -417,8 +417,13 @@ int svol_query_cross_bwd(const int64_t* dims, void* const* p, void* s) {
                       P(DKV), 2 * D, at(P(DKV), D, dt), 2 * D, d.B, d.H, d.N, d.L, dh, attn_scale(dh), attn_premul(dh, dt), P(ATTN_WS),
                       d.ws_bytes, dt, s));
     // the two video-sized products first: the video half's backward waits for them
-    RUN(nt(P(DKV), 2 * D, at(P(W_KV_T), D, dt), 3 * D, P(DMPOS), D, nullptr, nullptr, M, D, D, dt, s));
-    RUN(nt(at(P(DKV), D, dt), 2 * D, at(P(W_KV_T), 2 * D, dt), 3 * D, P(DMV), D, nullptr, nullptr, M, D, D, dt, s));
+    // (no DMPOS slot: the caller's m + pos is its m plus a constant, and wants the sum dk W_k + dv W_v — one product over K = 2 D into DMV)
+    if (P(DMPOS)) {
+        RUN(nt(P(DKV), 2 * D, at(P(W_KV_T), D, dt), 3 * D, P(DMPOS), D, nullptr, nullptr, M, D, D, dt, s));
+        RUN(nt(at(P(DKV), D, dt), 2 * D, at(P(W_KV_T), 2 * D, dt), 3 * D, P(DMV), D, nullptr, nullptr, M, D, D, dt, s));
+    } else {
+        RUN(nt(P(DKV), 2 * D, at(P(W_KV_T), D, dt), 3 * D, P(DMV), D, nullptr, nullptr, M, D, 2 * D, dt, s));
+    }
     const void* dq = P(DQC);
     if (mixed) {
         RUN(svol_cast(P(DQC), dt, P(DQ), qdt, R * D, s));

@@ -8,7 +8,8 @@
 //   1. weight-stationary, gemm_ws_bf16.hip: K == 256 (no wrap), N % 64 == 0, M >= 4096; bf16 out: no residual, act NONE / GELU / RELU /
 //      GELU_D; fp32 out: residual, no act / pre / colscale; epi 1: aux, bf16 out; 16-byte aligned rows
 //   2. full-width tiles, gemm_n256_bf16.hip: N % 256 == 0, K % 32 == 0, K >= 512, M >= 4096, epi 0, no pre / colscale; bf16 out: act
-//      NONE / GELU / RELU, no residual; fp32 out: act NONE; 16-byte aligned rows
+//      NONE / GELU / RELU, no residual; fp32 out: act NONE; 16-byte aligned rows.  Two grids, same bits: 128-row tiles; with N == 256 and
+//      M > 128 x the device's CU count the balanced variant — one eight-wave workgroup per CU for every 256 x CUs rows, equal rows (<= 256) each
 //   3. skinny split-K, gemm_bf16.hip: M <= 2048, K % 256 == 0, N % 64 == 0
 //   4. 128 x 128 tiles, gemm_bf16.hip: everything else up to 65535 row tiles; 64-deep K steps when K % 64 == 0 and K >= 1024
 // and when none of them takes the call (or the dtype is fp32, or A2 is set), gemm.hip goes on with
