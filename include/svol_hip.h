@@ -531,11 +531,12 @@ int svol_vit_embed(const float* patch_proj, const float* cls_token, const float*
  * BatchNorm scale folded in, BatchNorm shift as bias, SVOL_ACT_RELU / SVOL_ACT_RELU_RES epilogue); activations are NHWC.
  * cols[(n,ho,wo), (ky,kx,c)] = x[n, ho*stride-pad+ky, wo*stride-pad+kx, c] (0 outside the image); columns kh*kw*C .. ldcols-1
  * are zero-filled.  x is addressed by element strides (sn, sh, sw, sc), so NCHW pixel tensors and NHWC activations both fit;
- * src_dtype / dtype: element types of x / cols (fp32 -> bf16 conversion happens here for the stem). */
+ * src_dtype / dtype: element types of x / cols — fp32 -> fp32, fp32 -> bf16 / fp16 (the stem's conversion happens here), bf16 -> bf16,
+ * fp16 -> fp16; any other pair is SVOL_E_INVALID. */
 int svol_im2col(const void* x, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int src_dtype, void* cols, int64_t ldcols,
                 int64_t N, int64_t H, int64_t W, int64_t C, int64_t kh, int64_t kw, int64_t stride, int64_t pad, int dtype,
                 void* stream);
-/* Convolution without the im2col matrix (bf16, C % 32 == 0): y[(n,ho,wo), co] = act(sum x[n, ho*stride-pad+ky, wo*stride-pad+kx, c]
+/* Convolution without the im2col matrix (dtype SVOL_BF16 or SVOL_F16 — x, w, y, residual alike; C % 32 == 0): y[(n,ho,wo), co] = act(sum x[n, ho*stride-pad+ky, wo*stride-pad+kx, c]
  * * w[co, (ky*kw + kx)*C + c] + bias[co] (+ residual[(n,ho,wo), co])); x NHWC contiguous, w [Cout, >= kh*kw*C] with leading
  * dimension ldw, y / residual [N*Ho*Wo, Cout] contiguous; act in {SVOL_ACT_NONE, SVOL_ACT_RELU, SVOL_ACT_RELU_RES}.  The GEMM
  * tile kernel gathers its A operand from the activation tensor inside its LDS-DMA loads (zero padding = out-of-range buffer
@@ -543,10 +544,10 @@ int svol_im2col(const void* x, int64_t sn, int64_t sh, int64_t sw, int64_t sc, i
 int svol_conv_nhwc(const void* x, const void* w, int64_t ldw, void* y, const float* bias, int act, const void* residual,
                    int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh, int64_t kw, int64_t stride,
                    int64_t pad, int dtype, void* stream);
-/* nn.MaxPool2d(k, stride, pad) on NHWC activations, C % 8 == 0 (resnet stem: 3, 2, 1). */
+/* nn.MaxPool2d(k, stride, pad) on NHWC activations, C % 8 == 0 (resnet stem: 3, 2, 1); dtype SVOL_F32, SVOL_BF16 or SVOL_F16. */
 int svol_maxpool_nhwc(const void* x, void* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t k, int64_t stride,
                       int64_t pad, int dtype, void* stream);
-/* nn.AdaptiveAvgPool2d(1) on NHWC activations: y[n, c] (fp32) = mean over the HW positions. */
+/* nn.AdaptiveAvgPool2d(1) on NHWC activations (dtype SVOL_F32, SVOL_BF16 or SVOL_F16): y[n, c] (fp32) = mean over the HW positions. */
 int svol_avgpool_nhwc(const void* x, float* y, int64_t N, int64_t HW, int64_t C, int dtype, void* stream);
 /* ---- the backbone in TRAINING mode (the reference optimises every parameter of build_model(args), train.py:72; its backbone is
  * torchvision's ResNet-34 / ResNet-18 with train-mode BatchNorm, backbone.py:133-152).  Activations NHWC [M = n*h*w, C], 16-bit; C a

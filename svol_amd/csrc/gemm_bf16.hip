@@ -465,16 +465,13 @@ int svol_gemm_nt_bf16_fast(const GemmCall& c) {
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
 }
 
-#ifndef SVOL_H16_FP16   // (the ResNet extractor is a bf16 / fp32 path)
-// Implicit-GEMM convolution on NHWC bf16 activations: y[(n,ho,wo), co] = act(sum_{ky,kx,c} x[n, ho*s-p+ky,
+// Implicit-GEMM convolution on NHWC 16-bit activations: y[(n,ho,wo), co] = act(sum_{ky,kx,c} x[n, ho*s-p+ky,
 // wo*s-p+kx, c] * w[co, (ky,kx,c)] + bias[co] (+ residual)), the 128x128 tile kernel above with the A operand gathered by the
-// LDS-DMA loads themselves (padding = out-of-range buffer offsets, which read as zero).  C % 32 == 0.
-extern "C" int svol_conv_nhwc(const void* x, const void* w, int64_t ldw, void* y, const float* bias, int act, const void* residual,
-                              int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh, int64_t kw, int64_t stride,
-                              int64_t pad, int dtype, void* stream) {
-    if (!x || !w || !y || N < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
-        return SVOL_E_INVALID;
-    if (dtype != SVOL_BF16) return SVOL_E_UNSUPPORTED;
+// LDS-DMA loads themselves (padding = out-of-range buffer offsets, which read as zero).  C % 32 == 0.  This launcher is built for
+// both operand types; the one C-ABI entry below (in the bf16 build) hands it the arguments it has checked for null / sign.
+int svol_conv_nhwc_bf16_launch(const void* x, const void* w, int64_t ldw, void* y, const float* bias, int act, const void* residual,
+                               int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh, int64_t kw, int64_t stride,
+                               int64_t pad, hipStream_t s) {
     const int64_t Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
     if (Ho <= 0 || Wo <= 0) return SVOL_E_INVALID;
     const int64_t M = N * Ho * Wo, K = kh * kw * C;
@@ -489,9 +486,19 @@ extern "C" int svol_conv_nhwc(const void* x, const void* w, int64_t ldw, void* y
                (int)H, (int)W, (int)C, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo, a_bytes, (int)K};
     dim3 grid((unsigned)((Cout + 127) / 128), (unsigned)((M + 127) / 128));
     if (grid.y > 65535u) return SVOL_E_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (C % 64 == 0 && K >= 1024) hipLaunchKernelGGL(conv_nhwc_bf16_k64, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(conv_nhwc_bf16_k32, grid, dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? SVOL_OK : SVOL_E_LAUNCH;
+}
+
+#ifndef SVOL_H16_FP16   // one exported entry for both operand types
+extern "C" int svol_conv_nhwc(const void* x, const void* w, int64_t ldw, void* y, const float* bias, int act, const void* residual,
+                              int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh, int64_t kw, int64_t stride,
+                              int64_t pad, int dtype, void* stream) {
+    if (!x || !w || !y || N < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
+        return SVOL_E_INVALID;
+    if (!svol_is16(dtype)) return SVOL_E_UNSUPPORTED;
+    return (dtype == SVOL_BF16 ? svol_conv_nhwc_bf16_launch : svol_conv_nhwc_f16_launch)(x, w, ldw, y, bias, act, residual, N, H, W, C, Cout,
+                                                                                        kh, kw, stride, pad, reinterpret_cast<hipStream_t>(stream));
 }
 #endif

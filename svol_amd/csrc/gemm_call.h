@@ -21,6 +21,8 @@
 //      sizes <= 2^30, a row chunk within 32-bit byte offsets; grouped: 2 .. SVOL_TN_GROUP_MAX problems that all fit
 //   2. the generic kernel (tn_generic_plan, gemm.hip): N, K, lda, ldb on the 16-byte grid, aligned A / B; grouped for fp32 only
 //   A group that does not fit as a whole is issued problem by problem.  svol_conv_wgrad_*_fast is tn_plan on an im2col view.
+// svol_conv_nhwc (one C-ABI entry, gemm_bf16.hip) picks svol_conv_nhwc_*_launch by dtype: the 128 x 128 NT tile kernel with its A operand
+// gathered from an NHWC activation.
 #pragma once
 #include "common.h"
 
@@ -46,7 +48,10 @@ struct GemmCall {
     int svol_gemm_tn_##T##_fast(const svol_tn_problem& q, hipStream_t s);                                                         \
     int svol_gemm_tn_##T##_grouped(const svol_tn_problem* pr, int n, hipStream_t s);                                              \
     int svol_conv_wgrad_##T##_fast(const void* dz, const void* x, float* dwp, int64_t N, int64_t H, int64_t W, int64_t C,         \
-                                   int64_t Cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad, int64_t Kp, hipStream_t s);
+                                   int64_t Cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad, int64_t Kp, hipStream_t s);  \
+    int svol_conv_nhwc_##T##_launch(const void* x, const void* w, int64_t ldw, void* y, const float* bias, int act,               \
+                                    const void* residual, int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t kh,  \
+                                    int64_t kw, int64_t stride, int64_t pad, hipStream_t s);
 SVOL_GEMM_H16_ENTRIES(bf16)
 SVOL_GEMM_H16_ENTRIES(f16)
 #undef SVOL_GEMM_H16_ENTRIES

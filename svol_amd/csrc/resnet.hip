@@ -7,6 +7,7 @@
 //                       the same entry point; NHWC sources with c % 8 == 0 take a 16-byte-per-thread path.
 //   svol_maxpool_nhwc   k x k / stride / pad max pooling (the stem's 3x3 s2 p1), 8 channels per thread
 //   svol_avgpool_nhwc   mean over the h*w positions -> [n, c] fp32 (the sketch branch keeps torchvision's avgpool)
+// Activations bf16, fp16 or fp32; the two 16-bit types run the same kernels (a copy moves bits, a conversion is one template argument).
 #include "common.h"
 
 namespace {
@@ -34,10 +35,11 @@ __global__ void im2col_generic_kernel(const TS* __restrict__ x, int64_t sn, int6
 // one output row: the kh input rows they touch are staged in LDS with reads that run along the image row (coalesced in the
 // source), then the WT destination rows are written as 16-byte chunks (coalesced in the destination).
 constexpr int STEM_WT = 32;
-template <typename TS>
+template <typename TS, typename TD>   // TD: bf16_t / f16_t
 __global__ __launch_bounds__(256) void im2col_stem_kernel(const TS* __restrict__ x, int64_t sn, int64_t sh, int64_t sw, int64_t sc,
-                                                           bf16_t* __restrict__ cols, int64_t ldcols, int H, int W, int C, int kh,
+                                                           TD* __restrict__ cols, int64_t ldcols, int H, int W, int C, int kh,
                                                            int kw, int stride, int pad, int Ho, int Wo) {
+    typedef __attribute__((ext_vector_type(8))) TD td_x8;
     extern __shared__ float tile[];  // [C][kh][span]
     const int span = (STEM_WT - 1) * stride + kw;
     const int wo0 = blockIdx.x * STEM_WT, ho = blockIdx.y;
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void im2col_stem_kernel(const TS* __restrict__
     for (int j = threadIdx.x; j < STEM_WT * chunks; j += 256) {
         const int r = j / chunks, k8 = (j - r * chunks) * 8;
         if (wo0 + r >= Wo) continue;
-        bf16x8 o;
+        td_x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int k = k8 + e;
@@ -63,13 +65,13 @@ __global__ __launch_bounds__(256) void im2col_stem_kernel(const TS* __restrict__
                 const int c = k % C, kx = (k / C) % kw, ky = k / (C * kw);
                 v = tile[(c * kh + ky) * span + r * stride + kx];
             }
-            o[e] = (bf16_t)v;
+            o[e] = (TD)v;
         }
-        *reinterpret_cast<bf16x8*>(cols + ((n * Ho + ho) * (int64_t)Wo + wo0 + r) * ldcols + k8) = o;
+        *reinterpret_cast<td_x8*>(cols + ((n * Ho + ho) * (int64_t)Wo + wo0 + r) * ldcols + k8) = o;
     }
 }
 
-// NHWC contiguous source, C % 8 == 0 (bf16) / C % 4 == 0 (fp32): one 16-byte chunk per thread, consecutive threads walk
+// NHWC contiguous source, C % 8 == 0 (bf16, fp16) / C % 4 == 0 (fp32): one 16-byte chunk per thread, consecutive threads walk
 // c, then kx, then ky of one output position (contiguous in the destination row)
 template <typename T>
 __global__ void im2col_nhwc_vec_kernel(const T* __restrict__ x, T* __restrict__ cols, int64_t ldcols, int H, int W, int C, int kh,
@@ -153,17 +155,19 @@ extern "C" int svol_im2col(const void* x, int64_t sn, int64_t sh, int64_t sw, in
     if (rows * ldcols / 256 >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool nhwc = sc == 1 && sw == C && sh == W * C && sn == H * W * C;
-    const int V = dtype == SVOL_BF16 ? 8 : 4;
+    if (dtype != SVOL_F32 && !svol_is16(dtype)) return SVOL_E_INVALID;
+    const int V = svol_is16(dtype) ? 8 : 4;
     if (nhwc && src_dtype == dtype && C % V == 0 && ldcols % V == 0 && aligned16(x) && aligned16(cols)) {
         const int64_t total = rows * kh * kw * (C / V);
-        if (dtype == SVOL_BF16)
+        // (a copy of whole 16-byte chunks: both 16-bit types go through the bf16_t instances, bit for bit)
+        if (svol_is16(dtype))
             hipLaunchKernelGGL(im2col_nhwc_vec_kernel<bf16_t>, dim3(nblk(total)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)cols, ldcols,
                                (int)H, (int)W, (int)C, (int)kh, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo, rows);
         else
             hipLaunchKernelGGL(im2col_nhwc_vec_kernel<float>, dim3(nblk(total)), dim3(256), 0, s, (const float*)x, (float*)cols, ldcols,
                                (int)H, (int)W, (int)C, (int)kh, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo, rows);
         if (ldcols > K) {
-            if (dtype == SVOL_BF16)
+            if (svol_is16(dtype))   // (+0.0 is sixteen zero bits in either type)
                 hipLaunchKernelGGL(zero_tail_kernel<bf16_t>, dim3(nblk(rows * (ldcols - K))), dim3(256), 0, s, (bf16_t*)cols, ldcols, (int)K, rows);
             else
                 hipLaunchKernelGGL(zero_tail_kernel<float>, dim3(nblk(rows * (ldcols - K))), dim3(256), 0, s, (float*)cols, ldcols, (int)K, rows);
@@ -171,17 +175,19 @@ extern "C" int svol_im2col(const void* x, int64_t sn, int64_t sh, int64_t sw, in
         SVOL_CHECK_LAUNCH();
         return SVOL_OK;
     }
-    if (dtype == SVOL_BF16 && C <= 4 && ldcols % 8 == 0 && aligned16(cols) && Ho <= 65535 && N <= 65535) {
+    if (svol_is16(dtype) && C <= 4 && ldcols % 8 == 0 && aligned16(cols) && Ho <= 65535 && N <= 65535) {
         const size_t sh_bytes = (size_t)C * kh * ((STEM_WT - 1) * stride + kw) * sizeof(float);
         if (sh_bytes <= 64 * 1024) {
             const dim3 gs((unsigned)((Wo + STEM_WT - 1) / STEM_WT), (unsigned)Ho, (unsigned)N);
-            if (src_dtype == SVOL_F32)
-                hipLaunchKernelGGL(im2col_stem_kernel<float>, gs, dim3(256), sh_bytes, s, (const float*)x, sn, sh, sw, sc, (bf16_t*)cols,
-                                   ldcols, (int)H, (int)W, (int)C, (int)kh, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo);
-            else if (src_dtype == SVOL_BF16)
-                hipLaunchKernelGGL(im2col_stem_kernel<bf16_t>, gs, dim3(256), sh_bytes, s, (const bf16_t*)x, sn, sh, sw, sc, (bf16_t*)cols,
-                                   ldcols, (int)H, (int)W, (int)C, (int)kh, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo);
+#define SVOL_STEM(TS, TD)                                                                                                              \
+    hipLaunchKernelGGL((im2col_stem_kernel<TS, TD>), gs, dim3(256), sh_bytes, s, (const TS*)x, sn, sh, sw, sc, (TD*)cols, ldcols, (int)H, \
+                       (int)W, (int)C, (int)kh, (int)kw, (int)stride, (int)pad, (int)Ho, (int)Wo)
+            if (src_dtype == SVOL_F32 && dtype == SVOL_BF16) SVOL_STEM(float, bf16_t);
+            else if (src_dtype == SVOL_BF16 && dtype == SVOL_BF16) SVOL_STEM(bf16_t, bf16_t);
+            else if (src_dtype == SVOL_F32 && dtype == SVOL_F16) SVOL_STEM(float, f16_t);
+            else if (src_dtype == SVOL_F16 && dtype == SVOL_F16) SVOL_STEM(f16_t, f16_t);
             else return SVOL_E_INVALID;
+#undef SVOL_STEM
             SVOL_CHECK_LAUNCH();
             return SVOL_OK;
         }
@@ -193,6 +199,8 @@ extern "C" int svol_im2col(const void* x, int64_t sn, int64_t sh, int64_t sw, in
     if (src_dtype == SVOL_F32 && dtype == SVOL_BF16) SVOL_I2C(float, bf16_t);
     else if (src_dtype == SVOL_F32 && dtype == SVOL_F32) SVOL_I2C(float, float);
     else if (src_dtype == SVOL_BF16 && dtype == SVOL_BF16) SVOL_I2C(bf16_t, bf16_t);
+    else if (src_dtype == SVOL_F32 && dtype == SVOL_F16) SVOL_I2C(float, f16_t);
+    else if (src_dtype == SVOL_F16 && dtype == SVOL_F16) SVOL_I2C(f16_t, f16_t);
     else return SVOL_E_INVALID;
 #undef SVOL_I2C
     SVOL_CHECK_LAUNCH();
@@ -211,6 +219,9 @@ extern "C" int svol_maxpool_nhwc(const void* x, void* y, int64_t N, int64_t H, i
     if (dtype == SVOL_BF16)
         hipLaunchKernelGGL(maxpool_nhwc_kernel<bf16_t>, dim3(nblk(total)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (int)H, (int)W,
                            (int)C, (int)k, (int)stride, (int)pad, (int)Ho, (int)Wo, total);
+    else if (dtype == SVOL_F16)
+        hipLaunchKernelGGL(maxpool_nhwc_kernel<f16_t>, dim3(nblk(total)), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, (int)H, (int)W,
+                           (int)C, (int)k, (int)stride, (int)pad, (int)Ho, (int)Wo, total);
     else if (dtype == SVOL_F32)
         hipLaunchKernelGGL(maxpool_nhwc_kernel<float>, dim3(nblk(total)), dim3(256), 0, s, (const float*)x, (float*)y, (int)H, (int)W,
                            (int)C, (int)k, (int)stride, (int)pad, (int)Ho, (int)Wo, total);
@@ -226,6 +237,7 @@ extern "C" int svol_avgpool_nhwc(const void* x, float* y, int64_t N, int64_t HW,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 g((unsigned)((C + 255) / 256), (unsigned)N);
     if (dtype == SVOL_BF16) hipLaunchKernelGGL(avgpool_nhwc_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)x, y, (int)HW, (int)C);
+    else if (dtype == SVOL_F16) hipLaunchKernelGGL(avgpool_nhwc_kernel<f16_t>, g, dim3(256), 0, s, (const f16_t*)x, y, (int)HW, (int)C);
     else if (dtype == SVOL_F32) hipLaunchKernelGGL(avgpool_nhwc_kernel<float>, g, dim3(256), 0, s, (const float*)x, y, (int)HW, (int)C);
     else return SVOL_E_INVALID;
     SVOL_CHECK_LAUNCH();

@@ -11,7 +11,8 @@ frozen and the trainable path alike; a bf16 or fp32 head keeps the bf16 extracto
 form).  Its default stays frozen, unlike the ResNet's: the reference's
 ViT backbone cannot run as shipped (``device`` is undefined in ViTBackbone.forward, backbone.py:30), so no reference run
 trains it, and existing users of ``--backbone vit`` keep the frozen extractors; ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4), frozen by default,
-trained with the head when ``args.train_backbone`` is set (what the reference's train.py does).
+trained with the head when ``args.train_backbone`` is set (what the reference's train.py does); they run in ``args.compute_dtype``,
+fp16 included in both modes.
 """
 from __future__ import annotations
 
@@ -35,7 +36,9 @@ class FeatureBackbone(nn.Module):
 
 
 def build_backbone(args):
-    """Like backbone.py:116-152 this MUTATES args (input_vid_dim / input_skch_dim)."""
+    """Like backbone.py:116-152 this MUTATES args (input_vid_dim / input_skch_dim).  ``args.compute_dtype`` goes to the extractors: the
+    ViT pair takes fp16 and otherwise stays bf16 (module docstring); the ResNet pair takes it as it is — bf16, fp16 (frozen and
+    trainable; what the reference's apex amp runs) or fp32 (frozen only) — so a bf16 or fp32 head keeps the extractors it always had."""
     if args.backbone == 'features':
         args.input_vid_dim = getattr(args, 'input_vid_dim', 512)
         args.input_skch_dim = getattr(args, 'input_skch_dim', 512)

@@ -24,6 +24,13 @@ into the optimiser, and ``model.train()`` puts torchvision's BatchNorm into batc
 
 — plus max pooling with its argmax and the sketch branch's average pooling as Functions.  Activations bf16 / fp16 NHWC, statistics,
 parameters and parameter gradients fp32.
+
+compute_dtype: 'bf16' (default), 'fp16' (what the reference's apex amp runs; both modes) or 'fp32' (frozen mode only, explicit
+im2col + fp32 GEMM).  fp16 runs the same kernels with fp16 operands (v_mfma_*_f16 at bf16's rate, three more mantissa bits, five
+exponent bits).  Nothing clamps a forward activation: every convolution output before its BatchNorm, every unit's output and the
+loss-scaled dz must fit 65504 — they do by orders of magnitude on ImageNet-normalised pixels (profiles/resnet_fp16.md) — and the
+frozen path's folded weights are checked by refold().  Gradients reach the fp32 parameters through the same buckets as the head's,
+so FlatAdamW.loss_scale / DynamicLossScaler cover the backbone with nothing added.
 """
 from __future__ import annotations
 
@@ -33,7 +40,10 @@ from torch import nn
 from .. import ops, params, wgrad
 from ..ingest import FrameIngest, is_raw_frames
 
-_DTYPES = {'bf16': torch.bfloat16, 'fp32': torch.float32, torch.bfloat16: torch.bfloat16, torch.float32: torch.float32}
+_DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32,
+           torch.bfloat16: torch.bfloat16, torch.float16: torch.float16, torch.float32: torch.float32}
+_H16 = (torch.bfloat16, torch.float16)
+_NHWC_OUT = {torch.bfloat16: 'nhwc_bf16', torch.float16: 'nhwc_f16'}
 
 
 class BasicBlock(nn.Module):
@@ -53,7 +63,7 @@ class BasicBlock(nn.Module):
 
 def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype):
     """(W' [Cout, Kp] in `dtype`, shift [Cout] fp32): eval-mode BatchNorm folded into the convolution, K = kh*kw*Cin in
-    (ky, kx, c) order, zero-padded to a multiple of 32."""
+    (ky, kx, c) order, zero-padded to a multiple of 32.  The product W * gamma / sqrt(var + eps) is formed in fp32 and rounded once."""
     w = conv.weight.detach().float()
     scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
     shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
@@ -240,22 +250,37 @@ class ResNetExtractor(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     def refold(self):
-        """(re)build the folded compute-dtype weights; call after editing parameters in place."""
+        """(re)build the folded compute-dtype weights; call after editing parameters in place.  fp16: a folded weight that is not finite
+        after the cast (a BatchNorm channel with a tiny running variance scales its filter past 65504; bf16 has fp32's range and cannot
+        overflow there) raises a ValueError that names the unit — checked here, once per fold, not per step."""
         dt = self.compute_dtype
-        f = {'stem': _fold(getattr(self, '0'), getattr(self, '1'), dt), 'blocks': []}
+        units = []
+
+        def fold(name, conv, bn):
+            w, b = _fold(conv, bn, dt)
+            units.append((name, w))
+            return w, b
+        f = {'stem': fold('0', getattr(self, '0'), getattr(self, '1')), 'blocks': []}
         for li in range(self.n_layers):
-            for blk in getattr(self, str(4 + li)):
-                f['blocks'].append((blk.stride, blk.conv1.out_channels, _fold(blk.conv1, blk.bn1, dt), _fold(blk.conv2, blk.bn2, dt),
-                                    _fold(blk.downsample[0], blk.downsample[1], dt) if blk.downsample is not None else None))
+            for bi, blk in enumerate(getattr(self, str(4 + li))):
+                pre = f'{4 + li}.{bi}.'
+                f['blocks'].append((blk.stride, blk.conv1.out_channels, fold(pre + 'conv1', blk.conv1, blk.bn1), fold(pre + 'conv2', blk.conv2, blk.bn2),
+                                    fold(pre + 'downsample.0', blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
+        if dt == torch.float16:
+            finite = torch.stack([torch.isfinite(w).all() for _, w in units]).tolist()   # one host read for the whole fold
+            bad = [name for (name, _), ok in zip(units, finite) if not ok]
+            if bad:
+                raise ValueError(f'ResNetExtractor(compute_dtype="fp16"): the BatchNorm-folded weights of {", ".join(bad)} exceed fp16\'s range '
+                                 '(65504): a channel with a tiny running variance; use compute_dtype="bf16" for this checkpoint')
         self._folded = f
         return f
 
     def forward(self, pixel_values, nhwc=False):
         """pixel_values [n,3,H,W] fp32 (normalised as for torchvision's ImageNet weights) -> tokens [n, h*w, C] in the compute
         dtype (row-major over (h, w): the order backbone.py:85-87 flattens to), or [n, C] fp32 with ``avgpool``.
-        ``nhwc=True``: pixel_values is [n,H,W,3], contiguous, already in the compute dtype — what FrameIngest(out='nhwc_bf16') writes;
-        the stem reads it through svol_im2col's strides, and its im2col matrix has the bits of the fp32 route (one rounding to bf16
-        either way)."""
+        ``nhwc=True``: pixel_values is [n,H,W,3], contiguous, already in the compute dtype — what FrameIngest(out='nhwc_bf16' /
+        'nhwc_f16') writes; the stem reads it through svol_im2col's strides, and its im2col matrix has the bits of the fp32 route
+        (one rounding to the 16-bit type either way)."""
         if not pixel_values.is_cuda:
             raise RuntimeError('svol_amd ResNetExtractor runs on the MI355X HIP kernels only (no CPU path)')
         if nhwc and (pixel_values.dtype != self.compute_dtype or not pixel_values.is_contiguous()):
@@ -271,8 +296,9 @@ class ResNetExtractor(nn.Module):
     def _forward_train(self, pixel_values, nhwc=False):
         """batch-statistics BatchNorm, autograd through every unit (module docstring); folded weights are invalidated."""
         dt = self.compute_dtype
-        if dt != torch.bfloat16:
-            raise NotImplementedError('the training path of the ResNet extractor keeps its activations in bf16 (compute_dtype="bf16")')
+        if dt not in _H16:
+            raise NotImplementedError('the training path of the ResNet extractor keeps its activations in a 16-bit type '
+                                      '(compute_dtype="bf16" or "fp16")')
         self._folded = None
         x = pixel_values if nhwc else pixel_values.float().contiguous()
         n, c, H, W, _ = _pixel_geom(x, nhwc)
@@ -331,15 +357,15 @@ class ResNetBackbone(nn.Module):
 
     Raw frames — uint8 [N,T,H,W,3] (sketch [N,1,H,W,3]), or a list of N tensors [T,H_b,W_b,3] of any sizes — go through the
     FrameIngest this backbone owns (svol_dataset.py:218-229: Resize((224,224)) + ToTensor(); ``pixel_preset`` overrides
-    'totensor'): with bf16 extractors it writes the 16-bit NHWC image the stem's im2col reads directly.  Float inputs take exactly
-    the path they always took."""
+    'totensor'): with two extractors of one 16-bit type (bf16 or fp16) it writes the NHWC image in that type, which the stem's
+    im2col reads directly.  Float inputs take exactly the path they always took."""
 
     def __init__(self, video_backbone, sketch_backbone, pixel_preset=None):
         super().__init__()
         self.video_backbone = video_backbone
         self.sketch_backbone = sketch_backbone
-        self.nhwc = video_backbone.compute_dtype == torch.bfloat16 and sketch_backbone.compute_dtype == torch.bfloat16
-        self.ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out='nhwc_bf16' if self.nhwc else 'nchw_f32')
+        self.nhwc = video_backbone.compute_dtype in _H16 and sketch_backbone.compute_dtype == video_backbone.compute_dtype
+        self.ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out=_NHWC_OUT[video_backbone.compute_dtype] if self.nhwc else 'nchw_f32')
 
     def forward(self, sketch_batch, video_batch):
         if is_raw_frames(sketch_batch) or is_raw_frames(video_batch):

@@ -461,10 +461,10 @@ def ingest_resize(src, xtab, kx, ytab, ky, lut, flip, out, out_strides, OH, OW):
 
 def conv_nhwc(x, w, bias, act, N, H, W, C, kh, kw, stride, pad, residual=None):
     """convolution of an NHWC activation [N*H*W, C] with folded weights w [Cout, kh*kw*C (+pad)] -> (y [N*Ho*Wo, Cout], Ho, Wo).
-    The implicit-GEMM kernel when the shape fits it (bf16, C % 32 == 0), else im2col + gemm_nt."""
+    The implicit-GEMM kernel when the shape fits it (bf16 or fp16, C % 32 == 0), else im2col + gemm_nt."""
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     Cout = w.shape[0]
-    if x.dtype == torch.bfloat16 and C % 32 == 0 and _CONV_IMPLICIT:
+    if x.dtype in (torch.bfloat16, torch.float16) and C % 32 == 0 and _CONV_IMPLICIT:
         y = torch.empty((N * Ho * Wo, Cout), dtype=x.dtype, device=x.device)
         rc = _lib.lib().svol_conv_nhwc(_ptr(x), _ptr(w), w.stride(0), _ptr(y), _ptr(bias), act, _ptr(residual), N, H, W, C, Cout, kh,
                                        kw, stride, pad, _dt(x), _stream())
