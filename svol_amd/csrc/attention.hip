@@ -21,6 +21,7 @@
 //
 // Element types: this file's generic template serves f32 (v_mfma_f32_32x32x2_f32, exact fp32 — the parity
 // mode); bf16 (v_mfma_f32_32x32x16_bf16) is dispatched to the tuned kernels of attention_bf16.hip.
+// Head widths 32 < d_h <= 64 (two d-tiles), all three element types, go to attention_wide.hip.
 // Softmax runs in the log2 domain with fp32 statistics; exp via v_exp_f32.
 #include "attn_call.h"
 
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
 int check_common(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int dtype) {
     if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || dh <= 0) return SVOL_E_INVALID;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
-    if (dh > 32 || dh % 8) return SVOL_E_UNSUPPORTED;
+    if (dh > 64 || dh % 8) return SVOL_E_UNSUPPORTED;
     if (B > 65535 || H > 65535 || Lq > (1 << 24) || Lk > (1 << 24)) return SVOL_E_UNSUPPORTED;
     return SVOL_OK;
 }
@@ -515,6 +516,7 @@ extern "C" {
 
 int64_t svol_attn_ws_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh) {
     if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || dh <= 0 || B > (1 << 24) || Lq > (1 << 24) || Lk > (1 << 24)) return 0;
+    if (dh > 32) return 0;   // the wide kernels (attention_wide.hip) use no workspace
     return 4 * svol_attn_ws_floats_bf16((int)B, (int)H, (int)Lq, (int)Lk, (int)dh);
 }
 
@@ -528,6 +530,7 @@ int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
     c.drop_p = dropout_p; c.drop_seed = seed; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, false, B, H, Lq, Lk, dh, dtype)) return rc;
+    if (dh > 32) return svol_attn_wide_fwd_launch(c, dtype);
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_fwd_bf16_launch : svol_attn_fwd_f16_launch)(c);
     AttnArgs p{};
     attn_fill(p, c);
@@ -555,6 +558,7 @@ static int attn_bwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk,
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
     c.drop_p = drop_p; c.drop_seed = drop_seed; c.flags = flags; c.ev_prep = ev_prep; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, true, B, H, Lq, Lk, dh, dtype)) return rc;
+    if (dh > 32) return svol_attn_wide_bwd_launch(c, dtype);   // (no dQ image: SVOL_ATTN_DQ_PREZEROED means nothing there)
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_bwd_bf16_launch : svol_attn_bwd_f16_launch)(c);
     AttnArgs p{};
     attn_fill(p, c);
@@ -587,7 +591,7 @@ int svol_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, con
                          scale, q_premul, ws, ws_bytes, 0.f, 0, dtype, stream, flags, ev_prep);
 }
 int64_t svol_attn_bwd_sp_image_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int64_t ws_bytes, int dtype) {
-    if (!svol_is16(dtype) || check_common(B, H, Lq, Lk, dh, dtype)) return 0;
+    if (!svol_is16(dtype) || dh > 32 || check_common(B, H, Lq, Lk, dh, dtype)) return 0;
     return (dtype == SVOL_BF16 ? svol_attn_sp_image_bytes_bf16 : svol_attn_sp_image_bytes_f16)((int)B, (int)H, (int)Lq, (int)Lk, (int)dh,
                                                                                               ws_bytes);
 }
@@ -596,6 +600,7 @@ int svol_attn_bwd_zero_ws(void* ws, int64_t ws_bytes, int64_t B, int64_t H, int6
     if (!svol_is16(dtype)) return SVOL_E_UNSUPPORTED;
     const int rc = check_common(B, H, Lq, Lk, dh, dtype);
     if (rc) return rc;
+    if (dh > 32) return SVOL_E_UNSUPPORTED;   // no single-pass plan, no dQ image at the wide head widths
     return (dtype == SVOL_BF16 ? svol_attn_sp_zero_bf16_launch : svol_attn_sp_zero_f16_launch)(
         static_cast<float*>(ws), ws_bytes, (int)B, (int)H, (int)Lq, (int)Lk, (int)dh, reinterpret_cast<hipStream_t>(stream));
 }
