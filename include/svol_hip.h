@@ -246,8 +246,9 @@ int svol_act_bwd(const void* dy, const void* aux, void* dpre, int act, int64_t n
  * GEMMs consume (y, and ypos = y + pos).  Any of y32 / y may be NULL (not both); ypos/pos go together.
  * pos has `pos_rows` rows and is indexed row % pos_rows so a [N,d] query embedding broadcasts over
  * the batch.  Dropout (p, seed) is a stateless counter-based mask applied to LN's output; the effective
- * seed is seed + *seed_offset_dev (device int64, may be NULL) so that a captured hipGraph draws a fresh
- * mask on every replay.  mean/rstd
+ * seed is seed + (*seed_offset_dev << 8) (device int64, may be NULL; the stride of the heads' host-side step) so that
+ * a captured hipGraph draws a fresh mask on every replay; the stand-alone and attention dropouts have the same rule at their
+ * own stride (svol_dropout_sd below: seed + (seed_step_dev[0] << 12)).  mean/rstd
  * fp32 [M] are saved for backward.  nn.LayerNorm + nn.Dropout of svanet.py:168-178; post-norms
  * cross_modal_transformer.py:127-158. */
 int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float* beta, float* y32, void* y,
@@ -271,6 +272,14 @@ int svol_dropout(const void* x, void* y, int64_t n, int64_t row_len, float p, ui
 /* out32 = res32 + t32 * keep(seed, r, k): the residual dropouts src + dropout1(src2) (:171,:177,:232-247) on the fp32 stream;
  * out32 may alias t32. */
 int svol_dropout_add(const float* t32, const float* res32, float* out32, int64_t n, int64_t row_len, float p, uint64_t seed, void* stream);
+/* The same with a device-side step counter, for a captured hipGraph whose replays must draw fresh masks (as svol_layernorm_fwd's
+ * seed_offset_dev, at the enc/dec Transformer's stride): the effective seed is seed + ((uint64_t)seed_step_dev[0] << 12), the host's
+ * (step << 12) of modeling/transformer.py.  seed_step_dev (device int64) is only read, once per kernel; NULL, or a counter of 0, is
+ * bit for bit the entry without the suffix.  Also svol_attn_fwd_dropout_sd / svol_attn_bwd_dropout_sd below. */
+int svol_dropout_sd(const void* x, void* y, int64_t n, int64_t row_len, float p, uint64_t seed, const int64_t* seed_step_dev, int dtype,
+                    void* stream);
+int svol_dropout_add_sd(const float* t32, const float* res32, float* out32, int64_t n, int64_t row_len, float p, uint64_t seed,
+                        const int64_t* seed_step_dev, void* stream);
 
 /* ---- sine positional encoding (position_encoding.py:51-71) -------------- */
 /* mask [B,L] float (1 = valid) -> pos [B,L,D] (dtype). */
@@ -347,6 +356,17 @@ int svol_attn_bwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk
                           void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H,
                           int64_t Lq, int64_t Lk, int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes,
                           float dropout_p, uint64_t seed, int dtype, void* stream);
+/* The two with a device-side step counter (svol_dropout_sd's rule: effective seed = seed + (seed_step_dev[0] << 12); NULL or a counter
+ * of 0 is bit for bit the entry above).  Forward and backward of one step must see the same counter value. */
+int svol_attn_fwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                             int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk,
+                             int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed,
+                             const int64_t* seed_step_dev, int dtype, void* stream);
+int svol_attn_bwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                             int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta, const float* kbias,
+                             void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H,
+                             int64_t Lq, int64_t Lk, int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes,
+                             float dropout_p, uint64_t seed, const int64_t* seed_step_dev, int dtype, void* stream);
 
 /* ---- sketch->video gate (cross_modal_transformer.py:122-127) ------------
  * Only the head-averaged attention weights of the 1-query MHA are used by the reference, so the

@@ -115,6 +115,13 @@ SIGNATURES = {
                               _i64, _i64, _i64, _i64, _i64, _f32, _f32, _p, _i64, _f32, _u64, _int, _p],
     'svol_dropout': [_p, _p, _i64, _i64, _f32, _u64, _int, _p],
     'svol_dropout_add': [_p, _p, _p, _i64, _i64, _f32, _u64, _p],
+    # the four with a device-side step counter after the seed (graph replays draw fresh masks)
+    'svol_attn_fwd_dropout_sd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _p, _i64,
+                                 _f32, _u64, _p, _int, _p],
+    'svol_attn_bwd_dropout_sd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64,
+                                 _i64, _i64, _i64, _i64, _i64, _f32, _f32, _p, _i64, _f32, _u64, _p, _int, _p],
+    'svol_dropout_sd': [_p, _p, _i64, _i64, _f32, _u64, _p, _int, _p],
+    'svol_dropout_add_sd': [_p, _p, _p, _i64, _i64, _f32, _u64, _p, _p],
     'svol_gate_fwd': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p],
     'svol_gate_bwd': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int,
                       _p],

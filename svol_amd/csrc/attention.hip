@@ -182,6 +182,7 @@ struct AttnArgs {
     // ((b*H + h)*Lq + q)*Lk + key — the row sums / lse stay those of the undropped softmax; backward regenerates the mask
     float drop_p, drop_inv;
     uint64_t drop_seed;
+    const int64_t* drop_step;   // device step counter (drop_seed_at), or null
 };
 
 // keep-mask scale of score element (row, key); row = (b*H + h)*Lq + q
@@ -203,6 +204,7 @@ template <typename T> struct Smem {
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[Smem<T>::NAT + Smem<T>::TR + 64 * 4];
     char* sK = smem;
     char* sVt = smem + Smem<T>::NAT;
@@ -269,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) O[i] *= alpha;
             if (p.drop_p > 0.f) {
-                const uint32_t rm = drop_row(drop_seed32(p.drop_seed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
+                const uint32_t rm = drop_row(drop_seed32(dseed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
                 const uint32_t thr = drop_thr16(p.drop_p);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -318,6 +320,7 @@ __global__ void attn_delta_kernel(AttnArgs p) {
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[2 * Smem<T>::NAT + Smem<T>::TR + 64 * 4];
     char* sK = smem;
     char* sV = smem + Smem<T>::NAT;
@@ -374,7 +377,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
                     const float pe = __builtin_amdgcn_exp2f(S[4 * g + e] * sc + bb[e] - lse);
                     float dpe = dP[4 * g + e];
                     if (p.drop_p > 0.f)
-                        dpe *= attn_drop(p.drop_seed, (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)),
+                        dpe *= attn_drop(dseed, (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)),
                                          kt + sub * 32 + 8 * g + 4 * h + e, p.drop_p, p.drop_inv);
                     S[4 * g + e] = pe * (dpe - dl) * p.scale;
                 }
@@ -390,6 +393,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[2 * Smem<T>::NAT + 2 * Smem<T>::TR + 128 * 4];
     char* sQ = smem;
     char* sdO = smem + Smem<T>::NAT;
@@ -453,7 +457,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int qi = min(qt + sub * 32 + 8 * g + 4 * h + e, p.Lq - 1);
-                        MS[4 * g + e] = attn_drop(p.drop_seed, (((uint64_t)b * p.H + hh) * p.Lq + qi), kvalid ? krow : 0,
+                        MS[4 * g + e] = attn_drop(dseed, (((uint64_t)b * p.H + hh) * p.Lq + qi), kvalid ? krow : 0,
                                                   p.drop_p, p.drop_inv);
                     }
             }
@@ -520,15 +524,15 @@ int64_t svol_attn_ws_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t
     return 4 * svol_attn_ws_floats_bf16((int)B, (int)H, (int)Lq, (int)Lk, (int)dh);
 }
 
-int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                          int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
-                          float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed, int dtype,
-                          void* stream) {
+int svol_attn_fwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                             int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
+                             float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed,
+                             const int64_t* seed_step_dev, int dtype, void* stream) {
     AttnCall c{};
     c.q = q; c.k = k; c.v = v; c.out_o = o; c.lse2 = lse2; c.kbias = kbias;
     c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo;
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
-    c.drop_p = dropout_p; c.drop_seed = seed; c.stream = reinterpret_cast<hipStream_t>(stream);
+    c.drop_p = dropout_p; c.drop_seed = seed; c.drop_step = seed_step_dev; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, false, B, H, Lq, Lk, dh, dtype)) return rc;
     if (dh > 32) return svol_attn_wide_fwd_launch(c, dtype);
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_fwd_bf16_launch : svol_attn_fwd_f16_launch)(c);
@@ -538,6 +542,13 @@ int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk
     hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), 0, c.stream, p);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
+}
+int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                          int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
+                          float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed, int dtype,
+                          void* stream) {
+    return svol_attn_fwd_dropout_sd(q, ldq, k, ldk, v, ldv, o, ldo, lse2, kbias, B, H, Lq, Lk, dh, scale, q_premul, ws, ws_bytes,
+                                    dropout_p, seed, nullptr, dtype, stream);
 }
 int svol_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
                   int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
@@ -550,13 +561,13 @@ static int attn_bwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk,
                          int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta, const float* kbias, void* dq,
                          int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H, int64_t Lq, int64_t Lk,
                          int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, float drop_p, uint64_t drop_seed,
-                         int dtype, void* stream, int flags = 0, void* ev_prep = nullptr) {
+                         const int64_t* drop_step, int dtype, void* stream, int flags = 0, void* ev_prep = nullptr) {
     AttnCall c{};
     c.q = q; c.k = k; c.v = v; c.o = o; c.d_o = d_o; c.lse2 = const_cast<float*>(lse2); c.delta = delta; c.kbias = kbias;
     c.dq = dq; c.dk = dk; c.dv = dv;
     c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo; c.lddo = lddo; c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
-    c.drop_p = drop_p; c.drop_seed = drop_seed; c.flags = flags; c.ev_prep = ev_prep; c.stream = reinterpret_cast<hipStream_t>(stream);
+    c.drop_p = drop_p; c.drop_seed = drop_seed; c.drop_step = drop_step; c.flags = flags; c.ev_prep = ev_prep; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, true, B, H, Lq, Lk, dh, dtype)) return rc;
     if (dh > 32) return svol_attn_wide_bwd_launch(c, dtype);   // (no dQ image: SVOL_ATTN_DQ_PREZEROED means nothing there)
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_bwd_bf16_launch : svol_attn_bwd_f16_launch)(c);
@@ -579,7 +590,7 @@ int svol_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const 
                   int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H, int64_t Lq, int64_t Lk,
                   int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, int dtype, void* stream) {
     return attn_bwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse2, delta, kbias, dq, lddq, dk, lddk, dv, lddv, B, H, Lq, Lk, dh,
-                         scale, q_premul, ws, ws_bytes, 0.f, 0, dtype, stream);
+                         scale, q_premul, ws, ws_bytes, 0.f, 0, nullptr, dtype, stream);
 }
 int svol_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
                      int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta, const float* kbias, void* dq,
@@ -588,7 +599,7 @@ int svol_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, con
                      void* stream) {
     if (flags & ~SVOL_ATTN_DQ_PREZEROED) return SVOL_E_INVALID;
     return attn_bwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse2, delta, kbias, dq, lddq, dk, lddk, dv, lddv, B, H, Lq, Lk, dh,
-                         scale, q_premul, ws, ws_bytes, 0.f, 0, dtype, stream, flags, ev_prep);
+                         scale, q_premul, ws, ws_bytes, 0.f, 0, nullptr, dtype, stream, flags, ev_prep);
 }
 int64_t svol_attn_bwd_sp_image_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int64_t ws_bytes, int dtype) {
     if (!svol_is16(dtype) || dh > 32 || check_common(B, H, Lq, Lk, dh, dtype)) return 0;
@@ -610,7 +621,15 @@ int svol_attn_bwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk
                           int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p, uint64_t seed,
                           int dtype, void* stream) {
     return attn_bwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse2, delta, kbias, dq, lddq, dk, lddk, dv, lddv, B, H, Lq, Lk, dh,
-                         scale, q_premul, ws, ws_bytes, dropout_p, seed, dtype, stream);
+                         scale, q_premul, ws, ws_bytes, dropout_p, seed, nullptr, dtype, stream);
+}
+int svol_attn_bwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                             int64_t ldo, const void* d_o, int64_t lddo, const float* lse2, float* delta, const float* kbias,
+                             void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t B, int64_t H, int64_t Lq,
+                             int64_t Lk, int64_t dh, float scale, float q_premul, void* ws, int64_t ws_bytes, float dropout_p,
+                             uint64_t seed, const int64_t* seed_step_dev, int dtype, void* stream) {
+    return attn_bwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse2, delta, kbias, dq, lddq, dk, lddk, dv, lddv, B, H, Lq, Lk, dh,
+                         scale, q_premul, ws, ws_bytes, dropout_p, seed, seed_step_dev, dtype, stream);
 }
 
 }  // extern "C"

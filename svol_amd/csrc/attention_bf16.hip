@@ -48,6 +48,7 @@ struct Args {
     // attention-probability dropout (general kernels only; see attention.hip AttnArgs): keep mask of ((b*H + h)*Lq + q)*Lk + key
     float drop_p, drop_inv;
     uint64_t drop_seed;
+    const int64_t* drop_step;   // device step counter (drop_seed_at), or null
     int dq_rot;                   // unused (once the switch to the rotated dQ schedule); kept so the kernel arguments keep their layout
 };
 __device__ __forceinline__ float attn_drop(uint64_t seed, uint64_t row, int key, float p, float inv) {
@@ -223,6 +224,7 @@ __device__ __forceinline__ void stage_bias(float* sb, const float* kb, int row0,
 // forward: lane = queries (32 per wave, 128 per workgroup), tiles over keys
 template <bool MASKED>
 __global__ __launch_bounds__(256, 2) void attn_fwd_bf16(Args p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[4 * IMG + 2 * KT * 4];
     char* sK = smem;                 // [2][IMG]
     char* sV = smem + 2 * IMG;       // [2][IMG]
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16(Args p) {
             }
         l += (ls[0] + ls[1]) + (ls[2] + ls[3]);
         if (p.drop_p > 0.f) {   // row sums stay those of the undropped softmax; only what feeds P V is masked
-            const uint32_t rm = drop_row(drop_seed32(p.drop_seed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
+            const uint32_t rm = drop_row(drop_seed32(dseed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
             const uint32_t thr = drop_thr16(p.drop_p);
 #pragma unroll
             for (int sub = 0; sub < 4; ++sub)
@@ -458,6 +460,7 @@ __global__ void attn_dq_finish_bf16(Args p) {
 // dQ: lane = queries, tiles over keys.  dQ^T += K^T (P * (dP - delta)); scaled by 1/sqrt(dh) at the end.
 template <bool MASKED>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16(Args p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[4 * IMG + 2 * KT * 4];
     char* sK = smem;
     char* sV = smem + 2 * IMG;
@@ -511,7 +514,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16(Args p) {
             read_rows(a, vimg, sub * 32 + r, h);
             f32x16 dP = mma_first(a, dob);
             if (p.drop_p > 0.f) {
-                const uint32_t rm = drop_row(drop_seed32(p.drop_seed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
+                const uint32_t rm = drop_row(drop_seed32(dseed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
                 const uint32_t thr = drop_thr16(p.drop_p);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -572,6 +575,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16(Args p) {
 // dK, dV: lane = keys, tiles over queries.
 template <bool KBIAS>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_bf16(Args p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[4 * IMG + 4 * KT * 4];
     char* sQ = smem;
     char* sdO = smem + 2 * IMG;
@@ -650,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_bf16(Args p) {
                 // other key sits in the neighbouring lane (krow = ... + lane % 32): of two consecutive rows the even lane draws the
                 // first, the odd lane the second, one DPP swap hands each the other's word (a quarter of the integer multiplies of
                 // the per-element form: 20 -> ~17 ms of mask generation per enc/dec training step).
-                const uint32_t s0 = drop_seed32(p.drop_seed), thr = drop_thr16(p.drop_p), odd = (uint32_t)lane & 1u;
+                const uint32_t s0 = drop_seed32(dseed), thr = drop_thr16(p.drop_p), odd = (uint32_t)lane & 1u;
                 const uint64_t rbase = ((uint64_t)b * p.H + hh) * p.Lq;
                 const bool rows32 = rbase + (uint64_t)p.Lq <= 0xffffffffull;   // (uniform) the row index fits 32 bits: one multiply per row
 #pragma unroll

@@ -205,6 +205,7 @@ struct WideArgs {
     // that feed P V; row sums / lse2 stay those of the undropped softmax; both backward passes regenerate it
     float drop_p, drop_inv;
     uint64_t drop_seed;
+    const int64_t* drop_step;   // device step counter (drop_seed_at), or null
 };
 
 // keep-mask scale of score element (row, key); row = (b*H + h)*Lq + q
@@ -215,6 +216,7 @@ __device__ __forceinline__ float attn_drop(uint64_t seed, uint64_t row, int key,
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(WideArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[WT<T>::NAT + WT<T>::TR + 64 * 4];
     char* sK = smem;
     char* sVt = smem + WT<T>::NAT;
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(WideArgs p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { O0[i] *= alpha; O1[i] *= alpha; }
             if (p.drop_p > 0.f) {
-                const uint32_t rm = drop_row(drop_seed32(p.drop_seed), drow);
+                const uint32_t rm = drop_row(drop_seed32(dseed), drow);
                 const uint32_t thr = drop_thr16(p.drop_p);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -331,6 +333,7 @@ __global__ __launch_bounds__(256) void attn_wide_delta_kernel(WideArgs p) {
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_wide_bwd_dq_kernel(WideArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[2 * WT<T>::NAT + WT<T>::TR + 64 * 4];
     char* sK = smem;
     char* sV = smem + WT<T>::NAT;
@@ -389,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_bwd_dq_kernel(WideArgs p) {
                 for (int e = 0; e < 4; ++e) {
                     const float pe = __builtin_amdgcn_exp2f(S[4 * g + e] * sc + bb[e] - lse);
                     float dpe = dP[4 * g + e];
-                    if (p.drop_p > 0.f) dpe *= attn_drop(p.drop_seed, drow, kt + sub * 32 + 8 * g + 4 * h + e, p.drop_p, p.drop_inv);
+                    if (p.drop_p > 0.f) dpe *= attn_drop(dseed, drow, kt + sub * 32 + 8 * g + 4 * h + e, p.drop_p, p.drop_inv);
                     S[4 * g + e] = pe * (dpe - dl) * p.scale;
                 }
             }
@@ -404,6 +407,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_bwd_dq_kernel(WideArgs p) {
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_wide_bwd_dkdv_kernel(WideArgs p) {
+    const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
     __shared__ __attribute__((aligned(16))) char smem[2 * WT<T>::NAT + 2 * WT<T>::TR + 128 * 4];
     char* sQ = smem;
     char* sdO = smem + WT<T>::NAT;
@@ -469,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_bwd_dkdv_kernel(WideArgs p) 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int qi = min(qt + sub * 32 + 8 * g + 4 * h + e, p.Lq - 1);
-                        const float ms = attn_drop(p.drop_seed, ((uint64_t)b * p.H + hh) * p.Lq + qi, kvalid ? krow : 0, p.drop_p, p.drop_inv);
+                        const float ms = attn_drop(dseed, ((uint64_t)b * p.H + hh) * p.Lq + qi, kvalid ? krow : 0, p.drop_p, p.drop_inv);
                         Pd[4 * g + e] = S[4 * g + e] * ms;
                         dP[4 * g + e] *= ms;
                     }

@@ -14,6 +14,7 @@ struct AttnCall {
     int B, H, Lq, Lk, dh;
     float scale, premul, drop_p;
     uint64_t drop_seed;
+    const int64_t* drop_step;   // device step counter of the *_sd entries (drop_seed_at, common.h), or null
     float* ws;   // scratch of ws_bytes (svol_attn_ws_bytes), or null
     int64_t ws_bytes;
     int flags;       // SVOL_ATTN_* (backward)
@@ -27,7 +28,7 @@ template <typename A> static inline void attn_fill(A& p, const AttnCall& c) {
     p.kbias = c.kbias; p.lse2 = c.lse2; p.delta = c.delta;
     p.ldq = c.ldq; p.ldk = c.ldk; p.ldv = c.ldv; p.ldo = c.ldo; p.lddo = c.lddo; p.lddq = c.lddq; p.lddk = c.lddk; p.lddv = c.lddv;
     p.B = c.B; p.H = c.H; p.Lq = c.Lq; p.Lk = c.Lk; p.dh = c.dh; p.scale = c.scale; p.premul = c.premul;
-    p.drop_p = c.drop_p; p.drop_inv = c.drop_p > 0.f ? 1.f / (1.f - c.drop_p) : 1.f; p.drop_seed = c.drop_seed;
+    p.drop_p = c.drop_p; p.drop_inv = c.drop_p > 0.f ? 1.f / (1.f - c.drop_p) : 1.f; p.drop_seed = c.drop_seed; p.drop_step = c.drop_step;
 }
 
 // attention_bf16.hip's entry points, declared once for both of its builds (an fp16 build sees the bf16 names through common.h's

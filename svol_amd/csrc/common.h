@@ -258,6 +258,11 @@ __device__ __forceinline__ uint32_t hash_u64(uint64_t x) {
 // columns pays the two multiplies of a 32-bit finaliser (lowbias32): 16 mask bits per element.  Keep rate 0.9000 +- 2e-4 and neighbour / lag correlations within noise on
 // 8M samples; tests/gpu_checks.py::check_dropout_mask pins the function against a numpy twin.
 __device__ __forceinline__ uint32_t drop_seed32(uint64_t seed) { return hash_u64(seed * 0x9E3779B97F4A7C15ULL + 0x632BE59BD9B4E019ULL); }
+// the seed of a launch whose step counter lives on the device (the *_sd entries): seed + (step[0] << 12), the stride of the enc/dec
+// Transformer's host-side step; null = the host seed as it is.  A uniform load: call it once per kernel, before the loops.
+__device__ __forceinline__ uint64_t drop_seed_at(uint64_t seed, const int64_t* __restrict__ step) {
+    return seed + (step ? ((uint64_t)step[0] << 12) : 0ull);
+}
 __device__ __forceinline__ uint32_t drop_row(uint32_t s0, uint64_t r) {
     return s0 ^ ((uint32_t)r * 0x9E3779B1u) ^ ((uint32_t)(r >> 32) * 0x7F4A7C15u);
 }

@@ -258,8 +258,8 @@ __global__ __launch_bounds__(256) void posenc_kernel(const float* __restrict__ m
 // the same mask from (seed, row, column).  A thread walks along a row chunk: the row's share of the hash is computed once per chunk.
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, int64_t row_len, float p,
-                                                      float inv_keep, uint64_t seed) {
-    const uint32_t s0 = drop_seed32(seed);
+                                                      float inv_keep, uint64_t seed, const int64_t* __restrict__ step) {
+    const uint32_t s0 = drop_seed32(drop_seed_at(seed, step));
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     for (; i < n; i += stride) {
@@ -276,8 +276,8 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
 }
 // (t, res and out may alias — ops.dropout_add runs in place on t: no __restrict__)
 __global__ __launch_bounds__(256) void dropout_add_kernel(const float* t, const float* res, float* out, int64_t n, int64_t row_len, float p,
-                                                          float inv_keep, uint64_t seed) {
-    const uint32_t s0 = drop_seed32(seed);
+                                                          float inv_keep, uint64_t seed, const int64_t* __restrict__ step) {
+    const uint32_t s0 = drop_seed32(drop_seed_at(seed, step));
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     for (; i < n; i += stride) {
@@ -379,30 +379,39 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     return SVOL_OK;
 }
 
-int svol_dropout(const void* x, void* y, int64_t n, int64_t row_len, float p, uint64_t seed, int dtype, void* stream) {
+int svol_dropout_sd(const void* x, void* y, int64_t n, int64_t row_len, float p, uint64_t seed, const int64_t* seed_step_dev, int dtype,
+                    void* stream) {
     if (!x || !y || n < 0 || row_len <= 0 || row_len > 0xffffffffll || !(p >= 0.f && p < 1.f)) return SVOL_E_INVALID;
     if (n == 0) return SVOL_OK;
     const float inv = 1.f / (1.f - p);
     int64_t g = (n + 1023) / 1024;
     if (g > 8192) g = 8192;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == SVOL_F32) hipLaunchKernelGGL(dropout_kernel<float>, dim3((unsigned)g), dim3(256), 0, s, (const float*)x, (float*)y, n, row_len, p, inv, seed);
-    else if (dtype == SVOL_BF16) hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3((unsigned)g), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, n, row_len, p, inv, seed);
-    else if (dtype == SVOL_F16) hipLaunchKernelGGL(dropout_kernel<f16_t>, dim3((unsigned)g), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, n, row_len, p, inv, seed);
+    if (dtype == SVOL_F32) hipLaunchKernelGGL(dropout_kernel<float>, dim3((unsigned)g), dim3(256), 0, s, (const float*)x, (float*)y, n, row_len, p, inv, seed, seed_step_dev);
+    else if (dtype == SVOL_BF16) hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3((unsigned)g), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, n, row_len, p, inv, seed, seed_step_dev);
+    else if (dtype == SVOL_F16) hipLaunchKernelGGL(dropout_kernel<f16_t>, dim3((unsigned)g), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, n, row_len, p, inv, seed, seed_step_dev);
     else return SVOL_E_INVALID;
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
 
-int svol_dropout_add(const float* t32, const float* res32, float* out32, int64_t n, int64_t row_len, float p, uint64_t seed, void* stream) {
+int svol_dropout(const void* x, void* y, int64_t n, int64_t row_len, float p, uint64_t seed, int dtype, void* stream) {
+    return svol_dropout_sd(x, y, n, row_len, p, seed, nullptr, dtype, stream);
+}
+
+int svol_dropout_add_sd(const float* t32, const float* res32, float* out32, int64_t n, int64_t row_len, float p, uint64_t seed,
+                        const int64_t* seed_step_dev, void* stream) {
     if (!t32 || !res32 || !out32 || n < 0 || row_len <= 0 || row_len > 0xffffffffll || !(p >= 0.f && p < 1.f)) return SVOL_E_INVALID;
     if (n == 0) return SVOL_OK;
     int64_t g = (n + 1023) / 1024;
     if (g > 8192) g = 8192;
     hipLaunchKernelGGL(dropout_add_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), t32, res32, out32, n,
-                       row_len, p, 1.f / (1.f - p), seed);
+                       row_len, p, 1.f / (1.f - p), seed, seed_step_dev);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
+}
+int svol_dropout_add(const float* t32, const float* res32, float* out32, int64_t n, int64_t row_len, float p, uint64_t seed, void* stream) {
+    return svol_dropout_add_sd(t32, res32, out32, n, row_len, p, seed, nullptr, stream);
 }
 
 int svol_posenc_sine(const float* mask, void* pos, int64_t B, int64_t L, int64_t D, int dtype, void* stream) {

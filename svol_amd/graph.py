@@ -8,9 +8,17 @@ every decoder layer, losses, backward, fused AdamW — is captured ONCE and repl
 
 Per step the host only (1) copies the new inputs into the static input tensors, (2) flattens the new
 targets into the fixed-capacity static target buffers (`StaticPackedTargets.load`) and (3) replays.
-The SVANet input-projection dropout masks stay fresh because their seed is offset by a device-side step
-counter that the graph itself increments.  The enc/dec Transformer's attention / residual / FFN dropouts
+The dropout masks stay fresh because their seeds are offset by ONE device-side step counter that the graph itself
+increments: the input projections of every head (svol_layernorm_fwd's seed_offset_dev) and, for the heads on the enc/dec
+Transformer (svanet_variants' three modes, SketchDETR), the attention / residual / FFN dropouts (the *_sd entries of svol_hip.h,
+Transformer.step_dev).  A replay draws the masks of the eager step with the same step number, and Transformer.dropout_state()
+folds the counter in, so a checkpoint continues the mask stream in either direction.  Without a counter the enc/dec dropouts
 take their seeds from the host and REFUSE capture in training mode (svol_amd/modeling/transformer.py::_drop).
+The counter is read by a step's forward AND its backward (which regenerates the masks): it moves once per step, before the forward.
+
+The captured per-step weight cast reads the weight cache's descriptor table (svol_amd/params.py) through the pointer it had at
+capture time, and the table is rebuilt when a weight is registered or dies: build, and run once, every model of the process before
+the capture.
 """
 from __future__ import annotations
 
@@ -22,8 +30,9 @@ from .modeling.matcher import StaticPackedTargets
 class GraphedTrainStep:
     def __init__(self, model, criterion, optimizer, reducer, inputs: dict, targets, max_boxes_per_video: int = 128,
                  warmup: int = 3):
-        """model: SVANet head (training mode), criterion: SetCriterion, optimizer: a CAPTURABLE optimizer — a flat optimizer of
-        svol_amd.parallel built with ``capturable=True`` (its step count and hyper-parameters live on the device; a scheduler's
+        """model: SVANet head, a svanet_variants head or SketchDETR (training mode), criterion: SetCriterion (sketch_detr: it returns one
+        loss dict per frame; the total is summed over the frames and the list of dicts is handed back), optimizer: a CAPTURABLE
+        optimizer — a flat optimizer of svol_amd.parallel built with ``capturable=True`` (its step count and hyper-parameters live on the device; a scheduler's
         edits of ``param_groups`` reach the replays through its ``push_hyper()``, called here before every replay) or a torch one
         (e.g. AdamW(fused=True, capturable=True)), reducer: BucketedGradAllReduce (world size 1)."""
         if reducer.world != 1:
@@ -34,12 +43,16 @@ class GraphedTrainStep:
         self.static_in = {k: v.clone() for k, v in inputs.items()}
         B, N = inputs['src_video'].shape[0], model.num_queries
         m = criterion.matcher
-        nl = model.transformer.num_layers
+        tr = model.transformer
+        encdec = hasattr(tr, 'decoder')   # the enc/dec Transformer: the criterion matches its decoder layers' outputs
+        nl = tr.decoder.num_layers if encdec else tr.num_layers
         self.packed = StaticPackedTargets(m.kind, nl, B, N, m.num_frames, m.num_queries_per_frame, dev,
                                           max_boxes_per_video)
         self.packed.load(targets)
         criterion.static_packed = self.packed
         model.step_dev = torch.zeros((1,), dtype=torch.int64, device=dev)
+        if encdec:   # one counter for the head's input projections and the Transformer's dropouts
+            tr.step_dev = model.step_dev
         self.weights = criterion.weight_dict
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
@@ -73,14 +86,20 @@ class GraphedTrainStep:
         out = self.model(self.static_in['src_sketch'], self.static_in['src_sketch_mask'], self.static_in['src_video'],
                          self.static_in['src_video_mask'])
         ld = self.criterion(out, None)
-        loss = sum(ld[k] * self.weights[k] for k in ld.keys() if k in self.weights)
+        if isinstance(ld, list):   # sketch_detr: one dict per frame
+            loss = sum(sum(d[k] * self.weights[k] for k in d.keys() if k in self.weights) for d in ld)
+        else:
+            loss = sum(ld[k] * self.weights[k] for k in ld.keys() if k in self.weights)
         loss.backward()
         self.reducer.finish()
         self.optimizer.step()
+        if isinstance(ld, list):
+            return loss.detach(), [{k: v.detach() for k, v in d.items()} for d in ld]
         return loss.detach(), {k: v.detach() for k, v in ld.items()}
 
     def __call__(self, inputs: dict = None, targets=None):
-        """Run one training step; returns (loss, loss_dict) as STATIC tensors (overwritten by the next call)."""
+        """Run one training step; returns (loss, loss_dict — sketch_detr: the list of per-frame dicts) as STATIC tensors (overwritten by
+        the next call)."""
         if inputs is not None:
             for k, v in inputs.items():
                 self.static_in[k].copy_(v, non_blocking=True)

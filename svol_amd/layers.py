@@ -117,11 +117,16 @@ def _ln_out(s32, gamma, beta, pos_out, dt):
     return y32, y, ypos, mean, rstd
 
 
+def _sd(drop):
+    """the device-side step counter of drop = (p, seed_a, seed_b[, seed_dev]), or None"""
+    return drop[3] if len(drop) > 3 else None
+
+
 def _block_grad(dy32, dy, dypos, ln, dt, D, drop, sg, sbt, sb):
     """The opening of a residual block's backward: (dy32, dy, dypos) -> (ds32 the stream's gradient, g the gradient of the pre-norm sum
     in the compute dtype, dgamma, dbeta, column sums of g = the bias gradient of the Linear that fed the sum).  ln = (s32, gamma,
     mean, rstd) or None (pre-norm layers: the incoming fp32 stream gradient IS the gradient of the sum); sg / sbt / sb: the sinks
-    of gamma, beta and that bias.  drop = (p, ., seed_residual): g passes the residual dropout's mask before it meets any GEMM —
+    of gamma, beta and that bias.  drop = (p, ., seed_residual[, seed_dev]): g passes the residual dropout's mask before it meets any GEMM —
     LayerNorm backward without column sums, then the mask in place, then colsum."""
     if ln is None:
         ds32 = dy32.reshape(-1, D)
@@ -131,13 +136,13 @@ def _block_grad(dy32, dy, dypos, ln, dt, D, drop, sg, sbt, sb):
             g = cast(ds32, dt)
         else:
             g = torch.empty((ds32.shape[0], D), dtype=dt, device=ds32.device)   # (never ds32 itself: that is the stream's gradient)
-            dropout(cast(ds32, dt), drop[0], drop[2], out=g)
+            dropout(cast(ds32, dt), drop[0], drop[2], out=g, seed_dev=_sd(drop))
     elif drop is None:
         return layernorm_bwd(dy32, dy, dypos, *ln, dt, want32=True, want_colsum=True, dg_out=sink_view(sg), db_out=sink_view(sbt),
                              cs_out=sink_view(sb))
     else:
         ds32, g, dg, dbt = layernorm_bwd(dy32, dy, dypos, *ln, dt, want32=True, dg_out=sink_view(sg), db_out=sink_view(sbt))
-        dropout(g, drop[0], drop[2], out=g)
+        dropout(g, drop[0], drop[2], out=g, seed_dev=_sd(drop))
     return ds32, g, dg, dbt, colsum(g, out=sink_view(sb))
 
 
@@ -148,8 +153,10 @@ class MLPLNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x32, x, W1, b1, W2, b2, gamma, beta, pos_out, act=ACT_GELU, drop=None, wc=None):
-        """drop = (p, seed_hidden, seed_residual): training-mode dropout of the enc/dec FFN — linear2(dropout(act(linear1 x))) and
-        x + dropout2(.) (transformer.py:168,171,238-240).  wc = (W1, W1^T, W2, W2^T) in the compute dtype, cast by the caller
+        """drop = (p, seed_hidden, seed_residual[, seed_dev]): training-mode dropout of the enc/dec FFN — linear2(dropout(act(linear1 x)))
+        and x + dropout2(.) (transformer.py:168,171,238-240).  seed_dev: a device int64 step counter (ops.dropout), kept alive on ctx and
+        not a differentiable input; backward regenerates the masks through the same pointer, so the counter must not move between a
+        step's forward and its backward.  wc = (W1, W1^T, W2, W2^T) in the compute dtype, cast by the caller
         (a module that runs before the forward that advances ``weights``' epoch); None: from ``weights``."""
         ctx.set_materialize_grads(False)
         if drop is not None and drop[0] <= 0.0:
@@ -171,9 +178,9 @@ class MLPLNFn(torch.autograd.Function):
         else:
             raise _lib.SvolHipError('MLPLNFn: activation must be GELU or ReLU')
         if drop is not None:
-            dropout(hid, drop[0], drop[1], out=hid)   # (ReLU: aux IS hid — kept entries stay positive, dropped ones get relu' = 0, as the mask wants)
+            dropout(hid, drop[0], drop[1], out=hid, seed_dev=_sd(drop))   # (ReLU: aux IS hid — kept entries stay positive, dropped ones get relu' = 0, as the mask wants)
             s32 = dropout_add(gemm_nt(hid, W2c, b2, ACT_NONE, out_f32=True), x32_2 if x32_2.is_contiguous() else x32_2.contiguous(),
-                              drop[0], drop[2])
+                              drop[0], drop[2], _sd(drop))
         else:
             s32 = gemm_nt(hid, W2c, b2, ACT_NONE, residual=x32_2, out_f32=True)
         ctx.W1T, ctx.W2T, ctx.shp, ctx.act, ctx.has_ln = W1T, W2T, shp, act, gamma is not None
@@ -207,7 +214,7 @@ class MLPLNFn(torch.autograd.Function):
         # (ds W2) * act'(aux) and its column sums, one kernel
         if drop is not None:   # ... then the hidden dropout's mask, then the column sums
             dpre, _ = gemm_nt_dact(ds, ctx.W2T, aux, ctx.act, want_colsum=False)
-            dropout(dpre, drop[0], drop[1], out=dpre)
+            dropout(dpre, drop[0], drop[1], out=dpre, seed_dev=_sd(drop))
             db1 = colsum(dpre, out=sink_view(sb1))
         else:
             dpre, db1 = gemm_nt_dact(ds, ctx.W2T, aux, ctx.act, colsum_out=sink_view(sb1))
@@ -229,9 +236,11 @@ class AttnLNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, self_attn,
                 need_weights=False, drop=None):
-        """drop = (p, seed_attention, seed_residual): training-mode dropout of the enc/dec attention blocks — on the attention
+        """drop = (p, seed_attention, seed_residual[, seed_dev]): training-mode dropout of the enc/dec attention blocks — on the attention
         probabilities (nn.MultiheadAttention(dropout=p)) and on the block output before the residual add (dropout1 / dropout2,
-        transformer.py:158-177,216-247).  The returned attention weights stay those of the undropped softmax."""
+        transformer.py:158-177,216-247).  The returned attention weights stay those of the undropped softmax.  seed_dev: a device int64
+        step counter (ops.attn_fwd), kept alive on ctx, not a differentiable input; backward regenerates the masks through the same
+        pointer, so the counter must not move between a step's forward and its backward."""
         ctx.set_materialize_grads(False)
         if drop is not None and drop[0] <= 0.0:
             drop = None
@@ -277,12 +286,12 @@ class AttnLNFn(torch.autograd.Function):
             gemm_nt_split(a_v, Wv_hilo, b_in[2 * d:], out=v)
         else:
             gemm_nt(a_v, Wc[2 * d:], b_in[2 * d:], out=v)
-        o, lse2 = attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul, drop=(drop[0], drop[1]) if drop is not None else None)
+        o, lse2 = attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul, drop=(drop[0], drop[1], _sd(drop)) if drop is not None else None)
         att = attn_weights_mean(q, k, lse2, B, H, Lq, Lk, dh, kbias, premul) if need_weights else None
         if drop is not None:
             r32 = xq32.reshape(B * Lq, d)
             s32 = dropout_add(gemm_nt(cast(o, dt) if mixed else o, Woc, b_o, out_f32=True), r32 if r32.is_contiguous() else r32.contiguous(),
-                              drop[0], drop[2])
+                              drop[0], drop[2], _sd(drop))
         else:
             s32 = gemm_nt(cast(o, dt) if mixed else o, Woc, b_o, residual=xq32.reshape(B * Lq, d), out_f32=True)
         ctx.WcT, ctx.WoT, ctx.dims, ctx.self_attn, ctx.premul = WcT, WoT, (B, H, Lq, Lk, dh, d), self_attn, premul
@@ -326,7 +335,7 @@ class AttnLNFn(torch.autograd.Function):
         grads = GradGroup(((sW_in, (3 * d, d)), (sb_in, (3 * d,)), (sWo, (d, d))), g.device)   # dW_in | db_in | dW_o
         W_IN, B_IN, W_O = 0, 1, 2
         mixed = ctx.mixed
-        adrop = (drop[0], drop[1]) if drop is not None else None
+        adrop = (drop[0], drop[1], _sd(drop)) if drop is not None else None
         grads.tn(g, cast(o, dt) if mixed else o, W_O)
         do = gemm_nt(g, WoT)
         if mixed:

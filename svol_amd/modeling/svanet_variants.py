@@ -32,10 +32,16 @@ def _proj_stack(input_dim, hidden_dim, input_dropout, n_input_proj):
 class _DetrHead(nn.Module):
     """what the variants and SketchDETR share: projections through LinearLayer stacks, box / class heads on ``hs``."""
 
+    # a device int64 [1] step counter shared with ``transformer.step_dev`` (svol_amd.graph.GraphedTrainStep installs and advances
+    # it), else None.  With one, the input-projection masks are those of step ``_step + step_dev[0]`` (the layer-norm kernels add
+    # ``step_dev[0] << 8``, the stride of ``_step`` below) and the host ``_step`` stands still.
+    step_dev = None
+
     def _proj(self, seq, x, salt):
         n = len(seq)
         for j, layer in enumerate(seq):
-            x = layer(x, seed=(self.base_seed << 32) + (self._step << 8) + salt * 16 + j, out_f32=(j == n - 1))
+            x = layer(x, seed=(self.base_seed << 32) + (self._step << 8) + salt * 16 + j, out_f32=(j == n - 1),
+                      seed_dev=self.step_dev)
         return x
 
     def _begin(self, src_video):
@@ -43,7 +49,7 @@ class _DetrHead(nn.Module):
             raise RuntimeError(f'svol_amd.{type(self).__name__} runs on the MI355X HIP kernels only; move the module and '
                                'its inputs to cuda (there is no CPU path — the CPU oracle lives under oracle/).')
         params.weights.new_epoch()
-        if self.training:
+        if self.training and self.step_dev is None:
             self._step += 1
 
     def _heads(self, hs):

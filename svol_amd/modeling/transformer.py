@@ -22,7 +22,10 @@ compute dtype.  Differences from the reference, all documented in DESIGN.md:
   (``svol_attn_fwd_dropout``), the residual dropouts (``svol_dropout_add``) and the FFN hidden dropout (``svol_dropout``), all
   stateless masks of (seed, element index) that backward regenerates; the masks of a step are a function of
   ``(drop_base_seed, step, layer, site)``.  The returned attention WEIGHTS are those of the undropped softmax (torch
-  returns the dropped ones; no consumer in the reference reads them).
+  returns the dropped ones; no consumer in the reference reads them).  The step is a host integer, or — with
+  ``Transformer.step_dev`` installed (svol_amd.graph.GraphedTrainStep) — the host integer plus a device-side counter that the
+  kernels add to the seeds themselves (the ``*_sd`` entries): a captured graph then draws the masks of the eager step with the
+  same number on every replay.  Without a counter a capture in training mode is refused (``_drop``).
 * activation: ``relu`` (the only one ``build_transformer`` can select, :312-322) and ``gelu``; ``glu`` raises.
 * ``att_weights`` carry no gradient (every consumer in the reference discards them: sketch_detr.py:62,
   svanet_variants.py:107-116); ``need_weights=False`` skips computing them.
@@ -58,16 +61,21 @@ _n = lambda m: (m.weight, m.bias)
 _mha = lambda m: (m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias)
 
 
-def _drop(mod, seed, site_a, site_b):
+def _drop(mod, seed, site_a, site_b, seed_dev=None):
     """(p, seed_a, seed_b) of one block of layer `mod` in training mode, else None.  seed: the step's base seed (Transformer.forward),
     None outside a Transformer (then a per-layer counter stands in).  Sites 0..5 of a layer: self-attention probabilities / its
-    residual dropout1, cross-attention probabilities / dropout2, FFN hidden dropout / the FFN's residual dropout."""
+    residual dropout1, cross-attention probabilities / dropout2, FFN hidden dropout / the FFN's residual dropout.
+    seed_dev: a device int64 step counter (Transformer.step_dev) — the 4-tuple (p, seed_a, seed_b, seed_dev): the kernels add
+    (seed_dev[0] << 12) to the seeds on the device, so a captured graph draws fresh masks on every replay and capture is allowed."""
     if not (mod.training and mod.dropout_p > 0.0):
         return None
+    if seed_dev is not None and seed is not None:
+        base = seed + (getattr(mod, 'layer_id', 0) << 4)
+        return (mod.dropout_p, base + site_a, base + site_b, seed_dev)
     if torch.cuda.is_current_stream_capturing():
         # the seeds are host integers passed BY VALUE into the launches: a captured graph would replay one step's masks forever
         # (ADVICE r3).  The SVANet input projections take a device-side seed offset (svol_layernorm_fwd's seed_offset_dev) and can be
-        # captured; the enc/dec Transformer's attention / residual / FFN dropouts cannot.
+        # captured; the enc/dec Transformer's attention / residual / FFN dropouts can with a device step counter (seed_dev) only.
         raise RuntimeError('training-mode dropout of the enc/dec Transformer cannot be captured in a hipGraph (its mask seeds are host '
                            'values): run the step eagerly, or set --dropout 0')
     if seed is None:
@@ -89,30 +97,30 @@ class TransformerEncoderLayer(nn.Module):
         self.normalize_before = normalize_before
         self.nhead, self.dropout_p = nhead, float(dropout)
 
-    def _ffn(self, x32, x, norm, pos_out, seed=None):
+    def _ffn(self, x32, x, norm, pos_out, seed=None, seed_dev=None):
         g, b = _n(norm) if norm is not None else (None, None)
         return layers.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
-                          pos_out, self.act, _drop(self, seed, 4, 5))
+                          pos_out, self.act, _drop(self, seed, 4, 5, seed_dev))
 
-    def forward_post(self, state, pos, kbias, seed=None):
+    def forward_post(self, state, pos, kbias, seed=None, seed_dev=None):
         """state = (x32, x, x + pos) -> same triple (transformer.py:175-194)."""
         x32, x, xpos = state
         y32, y = layers.self_attn_ln(x32, x, xpos, *_mha(self.self_attn), *_n(self.norm1), None, self.nhead, kbias,
-                                  _drop(self, seed, 0, 1))
-        return self._ffn(y32, y, self.norm2, pos, seed)
+                                  _drop(self, seed, 0, 1, seed_dev))
+        return self._ffn(y32, y, self.norm2, pos, seed, seed_dev)
 
-    def forward_pre(self, x32, pos, kbias, seed=None):
+    def forward_pre(self, x32, pos, kbias, seed=None, seed_dev=None):
         """x32 -> x32 (transformer.py:196-208)."""
         dt = pos.dtype
         y, ypos = layers.ln_stream(x32, *_n(self.norm1), pos, dt)
-        s32 = layers.self_attn_ln(x32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, kbias, _drop(self, seed, 0, 1))
+        s32 = layers.self_attn_ln(x32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, kbias, _drop(self, seed, 0, 1, seed_dev))
         y2 = layers.ln_stream(s32, *_n(self.norm2), None, dt)
-        return self._ffn(s32, y2, None, None, seed)
+        return self._ffn(s32, y2, None, None, seed, seed_dev)
 
-    def forward(self, state, pos, kbias, seed=None):
+    def forward(self, state, pos, kbias, seed=None, seed_dev=None):
         if self.normalize_before:
-            return self.forward_pre(state, pos, kbias, seed)
-        return self.forward_post(state, pos, kbias, seed)
+            return self.forward_pre(state, pos, kbias, seed, seed_dev)
+        return self.forward_post(state, pos, kbias, seed, seed_dev)
 
 
 class TransformerDecoderLayer(nn.Module):
@@ -129,38 +137,38 @@ class TransformerDecoderLayer(nn.Module):
         self.normalize_before = normalize_before
         self.nhead, self.dropout_p = nhead, float(dropout)
 
-    def _ffn(self, x32, x, norm, pos_out, seed=None):
+    def _ffn(self, x32, x, norm, pos_out, seed=None, seed_dev=None):
         g, b = _n(norm) if norm is not None else (None, None)
         return layers.mlp_ln(x32, x, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, g, b,
-                          pos_out, self.act, _drop(self, seed, 4, 5))
+                          pos_out, self.act, _drop(self, seed, 4, 5, seed_dev))
 
-    def forward_post(self, state, mem, mempos, qpos, kbias, need_weights, seed=None):
+    def forward_post(self, state, mem, mempos, qpos, kbias, need_weights, seed=None, seed_dev=None):
         """state = (t32, t, t + query_pos) -> (same triple, att | None)   (transformer.py:229-250)."""
         t32, t, tpos = state
         a32, a, apos = layers.self_attn_ln(t32, t, tpos, *_mha(self.self_attn), *_n(self.norm1), qpos, self.nhead, None,
-                                        _drop(self, seed, 0, 1))
+                                        _drop(self, seed, 0, 1, seed_dev))
         r = layers.cross_attn_ln(a32, a, apos, mempos, mem, *_mha(self.multihead_attn), *_n(self.norm2), None, self.nhead,
-                              kbias, need_weights, _drop(self, seed, 2, 3))
+                              kbias, need_weights, _drop(self, seed, 2, 3, seed_dev))
         c32, c = r[0], r[1]
         att = r[2] if need_weights else None
-        return self._ffn(c32, c, self.norm3, qpos, seed), att
+        return self._ffn(c32, c, self.norm3, qpos, seed, seed_dev), att
 
-    def forward_pre(self, t32, mem, mempos, qpos, kbias, need_weights, seed=None):
+    def forward_pre(self, t32, mem, mempos, qpos, kbias, need_weights, seed=None, seed_dev=None):
         """t32 -> (t32, att | None)   (transformer.py:252-283)."""
         dt = mem.dtype
         y, ypos = layers.ln_stream(t32, *_n(self.norm1), qpos, dt)
-        s32 = layers.self_attn_ln(t32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, None, _drop(self, seed, 0, 1))
+        s32 = layers.self_attn_ln(t32, y, ypos, *_mha(self.self_attn), None, None, None, self.nhead, None, _drop(self, seed, 0, 1, seed_dev))
         y2, y2pos = layers.ln_stream(s32, *_n(self.norm2), qpos, dt)
         r = layers.cross_attn_ln(s32, y2, y2pos, mempos, mem, *_mha(self.multihead_attn), None, None, None, self.nhead,
-                              kbias, need_weights, _drop(self, seed, 2, 3))
+                              kbias, need_weights, _drop(self, seed, 2, 3, seed_dev))
         c32, att = (r[0], r[1]) if need_weights else (r, None)
         y3 = layers.ln_stream(c32, *_n(self.norm3), None, dt)
-        return self._ffn(c32, y3, None, None, seed), att
+        return self._ffn(c32, y3, None, None, seed, seed_dev), att
 
-    def forward(self, state, mem, mempos, qpos, kbias, need_weights=False, seed=None):
+    def forward(self, state, mem, mempos, qpos, kbias, need_weights=False, seed=None, seed_dev=None):
         if self.normalize_before:
-            return self.forward_pre(state, mem, mempos, qpos, kbias, need_weights, seed)
-        return self.forward_post(state, mem, mempos, qpos, kbias, need_weights, seed)
+            return self.forward_pre(state, mem, mempos, qpos, kbias, need_weights, seed, seed_dev)
+        return self.forward_post(state, mem, mempos, qpos, kbias, need_weights, seed, seed_dev)
 
 
 def _get_clones(module, N):
@@ -178,7 +186,7 @@ class TransformerEncoder(nn.Module):
         if return_intermediate:  # never requested by the reference's builder (transformer.py:27-29)
             raise NotImplementedError('encoder return_intermediate')
 
-    def forward(self, src32, pos, kbias, seed=None):
+    def forward(self, src32, pos, kbias, seed=None, seed_dev=None):
         """src32 [B,L,d] fp32, pos [B,L,d] compute dtype, kbias [B,L] fp32 additive key mask or None ->
         (memory32 [B,L,d] fp32, memory, memory + pos) — what the decoder's cross-attention reads."""
         dt = pos.dtype
@@ -186,7 +194,7 @@ class TransformerEncoder(nn.Module):
         if pre:
             x32 = src32
             for layer in self.layers:
-                x32 = layer(x32, pos, kbias, seed)
+                x32 = layer(x32, pos, kbias, seed, seed_dev)
             if self.norm is not None:  # the builder gives the pre-norm encoder a closing norm (:26)
                 return layers.ln_stream(x32, *_n(self.norm), pos, dt, True)
             x = layers.cast_ag(x32, dt)
@@ -194,7 +202,7 @@ class TransformerEncoder(nn.Module):
         x = layers.cast_ag(src32, dt)
         state = (src32, x, x + pos)  # layer 0's q = k = src + pos (:183); later layers get it from the norm2 epilogue
         for layer in self.layers:
-            state = layer(state, pos, kbias, seed)
+            state = layer(state, pos, kbias, seed, seed_dev)
         if self.norm is not None:
             return layers.ln_stream(state[0], *_n(self.norm), pos, dt, True)
         return state
@@ -210,7 +218,7 @@ class TransformerDecoder(nn.Module):
         self.norm = norm
         self.return_intermediate = return_intermediate
 
-    def forward(self, mem, mempos, qpos, kbias, need_weights=True, seed=None):
+    def forward(self, mem, mempos, qpos, kbias, need_weights=True, seed=None, seed_dev=None):
         """mem / mempos [B,L,d] compute dtype, qpos [N,d] or [B,N,d] compute dtype ->
         (hs [n,B,N,d] fp32, att [n,B,N,L] fp32 | None); n = num_layers with return_intermediate, else 1 (:116-152)."""
         B = mem.shape[0]
@@ -222,7 +230,7 @@ class TransformerDecoder(nn.Module):
         state = t32 if pre else (t32, torch.zeros((B, N, d), dtype=dt, device=mem.device), qfull)
         inter, atts = [], []
         for layer in self.layers:
-            state, att = layer(state, mem, mempos, qpos, kbias, need_weights and self.return_intermediate, seed)
+            state, att = layer(state, mem, mempos, qpos, kbias, need_weights and self.return_intermediate, seed, seed_dev)
             if self.return_intermediate:
                 o32 = state if pre else state[0]
                 inter.append(layers.ln_stream(o32, *_n(self.norm), None, torch.float32) if self.norm is not None else o32)
@@ -256,6 +264,12 @@ class Transformer(nn.Module):
         # after a resume through dropout_state() / load_dropout_state() (svol_amd.utils.checkpoint keeps them in the file)
         self.drop_base_seed = 1
         self._drop_step = 0
+        # a device int64 [1] step counter, installed by the owner of a captured training step (svol_amd.graph.GraphedTrainStep), else
+        # None.  With one, forward leaves _drop_step alone and the step number is _drop_step + step_dev[0]: the kernels add the
+        # counter to the host seeds on the device (the *_sd entries), so every replay of a captured graph draws the masks the eager
+        # step of the same number draws.  The owner advances the counter by one BEFORE each forward (a fresh model's first step is
+        # step 1, as in eager) and never between a step's forward and its backward (backward regenerates the masks from it).
+        self.step_dev = None
 
     def _reset_parameters(self):
         for p in self.parameters():
@@ -263,10 +277,17 @@ class Transformer(nn.Module):
                 nn.init.xavier_uniform_(p)
 
     def dropout_state(self):
-        return {'drop_base_seed': int(self.drop_base_seed), 'drop_step': int(self._drop_step)}
+        """the state a checkpoint keeps; drop_step is the EFFECTIVE step (host step + an installed device counter: one host read of
+        the device, for checkpoint time only — never during a capture)"""
+        step = int(self._drop_step)
+        if self.step_dev is not None:
+            step += int(self.step_dev.item())
+        return {'drop_base_seed': int(self.drop_base_seed), 'drop_step': step}
 
     def load_dropout_state(self, st):
         self.drop_base_seed, self._drop_step = int(st['drop_base_seed']), int(st['drop_step'])
+        if self.step_dev is not None:
+            self.step_dev.zero_()
 
     def forward(self, src, mask, query_embed, pos_embed, need_weights: bool = True):
         """src [B,L,d] (fp32: it starts the fp32 residual stream), mask [B,L] bool with True on PADDED positions (or
@@ -288,10 +309,11 @@ class Transformer(nn.Module):
         qpos = layers.cast_ag(qpos.float().contiguous(), dt)
         seed = None
         if self.training:
-            self._drop_step += 1
-            seed = ((int(self.drop_base_seed) + _rank()) << 44) + (self._drop_step << 12)
-        mem32, mem, mempos = self.encoder(src32.contiguous(), pos.contiguous(), kbias, seed)
-        hs, att = self.decoder(mem, mempos, qpos, kbias, need_weights, seed)
+            if self.step_dev is None:
+                self._drop_step += 1
+            seed = ((int(self.drop_base_seed) + _rank()) << 44) + (self._drop_step << 12)   # (+ step_dev[0] << 12 on the device)
+        mem32, mem, mempos = self.encoder(src32.contiguous(), pos.contiguous(), kbias, seed, self.step_dev)
+        hs, att = self.decoder(mem, mempos, qpos, kbias, need_weights, seed, self.step_dev)
         return hs, mem32, att
 
 

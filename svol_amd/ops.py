@@ -314,35 +314,53 @@ def _attn_ws(q, B, H, Lq, Lk, dh):
     return torch.empty((n // 4,), dtype=torch.float32, device=q.device) if n else None
 
 
-def dropout(x, p, seed, out=None):
-    """x * keep(seed, row, column) (0 or 1/(1-p)) over x viewed as [-1, x.shape[-1]]; out may be x (in place).  x contiguous."""
+def dropout(x, p, seed, out=None, seed_dev=None):
+    """x * keep(seed, row, column) (0 or 1/(1-p)) over x viewed as [-1, x.shape[-1]]; out may be x (in place).  x contiguous.
+    seed_dev: device int64 step counter or None — the mask is that of seed + (seed_dev[0] << 12) (svol_dropout_sd)."""
     assert x.is_contiguous()
     out = torch.empty_like(x) if out is None else out
-    _lib.check(_lib.lib().svol_dropout(_ptr(x), _ptr(out), x.numel(), max(1, x.shape[-1] if x.dim() else 1), float(p), int(seed), _dt(x),
-                                       _stream()), 'svol_dropout')
+    args = (_ptr(x), _ptr(out), x.numel(), max(1, x.shape[-1] if x.dim() else 1), float(p), int(seed))
+    if seed_dev is None:   # (the entry it always was: the launch sequence of a host-seeded step stays what it was)
+        _lib.check(_lib.lib().svol_dropout(*args, _dt(x), _stream()), 'svol_dropout')
+    else:
+        _lib.check(_lib.lib().svol_dropout_sd(*args, _ptr(seed_dev), _dt(x), _stream()), 'svol_dropout_sd')
     return out
 
 
-def dropout_add(t32, res32, p, seed):
-    """res32 + dropout(t32), fp32, written over t32 (rows = t32.shape[-1] wide)."""
+def dropout_add(t32, res32, p, seed, seed_dev=None):
+    """res32 + dropout(t32), fp32, written over t32 (rows = t32.shape[-1] wide).  seed_dev: as in dropout."""
     assert t32.is_contiguous() and res32.is_contiguous() and t32.dtype == torch.float32 and res32.dtype == torch.float32
-    _lib.check(_lib.lib().svol_dropout_add(_ptr(t32), _ptr(res32), _ptr(t32), t32.numel(), max(1, t32.shape[-1]), float(p), int(seed),
-                                           _stream()), 'svol_dropout_add')
+    args = (_ptr(t32), _ptr(res32), _ptr(t32), t32.numel(), max(1, t32.shape[-1]), float(p), int(seed))
+    if seed_dev is None:
+        _lib.check(_lib.lib().svol_dropout_add(*args, _stream()), 'svol_dropout_add')
+    else:
+        _lib.check(_lib.lib().svol_dropout_add_sd(*args, _ptr(seed_dev), _stream()), 'svol_dropout_add_sd')
     return t32
+
+
+def _attn_drop(drop):
+    """drop = None | (p, seed) | (p, seed, seed_dev) -> (p, seed, seed_dev) of the launch; p <= 0: no dropout"""
+    if drop is None or drop[0] <= 0.0:
+        return 0.0, 0, None
+    return float(drop[0]), int(drop[1]), (drop[2] if len(drop) > 2 else None)
 
 
 def attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias=None, premul=0.0, drop=None):
     """q/k/v: 2-D [B*L, >=H*dh] views (column slices allowed). Returns o [B*Lq, H*dh], lse2 [B,H,Lq].
-    drop = (p, seed): attention-probability dropout (None or p <= 0: none)."""
+    drop = (p, seed) or (p, seed, seed_dev): attention-probability dropout (None or p <= 0: none); seed_dev: device int64 step counter,
+    the masks are those of seed + (seed_dev[0] << 12)."""
     o = torch.empty((B * Lq, H * dh), dtype=q.dtype, device=q.device)
     lse2 = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
     ws = _attn_ws(q, B, H, Lq, Lk, dh)
-    p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
+    p, seed, seed_dev = _attn_drop(drop)
     wgrad.attn_forward(B * H * Lq * Lk)
     tok = timer.start('attn_fwd', (B, H, Lq, Lk, dh))
-    rc = _lib.lib().svol_attn_fwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                                          _ptr(lse2), _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws),
-                                          ws.numel() * 4 if ws is not None else 0, p, seed, _dt(q), _stream())
+    args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(lse2), _ptr(kbias), B, H, Lq, Lk,
+            dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, p, seed)
+    if seed_dev is None:
+        rc = _lib.lib().svol_attn_fwd_dropout(*args, _dt(q), _stream())
+    else:
+        rc = _lib.lib().svol_attn_fwd_dropout_sd(*args, _ptr(seed_dev), _dt(q), _stream())
     timer.stop(tok)
     _lib.check(rc, 'svol_attn_fwd')
     return o, lse2
@@ -354,13 +372,15 @@ def attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, pre
     wgrad.attn_backward(B * H * Lq * Lk)   # the queued weight-gradient GEMMs run beside this launch
     delta = torch.empty((3, B, H, Lq), dtype=torch.float32, device=q.device)  # delta | -lse2 pairs | -delta pairs (svol_hip.h)
     ws = _attn_ws(q, B, H, Lq, Lk, dh)
-    p, seed = (float(drop[0]), int(drop[1])) if drop is not None and drop[0] > 0.0 else (0.0, 0)
+    p, seed, seed_dev = _attn_drop(drop)
     tok = timer.start('attn_bwd', (B, H, Lq, Lk, dh))
-    rc = _lib.lib().svol_attn_bwd_dropout(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                                          _ptr(do), do.stride(0), _ptr(lse2), _ptr(delta), _ptr(kbias), _ptr(dq), dq.stride(0),
-                                          _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh),
-                                          float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, p, seed, _dt(q),
-                                          _stream())
+    args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(do), do.stride(0), _ptr(lse2),
+            _ptr(delta), _ptr(kbias), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), B, H, Lq, Lk, dh,
+            1.0 / math.sqrt(dh), float(premul), _ptr(ws), ws.numel() * 4 if ws is not None else 0, p, seed)
+    if seed_dev is None:
+        rc = _lib.lib().svol_attn_bwd_dropout(*args, _dt(q), _stream())
+    else:
+        rc = _lib.lib().svol_attn_bwd_dropout_sd(*args, _ptr(seed_dev), _dt(q), _stream())
     timer.stop(tok)
     _lib.check(rc, 'svol_attn_bwd')
 
