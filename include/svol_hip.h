@@ -625,7 +625,7 @@ int svol_maxpool_bwd_nhwc(const void* dy, const uint8_t* idx, void* dx, int64_t 
 /* att[B,Lq,Lk] (fp32) = 1/H * sum_h softmax_l(q_h k_h^T * scale + kbias): the head-averaged attention weights that
  * nn.MultiheadAttention returns with need_weights=True and the reference's TransformerDecoder stacks per layer
  * (transformer.py:139-152, 258-262).  Recomputed from q, k (layouts as svol_attn_fwd, q_premul as there) and the
- * lse2 [B,H,Lq] that svol_attn_fwd wrote; dh in {8,16,32,64}.  No gradient. */
+ * lse2 [B,H,Lq] that svol_attn_fwd wrote; dh in {8,16,32,40,48,56,64}; SVOL_F32, SVOL_BF16 or SVOL_F16.  No gradient. */
 int svol_attn_weights_mean(const void* q, int64_t ldq, const void* k, int64_t ldk, const float* lse2, const float* kbias,
                            float* att, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, float scale,
                            float q_premul, int dtype, void* stream);

@@ -72,6 +72,9 @@ int launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const float* 
     if (dh == 8) SVOL_AW(8);
     else if (dh == 16) SVOL_AW(16);
     else if (dh == 32) SVOL_AW(32);
+    else if (dh == 40) SVOL_AW(40);   // the widths svol_attn_fwd serves above 32 (attention_wide.hip)
+    else if (dh == 48) SVOL_AW(48);
+    else if (dh == 56) SVOL_AW(56);
     else if (dh == 64) SVOL_AW(64);
     else return SVOL_E_UNSUPPORTED;
 #undef SVOL_AW
@@ -91,6 +94,7 @@ extern "C" int svol_attn_weights_mean(const void* q, int64_t ldq, const void* k,
     // q already carries d_h^-1/2 * log2(e) when q_premul != 0 (bf16 projection epilogue), as in svol_attn_fwd
     const float c = q_premul != 0.f ? 1.f : scale * LOG2E;
     if (dtype == SVOL_BF16) return launch<bf16_t>(q, ldq, k, ldk, lse2, kbias, att, B, H, Lq, Lk, dh, c, s);
+    if (dtype == SVOL_F16) return launch<f16_t>(q, ldq, k, ldk, lse2, kbias, att, B, H, Lq, Lk, dh, c, s);
     if (dtype == SVOL_F32) return launch<float>(q, ldq, k, ldk, lse2, kbias, att, B, H, Lq, Lk, dh, c, s);
     return SVOL_E_INVALID;
 }

@@ -21,14 +21,17 @@ fp64 on the CPU, tests/test_gpu_attn_range.py runs the cases on the device.
 
    Heads take the layouts in the cycle late, none, step, front.  Planted rows sit in the first and the last query tile of a planted
    head, at most four per tile, in different waves (32-row groups).  Variant 'calm' turns every 'over' row into a 'near' row.
-3. Mask layouts (`key_bias`): first_dead, mid_dead, one_live, edge, per_batch, finite, zero, first_split_dead, cls65.
+3. Mask layouts (`key_bias`): first_dead, mid_dead, one_live, edge, per_batch, finite, zero, first_split_dead, cls65; sub_dead and
+   pair at the granularity of the head-width 40-64 kernels.
 4. `figures`: slice errors, element errors per (batch, head, 128-row tile) separately over planted and other rows / keys, lse2 per
    row set, gradient rows of -inf keys, finiteness.
 5. Fault runners: the fp64 reference with one deliberate defect each.
+
+make_case, key_bias, case_plan and points take the case table (CASES unless given); everything behind make_case works on the case
+dict.  tests/attn_wide_range_cases.py holds the table, the faults and the attention-weights reference of head widths 40-64.
 """
 from __future__ import annotations
 
-import functools
 import math
 
 import torch
@@ -75,6 +78,8 @@ def sp_ws_floats(B, H, Lq, Lk):
 
 def ws_floats(B, H, Lq, Lk, dh):
     """svol_attn_ws_bytes / 4"""
+    if dh > 32:                              # csrc/attention_wide.hip: no workspace
+        return 0
     ks, _ = plan_ksplit(B, H, Lq, Lk, dh)
     if ks < 2:
         cls, redo = B * cdiv(Lk, KT), B * H * cdiv(Lq, 128)
@@ -96,6 +101,8 @@ def head_xcd(B, H, dh):
 def plan(B, H, Lq, Lk, dh, premul, has_kbias, ws_bytes=None, deterministic=False):
     """the kernels one forward and one backward of this launch take (drop_p = 0, the scratch ops.attn_fwd hands over unless given)
     -> dict(fwd, bwd, ksplit, tps, head_xcd)"""
+    if dh > 32:                              # csrc/attention_wide.hip: one forward, one backward, no key split, no head-to-XCD deal
+        return dict(fwd='wide', bwd='wide', ksplit=1, tps=cdiv(Lk, KT), head_xcd=0)
     ws_bytes = 4 * ws_floats(B, H, Lq, Lk, dh) if ws_bytes is None else ws_bytes
     ws = ws_bytes > 0
     masked = has_kbias or Lk % KT != 0
@@ -162,14 +169,14 @@ PLANS_BWD = ('bwd_rot_dma', 'bwd_pre', 'bwd_sp', 'bwd_pre_masked', '2pass_m', '2
 DT_NAME = R.DT_NAME
 
 
-def case_plan(name, layout):
-    c = CASES[name]
+def case_plan(name, layout, cases=None):
+    c = (CASES if cases is None else cases)[name]
     return plan(*c['dims'], c['premul'], layout != 'none')
 
 
-def points(dtype):
-    """[(case, variant, layout)] of one dtype"""
-    return [(n, v, m) for n, c in CASES.items() if dtype != FP32 or c['fp32'] for v, m in c['points']]
+def points(dtype, cases=None):
+    """[(case, variant, layout)] of one dtype.  cases: a table like CASES (tests/attn_wide_range_cases.py holds the wide one)"""
+    return [(n, v, m) for n, c in (CASES if cases is None else cases).items() if dtype != FP32 or c['fp32'] for v, m in c['points']]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -181,9 +188,9 @@ NINF = float('-inf')
 KB_BIG = (87.0 / LOG2E, 87.78125 / LOG2E)
 
 
-def key_bias(name, layout):
+def key_bias(name, layout, cases=None):
     """[B, Lk] fp32 additive key bias, or None.  Every video keeps at least one live key."""
-    B, H, Lq, Lk, dh = CASES[name]['dims']
+    B, H, Lq, Lk, dh = (CASES if cases is None else cases)[name]['dims']
     if layout == 'none':
         return None
     kb = torch.zeros(B, Lk)
@@ -223,6 +230,15 @@ def key_bias(name, layout):
         kb[2, T(63)] = NINF                  # video 2: 63 dead, 64 with a single live key / 0 plain
         kb[2, T(64)] = NINF
         kb[2, 64 * 128 + 3] = 0
+    elif layout == 'sub_dead':               # at the wide kernels' granularity (64-key tiles, 32-key blocks): a dead LEADING block
+        kb[:, 0:32] = NINF                   # with the rest of its tile live, a dead block inside a live tile (96:128; 64:96 in
+        kb[:, 96:128] = NINF                 # every video but the first), one whole dead tile (192:256)
+        kb[:, 192:256] = NINF
+        kb[1:, 64:96] = NINF
+    elif layout == 'pair':                   # two live keys per video
+        kb[:] = NINF
+        kb[:, 70] = 0
+        kb[:, Lk - 5] = 0
     else:
         raise ValueError(layout)
     return kb
@@ -298,12 +314,23 @@ def _key_in_tile(live_b, t, Lk, off=37):
     return lo + int(torch.nonzero(live_b[lo:hi])[0])
 
 
-@functools.lru_cache(maxsize=None)
-def make_case(name, variant, layout, dtype):
+_MADE = {}
+
+
+def make_case(name, variant, layout, dtype, cases=None):
+    """one point of the table ``cases`` (CASES unless given), made once per table and shared"""
+    cases = CASES if cases is None else cases
+    key = (id(cases), name, variant, layout, dtype)
+    if key not in _MADE:
+        _MADE[key] = _make_case(cases, name, variant, layout, dtype)
+    return _MADE[key]
+
+
+def _make_case(cases, name, variant, layout, dtype):
     """-> dict: q (what the kernel is given), qref (fp64, the unscaled q it effectively sees), k, v, do (2-D [B L, H dh]), kb, pm,
     dims, prow [B, H, Lq] / pkey [B, H, Lk] (planted rows / keys), kinds {(b, h, row): kind}, sel (the (batch, head) pairs the
     reference covers, or None for all).  Shared between tests: never modified."""
-    cs = CASES[name]
+    cs = cases[name]
     B, H, Lq, Lk, dh = dims = cs['dims']
     d = H * dh
     pm = LOG2E / math.sqrt(dh) if cs['premul'] else 0.0
@@ -311,7 +338,7 @@ def make_case(name, variant, layout, dtype):
         R._rnd((B * Lq, d), dtype, 33)
     if pm:
         q = (q.double() * pm).to(dtype)
-    kb = key_bias(name, layout)
+    kb = key_bias(name, layout, cases)
     live = torch.ones(B, Lk, dtype=torch.bool) if kb is None else kb > NINF
     if layout == 'finite':                   # the two keys that KB_BIG lifts above all others carry opposite values
         v.view(B, Lk, H, dh)[0, 201] = -v.view(B, Lk, H, dh)[0, 200]

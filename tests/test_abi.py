@@ -198,10 +198,13 @@ def test_attention_scratch_queries_agree_with_the_dispatch_twin():
     L = _lib.lib()
     lens = (1, 70, 100, 128, 129, 200, 256, 384, 640, 1024, 1100, 1152, 2048, 6272, 8400)
     n = images = 0
-    for B, H, Lq, Lk, dh in itertools.product((1, 2, 3, 8), (1, 4, 8, 16), lens, lens, (8, 16, 32)):
+    for B, H, Lq, Lk, dh in itertools.product((1, 2, 3, 8), (1, 4, 8, 16), lens, lens, (8, 16, 32, 40, 64)):
         dims = (B, H, Lq, Lk, dh)
         ws = int(L.svol_attn_ws_bytes(*dims))
         assert ws == 4 * A.ws_floats(*dims), dims
+        if dh > 32:   # csrc/attention_wide.hip: no scratch, no single-pass image, whatever the scratch
+            assert ws == 0 and int(L.svol_attn_bwd_sp_image_bytes(*dims, 1 << 30, 1)) == 0, dims
+            assert A.plan(*dims, True, False) == dict(fwd='wide', bwd='wide', ksplit=1, tps=A.cdiv(Lk, A.KT), head_xcd=0), dims
         sp = 4 * A.sp_ws_floats(B, H, Lq, Lk)
         want = B * Lq * H * 32 * 4 if A.sp_shape_ok(*dims) and ws >= sp else 0
         assert int(L.svol_attn_bwd_sp_image_bytes(*dims, ws, 1)) == want, dims   # (1: SVOL_BF16)
@@ -209,7 +212,7 @@ def test_attention_scratch_queries_agree_with_the_dispatch_twin():
             assert int(L.svol_attn_bwd_sp_image_bytes(*dims, sp - 4, 1)) == 0, dims
             images += 1
         n += 1
-    assert n == 10800 and images > 0
+    assert n == 18000 and images > 0
 
 
 def test_reference_style_cli_trains_the_resnet_backbone_by_default():
