@@ -290,7 +290,7 @@ int svol_posenc_sine(const float* mask, void* pos, int64_t B, int64_t L, int64_t
  * + kbias) v; kbias [B,Lk] fp32 additive (0 / -inf = key_padding_mask, cross_modal_transformer.py:154)
  * or NULL.  lse2 [B,H,Lq] fp32 = log2-domain log-sum-exp saved for backward.  dh <= 64, dh % 8 == 0 (else SVOL_E_UNSUPPORTED).
  * Head widths 40 .. 64 (fp32, bf16, fp16; this entry and every svol_attn_* entry below) run on the two-pass kernels of
- * csrc/attention_wide.hip: same contract, no atomics (bit-reproducible), no use of ws -- svol_attn_ws_bytes and
+ * csrc/attention.hip's generic template at two d-tiles: same contract, no atomics (bit-reproducible), no use of ws -- svol_attn_ws_bytes and
  * svol_attn_bwd_sp_image_bytes return 0, svol_attn_bwd_zero_ws returns SVOL_E_UNSUPPORTED, SVOL_ATTN_DQ_PREZEROED is ignored;
  * everything said about the scratch below is about dh <= 32.
  * q_premul != 0: the caller already multiplied q by q_premul = scale*log2(e) (fused into the projection

@@ -2,14 +2,16 @@
 // never materialise the Lq x Lk score matrix (the reference's nn.MultiheadAttention writes
 // [B*h, L, L] = 9.4 GiB per layer at the benchmark size; cross_modal_transformer.py:139).
 //
-// Head dim is small (d_h = 32 at the benchmark size, 8 at the CPU config), so ONE 32x32 MFMA tile
-// spans the whole head dim.  All three kernels share one scheme built on the "swapped" product so
-// that softmax statistics are lane-local (MI355X guide: swapped QK^T, accumulator-as-next-operand):
+// This file holds the C-ABI entries and ONE generic kernel template on the element type T and the number ND of 32-column
+// d-tiles that span the head: ND = 1 for d_h <= 32 (d_h = 32 at the benchmark size, 8 at the CPU config), ND = 2 for
+// 32 < d_h <= 64 (d_h % 8 == 0: --nheads 4 at hidden_dim 256, --hidden_dim 512 / 384 at eight heads).  All three kernels share one
+// scheme built on the "swapped" product so that softmax statistics are lane-local (MI355X guide: swapped QK^T,
+// accumulator-as-next-operand):
 //
 //   "lane side"  : a block of 32 rows held in registers as the MFMA B operand (one row per lane&31)
 //   "reg side"   : 64-row tiles streamed through LDS, used as the MFMA A operand
-//   first product : X[reg row][lane row] = A_tile[reg row][:] . B_block[lane row][:]   (contract d)
-//   second product: Y[d][lane row]      += A_tileT[d][reg row] * f(X)[reg row][lane row]
+//   first product : X[reg row][lane row] = A_tile[reg row][0:32 ND] . B_block[lane row][0:32 ND]     (contract d)
+//   second product: Y_t[d][lane row]    += A_tileT[32 t + d][reg row] * f(X)[reg row][lane row]      (t < ND: one accumulator tile each)
 //                   f(X) is fed straight from the accumulator registers (no LDS round trip).
 //
 //   forward : lane = queries, reg = keys : X = K Q^T -> P ; O^T += V^T P
@@ -19,46 +21,61 @@
 // dQ is produced by its own pass instead of fp32 atomics: with d_h = 32 there are only 64 FLOP per
 // atomic byte and the chip-wide atomic rate (~1.3 TB/s) would bound the kernel (guide, Guideline 12).
 //
-// Element types: this file's generic template serves f32 (v_mfma_f32_32x32x2_f32, exact fp32 — the parity
-// mode); bf16 (v_mfma_f32_32x32x16_bf16) is dispatched to the tuned kernels of attention_bf16.hip.
-// Head widths 32 < d_h <= 64 (two d-tiles), all three element types, go to attention_wide.hip.
-// Softmax runs in the log2 domain with fp32 statistics; exp via v_exp_f32.
+// Columns >= d_h are zero in registers and LDS.  Plain compiler-scheduled HIP: no key split, no single pass, no atomics, no workspace —
+// results are bit-reproducible, and the same under SVOL_DETERMINISTIC=1.  Softmax runs in the log2 domain with fp32 statistics; exp via
+// v_exp_f32.
+//
+// Instances: <float, 1>, <float, 2> (v_mfma_f32_32x32x2_f32, exact fp32 — the parity mode), <bf16, 2>, <fp16, 2>
+// (v_mfma_f32_32x32x16_{bf16,f16}).  16-bit operands at d_h <= 32 are dispatched to the tuned kernels of attention_bf16.hip.
+//
+// LDS per workgroup (bytes; 64 rows x 32 ND d natural image, [32 ND d][64 rows] transposed image with a padded row stride):
+//                  natural   transposed   forward   dq       dk/dv
+//   f32,    ND = 1   8192       8704       17152    25344    34304
+//   16-bit, ND = 2   8192       9216       17664    25856    35328
+//   f32,    ND = 2  16384      17408       34048    50432    68096     (two workgroups per CU: 136192 of 163840)
 #include "attn_call.h"
 
 namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-template <typename T> struct AT;
-template <> struct AT<float> {
-    static constexpr int EPC = 4, NA = 4, CPR = 8, NAT_ROW = 128, TR_STRIDE = 64 * 4 + 16;
+// EPC: elements per 16-byte chunk; CPR: chunks per 32 ND-wide row; NA1: chunks a lane feeds to the first product; NA2: 16-byte operands
+// of one d-tile's second product (32 reg-side rows)
+template <typename T_, int ND_> struct AT {
+    typedef T_ T;
+    static constexpr int ND = ND_;
+    static constexpr bool H = sizeof(T) == 2;
+    // 16 bits at one d-tile belongs to attention_bf16.hip; the natural image's swizzle below is not the one that layout would need
+    static_assert(ND == 2 || (ND == 1 && !H), "instances: <float, 1>, <float, 2>, <bf16_t, 2>, <f16_t, 2>");
+    static constexpr int EPC = H ? 8 : 4, CPR = (H ? 4 : 8) * ND, NA1 = (H ? 2 : 4) * ND, NA2 = H ? 2 : 4;
+    static constexpr int NAT_ROW = (H ? 64 : 128) * ND, TR_STRIDE = H ? 64 * 2 + 16 : 64 * 4 + 16;
+    static constexpr int NAT = 64 * NAT_ROW, TR = 32 * ND * TR_STRIDE;
 };
 
 // ---- staging ---------------------------------------------------------------
-// natural image: [64 rows][32 d] (zero padded), 16-byte chunks XOR-swizzled against bank conflicts
-template <typename T>
+// natural image: [64 rows][32 ND d] (zero padded), 16-byte chunks XOR-swizzled against bank conflicts
+template <typename W>
 __device__ __forceinline__ int nat_off(int row, int ch) {
-    if constexpr (sizeof(T) == 2) return row * 64 + ((ch ^ ((row >> 2) & 3)) << 4);
-    else return row * 128 + ((ch ^ (row & 7)) << 4);
+    return row * W::NAT_ROW + ((ch ^ (row & (W::CPR - 1))) << 4);
 }
 
-// Stage 64 rows starting at row0 of a [rows, ld] matrix (head column offset already applied) into the
-// natural image `nat` and/or the transposed image `tr` ([32 d][64 rows], padded row stride).
-template <typename T>
-__device__ __forceinline__ void stage_tile(char* nat, char* tr, const T* g, int64_t ld, int row0, int limit, int dh,
-                                           int tid) {
-    constexpr int EPC = AT<T>::EPC, CPR = AT<T>::CPR, ST = AT<T>::TR_STRIDE;
+// Stage 64 rows starting at row0 of a [rows, ld] matrix (head column offset already applied) into the natural image `nat` and/or the
+// transposed image `tr`.
+template <typename W>
+__device__ __forceinline__ void stage_tile(char* nat, char* tr, const typename W::T* g, int64_t ld, int row0, int limit, int dh, int tid) {
+    constexpr int EPC = W::EPC, CPR = W::CPR, ST = W::TR_STRIDE;
     for (int c = tid; c < 64 * CPR; c += 256) {
         const int row = c / CPR, ch = c % CPR;
         const int d0 = ch * EPC;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (row0 + row < limit && d0 < dh) v = *reinterpret_cast<const uint4*>(g + (int64_t)(row0 + row) * ld + d0);
-        if (nat) *reinterpret_cast<uint4*>(nat + nat_off<T>(row, ch)) = v;
+        if (nat) *reinterpret_cast<uint4*>(nat + nat_off<W>(row, ch)) = v;
         if (tr) {
-            if constexpr (sizeof(T) == 2) {
-                const bf16x8 e = __builtin_bit_cast(bf16x8, v);
+            if constexpr (W::H) {
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-                for (int j = 0; j < 8; ++j) *reinterpret_cast<bf16_t*>(tr + (d0 + j) * ST + row * 2) = e[j];
+                for (int j = 0; j < 8; ++j)
+                    *reinterpret_cast<uint16_t*>(tr + (d0 + j) * ST + row * 2) = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
             } else {
                 const f32x4 e = __builtin_bit_cast(f32x4, v);
 #pragma unroll
@@ -68,61 +85,61 @@ __device__ __forceinline__ void stage_tile(char* nat, char* tr, const T* g, int6
     }
 }
 
-// lane-side block: this lane's row (r = lane & 31), the d-chunks its half (h = lane >> 5) feeds to the MFMA
-template <typename T>
-__device__ __forceinline__ void load_lane_block(uint4 (&out)[AT<T>::NA], const T* g, int64_t ld, int row, bool valid,
-                                                int dh, int h) {
-    constexpr int EPC = AT<T>::EPC, NA = AT<T>::NA;
+// the d-chunk that slot i of half h (= lane >> 5) feeds to the first product: 16-bit, MFMA step i contracts d in [16 i, 16 i + 16), eight
+// per half; f32, half h owns d in [16 ND h, 16 ND h + 16 ND) and step (i, e) contracts d = 4 i + e of both halves
+template <typename W>
+__device__ __forceinline__ int first_chunk(int i, int h) {
+    return W::H ? (2 * i + h) : (4 * W::ND * h + i);
+}
+
+// lane-side block: this lane's row (r = lane & 31), the d-chunks its half feeds to the MFMA
+template <typename W>
+__device__ __forceinline__ void load_lane_block(uint4 (&out)[W::NA1], const typename W::T* g, int64_t ld, int row, bool valid, int dh, int h) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int ch = (sizeof(T) == 2) ? (2 * i + h) : (4 * h + i);
-        const int d0 = ch * EPC;
+    for (int i = 0; i < W::NA1; ++i) {
+        const int d0 = first_chunk<W>(i, h) * W::EPC;
         out[i] = (valid && d0 < dh) ? *reinterpret_cast<const uint4*>(g + (int64_t)row * ld + d0) : make_uint4(0, 0, 0, 0);
     }
 }
 
 // A operand of the first product from the natural image: tile row `row`, contraction over d
-template <typename T>
-__device__ __forceinline__ void read_nat(uint4 (&a)[AT<T>::NA], const char* nat, int row, int h) {
+template <typename W>
+__device__ __forceinline__ void read_nat(uint4 (&a)[W::NA1], const char* nat, int row, int h) {
 #pragma unroll
-    for (int i = 0; i < AT<T>::NA; ++i) {
-        const int ch = (sizeof(T) == 2) ? (2 * i + h) : (4 * h + i);
-        a[i] = *reinterpret_cast<const uint4*>(nat + nat_off<T>(row, ch));
-    }
+    for (int i = 0; i < W::NA1; ++i) a[i] = *reinterpret_cast<const uint4*>(nat + nat_off<W>(row, first_chunk<W>(i, h)));
 }
 
-// A operand of the second product from the transposed image: row r = d, contraction over the 32 reg-side
-// rows of sub-tile t, in the order the accumulator registers of the first product present them
-template <typename T>
-__device__ __forceinline__ void read_tr(uint4 (&a)[AT<T>::NA], const char* tr, int r, int h, int t) {
-    constexpr int ST = AT<T>::TR_STRIDE;
-    if constexpr (sizeof(T) == 2) {
+// A operand of the second product from the transposed image: row d (0 .. 32 ND - 1), contraction over the 32 reg-side rows of sub-tile
+// t, in the order the accumulator registers of the first product present them (register 4 g + e holds reg-side row 8 g + 4 h + e)
+template <typename W>
+__device__ __forceinline__ void read_tr(uint4 (&a)[W::NA2], const char* tr, int d, int h, int t) {
+    constexpr int ST = W::TR_STRIDE;
+    if constexpr (W::H) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int col = 32 * t + 16 * s + 4 * h;
-            const uint2 p0 = *reinterpret_cast<const uint2*>(tr + r * ST + col * 2);
-            const uint2 p1 = *reinterpret_cast<const uint2*>(tr + r * ST + (col + 8) * 2);
+            const uint2 p0 = *reinterpret_cast<const uint2*>(tr + d * ST + col * 2);
+            const uint2 p1 = *reinterpret_cast<const uint2*>(tr + d * ST + (col + 8) * 2);
             a[s] = make_uint4(p0.x, p0.y, p1.x, p1.y);
         }
     } else {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int col = 32 * t + 8 * g + 4 * h;
-            a[g] = *reinterpret_cast<const uint4*>(tr + r * ST + col * 4);
+            a[g] = *reinterpret_cast<const uint4*>(tr + d * ST + col * 4);
         }
     }
 }
 
-template <typename T>
-__device__ __forceinline__ void mma_first(f32x16& acc, const uint4 (&a)[AT<T>::NA], const uint4 (&b)[AT<T>::NA]) {
-    if constexpr (sizeof(T) == 2) {
+template <typename W>
+__device__ __forceinline__ void mma_first(f32x16& acc, const uint4 (&a)[W::NA1], const uint4 (&b)[W::NA1]) {
+    if constexpr (W::H) {
+        typedef typename H16<typename W::T>::v8 v8;
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), __builtin_bit_cast(bf16x8, b[s]),
-                                                          acc, 0, 0, 0);
+        for (int s = 0; s < 2 * W::ND; ++s) acc = H16<typename W::T>::mfma32(__builtin_bit_cast(v8, a[s]), __builtin_bit_cast(v8, b[s]), acc);
     } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < 4 * W::ND; ++j) {
             const f32x4 af = __builtin_bit_cast(f32x4, a[j]), bf = __builtin_bit_cast(f32x4, b[j]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
@@ -130,35 +147,73 @@ __device__ __forceinline__ void mma_first(f32x16& acc, const uint4 (&a)[AT<T>::N
     }
 }
 
-// acc += A_tr * X, X = accumulator tile of the first product used directly as B operand
-template <typename T>
-__device__ __forceinline__ void mma_second(f32x16& acc, const uint4 (&a)[AT<T>::NA], const f32x16& x) {
-    if constexpr (sizeof(T) == 2) {
+// the accumulator tile of the first product as the B operand of the second: rounded to T once, used for every d-tile
+template <typename W>
+__device__ __forceinline__ void acc_operand(uint4 (&b)[W::NA2], const f32x16& x) {
+    if constexpr (W::H) {
+        typedef H16<typename W::T> HT;
+        typedef typename HT::v4 v4;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            bf16x8 b;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) b[j] = (bf16_t)x[8 * s + j];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), b, acc, 0, 0, 0);
+            const v4 lo = HT::cvt4(f32x4{x[8 * s + 0], x[8 * s + 1], x[8 * s + 2], x[8 * s + 3]});
+            const v4 hi = HT::cvt4(f32x4{x[8 * s + 4], x[8 * s + 5], x[8 * s + 6], x[8 * s + 7]});
+            const uint2 l = __builtin_bit_cast(uint2, lo), u = __builtin_bit_cast(uint2, hi);
+            b[s] = make_uint4(l.x, l.y, u.x, u.y);
         }
     } else {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 af = __builtin_bit_cast(f32x4, a[g]);
+        for (int g = 0; g < 4; ++g) b[g] = __builtin_bit_cast(uint4, f32x4{x[4 * g + 0], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]});
+    }
+}
+
+// acc += A_tr * X
+template <typename W>
+__device__ __forceinline__ void mma_second(f32x16& acc, const uint4 (&a)[W::NA2], const uint4 (&b)[W::NA2]) {
+    if constexpr (W::H) {
+        typedef typename H16<typename W::T>::v8 v8;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], x[4 * g + e], acc, 0, 0, 0);
+        for (int s = 0; s < 2; ++s) acc = H16<typename W::T>::mfma32(__builtin_bit_cast(v8, a[s]), __builtin_bit_cast(v8, b[s]), acc);
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 af = __builtin_bit_cast(f32x4, a[g]), bf = __builtin_bit_cast(f32x4, b[g]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
         }
     }
 }
 
-// accumulator [d][lane row] -> out[row][d] (T), optionally scaled
+// The accumulator tiles of a second product, Y_t[d - 32 t][lane row].  Two named tiles, not f32x16[ND]: under the array the compiler
+// assigns the two-tile kernels' registers differently, which cost the 16-bit dQ kernel 1.2 % (profiles/attn_generic.md).  At ND = 1
+// nothing reads t1 and what the kernels do to it is dead code.
+struct Tiles {
+    f32x16 t0, t1;
+    __device__ __forceinline__ void fill(float x) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { t0[i] = x; t1[i] = x; }
+    }
+};
+
+// every d-tile of the second product: Y_t += trT[32 t + r][sub-tile `sub`] * x
+template <typename W>
+__device__ __forceinline__ void mma_second_tiles(Tiles& y, const char* tr, int r, int h, int sub, const f32x16& x) {
+    uint4 xb[W::NA2], a[W::NA2];
+    acc_operand<W>(xb, x);
+    read_tr<W>(a, tr, r, h, sub);
+    mma_second<W>(y.t0, a, xb);
+    if constexpr (W::ND > 1) {
+        read_tr<W>(a, tr, 32 + r, h, sub);
+        mma_second<W>(y.t1, a, xb);
+    }
+}
+
+// accumulator tile t -> out[row][32 t + d] (T), optionally scaled
 template <typename T>
-__device__ __forceinline__ void store_acc_T(const f32x16& acc, T* out, int64_t ld, int row, bool valid, int dh, int h,
-                                            float mul) {
+__device__ __forceinline__ void store_acc_T(const f32x16& acc, int t, T* out, int64_t ld, int row, bool valid, int dh, int h, float mul) {
     if (!valid) return;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const int d0 = 8 * g + 4 * h;
+        const int d0 = 32 * t + 8 * g + 4 * h;
         if (d0 < dh) {
             Vec4<T> v;
 #pragma unroll
@@ -166,6 +221,11 @@ __device__ __forceinline__ void store_acc_T(const f32x16& acc, T* out, int64_t l
             v.store(out + (int64_t)row * ld + d0);
         }
     }
+}
+template <typename W>
+__device__ __forceinline__ void store_tiles(const Tiles& y, typename W::T* out, int64_t ld, int row, bool valid, int dh, int h, float mul) {
+    store_acc_T(y.t0, 0, out, ld, row, valid, dh, h, mul);
+    if constexpr (W::ND > 1) store_acc_T(y.t1, 1, out, ld, row, valid, dh, h, mul);
 }
 
 struct AttnArgs {
@@ -179,7 +239,7 @@ struct AttnArgs {
     float premul;
     // attention-probability dropout (nn.MultiheadAttention(dropout=p) in training mode, transformer.py:158-160,216-222): the
     // softmax numerators that feed P V are multiplied by a stateless keep mask (0 or 1/(1-p)) of the element index
-    // ((b*H + h)*Lq + q)*Lk + key — the row sums / lse stay those of the undropped softmax; backward regenerates the mask
+    // ((b*H + h)*Lq + q)*Lk + key — the row sums / lse stay those of the undropped softmax; both backward passes regenerate the mask
     float drop_p, drop_inv;
     uint64_t drop_seed;
     const int64_t* drop_step;   // device step counter (drop_seed_at), or null
@@ -189,26 +249,22 @@ struct AttnArgs {
 __device__ __forceinline__ float attn_drop(uint64_t seed, uint64_t row, int key, float p, float inv) {
     return dropout_scale(seed, row, (uint32_t)key, p, inv);
 }
-// the same for keys key0 (EVEN) and key0 + 1 of one row: one generator call for the pair
-__device__ __forceinline__ void attn_drop2(uint32_t rowmix, int key0, uint32_t thr16, float inv, float& s0, float& s1) {
+// the same for keys key0 (EVEN) and key0 + 1 of one row, onto x[i] and x[i + 1]: one generator call for the pair
+__device__ __forceinline__ void attn_drop2(f32x16& x, int i, uint32_t rowmix, int key0, uint32_t thr16, float inv) {
     const uint32_t bits = drop_bits(rowmix, (uint32_t)key0 >> 1);
-    s0 = drop_pick(bits, 0u, thr16, inv);
-    s1 = drop_pick(bits, 1u, thr16, inv);
+    x[i] *= drop_pick(bits, 0u, thr16, inv);
+    x[i + 1] *= drop_pick(bits, 1u, thr16, inv);
 }
 
-template <typename T> struct Smem {
-    static constexpr int NAT = 64 * AT<T>::NAT_ROW;
-    static constexpr int TR = 32 * AT<T>::TR_STRIDE;
-};
-
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, int ND>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
+    typedef AT<T, ND> W;
     const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
-    __shared__ __attribute__((aligned(16))) char smem[Smem<T>::NAT + Smem<T>::TR + 64 * 4];
+    __shared__ __attribute__((aligned(16))) char smem[W::NAT + W::TR + 64 * 4];
     char* sK = smem;
-    char* sVt = smem + Smem<T>::NAT;
-    float* sbias = reinterpret_cast<float*>(smem + Smem<T>::NAT + Smem<T>::TR);
+    char* sVt = smem + W::NAT;
+    float* sbias = reinterpret_cast<float*>(smem + W::NAT + W::TR);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -220,19 +276,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
     const T* V = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.Lk * p.ldv + hh * p.dh;
     const float* kb = p.kbias ? p.kbias + (int64_t)b * p.Lk : nullptr;
     const float sc = p.premul != 0.f ? 1.f : p.scale * LOG2E;
+    const uint64_t drow = ((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0);
 
-    uint4 qb[AT<T>::NA];
-    load_lane_block<T>(qb, Q, p.ldq, qrow, qvalid, p.dh, h);
+    uint4 qb[W::NA1];
+    load_lane_block<W>(qb, Q, p.ldq, qrow, qvalid, p.dh, h);
 
     float m = -INFINITY, l = 0.f;
-    f32x16 O;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) O[i] = 0.f;
+    Tiles O;
+    O.fill(0.f);
 
     for (int kt = 0; kt < p.Lk; kt += 64) {
         __syncthreads();
-        stage_tile<T>(sK, nullptr, K, p.ldk, kt, p.Lk, p.dh, tid);
-        stage_tile<T>(nullptr, sVt, V, p.ldv, kt, p.Lk, p.dh, tid);
+        stage_tile<W>(sK, nullptr, K, p.ldk, kt, p.Lk, p.dh, tid);
+        stage_tile<W>(nullptr, sVt, V, p.ldv, kt, p.Lk, p.dh, tid);
         if (tid < 64) {
             const int key = kt + tid;
             sbias[tid] = key < p.Lk ? (kb ? kb[key] * LOG2E : 0.f) : -INFINITY;
@@ -240,12 +296,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         __syncthreads();
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
-            uint4 ka[AT<T>::NA];
-            read_nat<T>(ka, sK, sub * 32 + r, h);
             f32x16 S;
 #pragma unroll
             for (int i = 0; i < 16; ++i) S[i] = 0.f;
-            mma_first<T>(S, ka, qb);
+            {
+                uint4 ka[W::NA1];
+                read_nat<W>(ka, sK, sub * 32 + r, h);
+                mma_first<W>(S, ka, qb);
+            }
             float mloc = -INFINITY;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -269,35 +327,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
             l = l * alpha + ls;
             m = m_new;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) O[i] *= alpha;
+            for (int i = 0; i < 16; ++i) { O.t0[i] *= alpha; O.t1[i] *= alpha; }
             if (p.drop_p > 0.f) {
-                const uint32_t rm = drop_row(drop_seed32(dseed), (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)));
+                const uint32_t rm = drop_row(drop_seed32(dseed), drow);
                 const uint32_t thr = drop_thr16(p.drop_p);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
-                    for (int e = 0; e < 4; e += 2) {   // (the lane's keys 8g + 4h + e: pairs share one generator call)
-                        float s0, s1;
-                        attn_drop2(rm, kt + sub * 32 + 8 * g + 4 * h + e, thr, p.drop_inv, s0, s1);
-                        S[4 * g + e] *= s0;
-                        S[4 * g + e + 1] *= s1;
+                    for (int e = 0; e < 4; e += 2) {   // (the lane's keys 8g + 4h + e: an even / odd pair shares one generator call)
+                        attn_drop2(S, 4 * g + e, rm, kt + sub * 32 + 8 * g + 4 * h + e, thr, p.drop_inv);
                     }
             }
-            uint4 va[AT<T>::NA];
-            read_tr<T>(va, sVt, r, h, sub);
-            mma_second<T>(O, va, S);
+            mma_second_tiles<W>(O, sVt, r, h, sub, S);
         }
     }
     const float lt = l + __shfl_xor(l, 32, 64);
     const float inv = lt > 0.f ? 1.f / lt : 0.f;
     T* Oo = reinterpret_cast<T*>(p.out_o) + (int64_t)b * p.Lq * p.ldo + hh * p.dh;
-    store_acc_T<T>(O, Oo, p.ldo, qrow, qvalid, p.dh, h, inv);
+    store_tiles<W>(O, Oo, p.ldo, qrow, qvalid, p.dh, h, inv);
     if (qvalid && h == 0) p.lse2[((int64_t)b * p.H + hh) * p.Lq + qrow] = m + __builtin_amdgcn_logf(lt);
 }
 
 // delta[b,h,q] = sum_d dO[q, h*dh + d] * O[q, h*dh + d]
 template <typename T>
-__global__ void attn_delta_kernel(AttnArgs p) {
+__global__ __launch_bounds__(256) void attn_delta_kernel(AttnArgs p) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t total = (int64_t)p.B * p.Lq * p.H;
     if (idx >= total) return;
@@ -318,14 +371,15 @@ __global__ void attn_delta_kernel(AttnArgs p) {
 }
 
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, int ND>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
+    typedef AT<T, ND> W;
     const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
-    __shared__ __attribute__((aligned(16))) char smem[2 * Smem<T>::NAT + Smem<T>::TR + 64 * 4];
+    __shared__ __attribute__((aligned(16))) char smem[2 * W::NAT + W::TR + 64 * 4];
     char* sK = smem;
-    char* sV = smem + Smem<T>::NAT;
-    char* sKt = smem + 2 * Smem<T>::NAT;
-    float* sbias = reinterpret_cast<float*>(smem + 2 * Smem<T>::NAT + Smem<T>::TR);
+    char* sV = smem + W::NAT;
+    char* sKt = smem + 2 * W::NAT;
+    float* sbias = reinterpret_cast<float*>(smem + 2 * W::NAT + W::TR);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -338,22 +392,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
     const T* V = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.Lk * p.ldv + hh * p.dh;
     const float* kb = p.kbias ? p.kbias + (int64_t)b * p.Lk : nullptr;
     const float sc = p.premul != 0.f ? 1.f : p.scale * LOG2E;
+    const uint64_t drow = ((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0);
 
-    uint4 qb[AT<T>::NA], dob[AT<T>::NA];
-    load_lane_block<T>(qb, Q, p.ldq, qrow, qvalid, p.dh, h);
-    load_lane_block<T>(dob, dO, p.lddo, qrow, qvalid, p.dh, h);
+    uint4 qb[W::NA1], dob[W::NA1];
+    load_lane_block<W>(qb, Q, p.ldq, qrow, qvalid, p.dh, h);
+    load_lane_block<W>(dob, dO, p.lddo, qrow, qvalid, p.dh, h);
     const int64_t sidx = ((int64_t)b * p.H + hh) * p.Lq + qrow;
     const float lse = qvalid ? p.lse2[sidx] : INFINITY;
     const float dl = qvalid ? p.delta[sidx] : 0.f;
 
-    f32x16 dQ;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dQ[i] = 0.f;
+    Tiles dQ;
+    dQ.fill(0.f);
 
     for (int kt = 0; kt < p.Lk; kt += 64) {
         __syncthreads();
-        stage_tile<T>(sK, sKt, K, p.ldk, kt, p.Lk, p.dh, tid);
-        stage_tile<T>(sV, nullptr, V, p.ldv, kt, p.Lk, p.dh, tid);
+        stage_tile<W>(sK, sKt, K, p.ldk, kt, p.Lk, p.dh, tid);
+        stage_tile<W>(sV, nullptr, V, p.ldv, kt, p.Lk, p.dh, tid);
         if (tid < 64) {
             const int key = kt + tid;
             sbias[tid] = key < p.Lk ? (kb ? kb[key] * LOG2E : 0.f) : -INFINITY;
@@ -361,14 +415,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
         __syncthreads();
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
-            uint4 a[AT<T>::NA];
-            read_nat<T>(a, sK, sub * 32 + r, h);
             f32x16 S, dP;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
-            mma_first<T>(S, a, qb);
-            read_nat<T>(a, sV, sub * 32 + r, h);
-            mma_first<T>(dP, a, dob);
+            {
+                uint4 a[W::NA1];
+                read_nat<W>(a, sK, sub * 32 + r, h);
+                mma_first<W>(S, a, qb);
+                read_nat<W>(a, sV, sub * 32 + r, h);
+                mma_first<W>(dP, a, dob);
+            }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 bb = *reinterpret_cast<const f32x4*>(sbias + sub * 32 + 8 * g + 4 * h);
@@ -376,30 +432,28 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
                 for (int e = 0; e < 4; ++e) {
                     const float pe = __builtin_amdgcn_exp2f(S[4 * g + e] * sc + bb[e] - lse);
                     float dpe = dP[4 * g + e];
-                    if (p.drop_p > 0.f)
-                        dpe *= attn_drop(dseed, (((uint64_t)b * p.H + hh) * p.Lq + (qvalid ? qrow : 0)),
-                                         kt + sub * 32 + 8 * g + 4 * h + e, p.drop_p, p.drop_inv);
+                    if (p.drop_p > 0.f) dpe *= attn_drop(dseed, drow, kt + sub * 32 + 8 * g + 4 * h + e, p.drop_p, p.drop_inv);
                     S[4 * g + e] = pe * (dpe - dl) * p.scale;
                 }
             }
-            read_tr<T>(a, sKt, r, h, sub);
-            mma_second<T>(dQ, a, S);
+            mma_second_tiles<W>(dQ, sKt, r, h, sub, S);
         }
     }
     T* dQo = reinterpret_cast<T*>(p.dq) + (int64_t)b * p.Lq * p.lddq + hh * p.dh;
-    store_acc_T<T>(dQ, dQo, p.lddq, qrow, qvalid, p.dh, h, 1.f);
+    store_tiles<W>(dQ, dQo, p.lddq, qrow, qvalid, p.dh, h, 1.f);
 }
 
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, int ND>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
+    typedef AT<T, ND> W;
     const uint64_t dseed = drop_seed_at(p.drop_seed, p.drop_step);   // (one uniform load per kernel)
-    __shared__ __attribute__((aligned(16))) char smem[2 * Smem<T>::NAT + 2 * Smem<T>::TR + 128 * 4];
+    __shared__ __attribute__((aligned(16))) char smem[2 * W::NAT + 2 * W::TR + 128 * 4];
     char* sQ = smem;
-    char* sdO = smem + Smem<T>::NAT;
-    char* sQt = smem + 2 * Smem<T>::NAT;
-    char* sdOt = smem + 2 * Smem<T>::NAT + Smem<T>::TR;
-    float* slse = reinterpret_cast<float*>(smem + 2 * Smem<T>::NAT + 2 * Smem<T>::TR);
+    char* sdO = smem + W::NAT;
+    char* sQt = smem + 2 * W::NAT;
+    char* sdOt = smem + 2 * W::NAT + W::TR;
+    float* slse = reinterpret_cast<float*>(smem + 2 * W::NAT + 2 * W::TR);
     float* sdl = slse + 64;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -416,18 +470,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
     const float* lse_g = p.lse2 + ((int64_t)b * p.H + hh) * p.Lq;
     const float* dl_g = p.delta + ((int64_t)b * p.H + hh) * p.Lq;
 
-    uint4 kbk[AT<T>::NA], vbk[AT<T>::NA];
-    load_lane_block<T>(kbk, K, p.ldk, krow, kvalid, p.dh, h);
-    load_lane_block<T>(vbk, V, p.ldv, krow, kvalid, p.dh, h);
+    uint4 kbk[W::NA1], vbk[W::NA1];
+    load_lane_block<W>(kbk, K, p.ldk, krow, kvalid, p.dh, h);
+    load_lane_block<W>(vbk, V, p.ldv, krow, kvalid, p.dh, h);
 
-    f32x16 dK, dV;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dK[i] = 0.f; dV[i] = 0.f; }
+    Tiles dK, dV;
+    dK.fill(0.f);
+    dV.fill(0.f);
 
     for (int qt = 0; qt < p.Lq; qt += 64) {
         __syncthreads();
-        stage_tile<T>(sQ, sQt, Q, p.ldq, qt, p.Lq, p.dh, tid);
-        stage_tile<T>(sdO, sdOt, dO, p.lddo, qt, p.Lq, p.dh, tid);
+        stage_tile<W>(sQ, sQt, Q, p.ldq, qt, p.Lq, p.dh, tid);
+        stage_tile<W>(sdO, sdOt, dO, p.lddo, qt, p.Lq, p.dh, tid);
         if (tid < 64) {
             const int qi = qt + tid;
             slse[tid] = qi < p.Lq ? lse_g[qi] : INFINITY;
@@ -436,54 +490,75 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs p) {
         __syncthreads();
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
-            uint4 a[AT<T>::NA];
-            read_nat<T>(a, sQ, sub * 32 + r, h);
             f32x16 S, dP;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
-            mma_first<T>(S, a, kbk);  // S[q][key]
+            {
+                uint4 a[W::NA1];
+                read_nat<W>(a, sQ, sub * 32 + r, h);
+                mma_first<W>(S, a, kbk);  // S[q][key]
+                read_nat<W>(a, sdO, sub * 32 + r, h);
+                mma_first<W>(dP, a, vbk);  // dP[q][key] = dO V^T
+            }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 ls = *reinterpret_cast<const f32x4*>(slse + sub * 32 + 8 * g + 4 * h);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) S[4 * g + e] = __builtin_amdgcn_exp2f(S[4 * g + e] * sc + kbl - ls[e]);
             }
-            f32x16 MS;   // keep-mask scales of this block (all ones without dropout)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) MS[i] = 1.f;
-            if (p.drop_p > 0.f) {
+            f32x16 Pd = S;   // P as the dV product takes it
+            if (p.drop_p > 0.f) {   // the keep-mask scales of this block go onto P for dV and onto dP for dS
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int qi = min(qt + sub * 32 + 8 * g + 4 * h + e, p.Lq - 1);
-                        MS[4 * g + e] = attn_drop(dseed, (((uint64_t)b * p.H + hh) * p.Lq + qi), kvalid ? krow : 0,
-                                                  p.drop_p, p.drop_inv);
+                        const float ms = attn_drop(dseed, ((uint64_t)b * p.H + hh) * p.Lq + qi, kvalid ? krow : 0, p.drop_p, p.drop_inv);
+                        Pd[4 * g + e] = S[4 * g + e] * ms;
+                        dP[4 * g + e] *= ms;
                     }
             }
-            read_tr<T>(a, sdOt, r, h, sub);
-            {
-                f32x16 Pd = S;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) Pd[i] *= MS[i];
-                mma_second<T>(dV, a, Pd);  // dV^T += dO^T (P . mask)
-            }
-            read_nat<T>(a, sdO, sub * 32 + r, h);
-            mma_first<T>(dP, a, vbk);  // dP[q][key] = dO V^T
+            mma_second_tiles<W>(dV, sdOt, r, h, sub, Pd);  // dV^T += dO^T (P . mask)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 dd = *reinterpret_cast<const f32x4*>(sdl + sub * 32 + 8 * g + 4 * h);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) S[4 * g + e] = S[4 * g + e] * (dP[4 * g + e] * MS[4 * g + e] - dd[e]) * p.scale;
+                for (int e = 0; e < 4; ++e) S[4 * g + e] = S[4 * g + e] * (dP[4 * g + e] - dd[e]) * p.scale;
             }
-            read_tr<T>(a, sQt, r, h, sub);
-            mma_second<T>(dK, a, S);  // dK^T += Q^T dS
+            mma_second_tiles<W>(dK, sQt, r, h, sub, S);  // dK^T += Q^T dS
         }
     }
     T* dKo = reinterpret_cast<T*>(p.dk) + (int64_t)b * p.Lk * p.lddk + hh * p.dh;
     T* dVo = reinterpret_cast<T*>(p.dv) + (int64_t)b * p.Lk * p.lddv + hh * p.dh;
-    store_acc_T<T>(dK, dKo, p.lddk, krow, kvalid, p.dh, h, p.premul != 0.f ? 1.f / p.premul : 1.f);
-    store_acc_T<T>(dV, dVo, p.lddv, krow, kvalid, p.dh, h, 1.f);
+    store_tiles<W>(dK, dKo, p.lddk, krow, kvalid, p.dh, h, p.premul != 0.f ? 1.f / p.premul : 1.f);
+    store_tiles<W>(dV, dVo, p.lddv, krow, kvalid, p.dh, h, 1.f);
+}
+
+// a validated call (check_call): dh <= 32 ND
+template <typename T, int ND>
+int fwd_launch(const AttnCall& c) {
+    AttnArgs p{};
+    attn_fill(p, c);
+    dim3 grid((unsigned)((c.Lq + 127) / 128), (unsigned)c.H, (unsigned)c.B);
+    hipLaunchKernelGGL((attn_fwd_kernel<T, ND>), grid, dim3(256), 0, c.stream, p);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+template <typename T, int ND>
+int bwd_launch(const AttnCall& c) {
+    AttnArgs p{};
+    attn_fill(p, c);
+    const int64_t total = (int64_t)c.B * c.Lq * c.H;
+    dim3 gd((unsigned)((total + 255) / 256));
+    dim3 gq((unsigned)((c.Lq + 127) / 128), (unsigned)c.H, (unsigned)c.B);
+    dim3 gk((unsigned)((c.Lk + 127) / 128), (unsigned)c.H, (unsigned)c.B);
+    hipLaunchKernelGGL(attn_delta_kernel<T>, gd, dim3(256), 0, c.stream, p);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, ND>), gq, dim3(256), 0, c.stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, ND>), gk, dim3(256), 0, c.stream, p);
+    if (c.ev_prep) (void)hipEventRecord(static_cast<hipEvent_t>(c.ev_prep), c.stream);   // behind the last launch: nothing here uses a workspace
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
 }
 
 int check_common(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, int dtype) {
@@ -520,7 +595,7 @@ extern "C" {
 
 int64_t svol_attn_ws_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh) {
     if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || dh <= 0 || B > (1 << 24) || Lq > (1 << 24) || Lk > (1 << 24)) return 0;
-    if (dh > 32) return 0;   // the wide kernels (attention_wide.hip) use no workspace
+    if (dh > 32) return 0;   // the generic kernels use no workspace
     return 4 * svol_attn_ws_floats_bf16((int)B, (int)H, (int)Lq, (int)Lk, (int)dh);
 }
 
@@ -534,14 +609,9 @@ int svol_attn_fwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t 
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
     c.drop_p = dropout_p; c.drop_seed = seed; c.drop_step = seed_step_dev; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, false, B, H, Lq, Lk, dh, dtype)) return rc;
-    if (dh > 32) return svol_attn_wide_fwd_launch(c, dtype);
+    if (dh > 32) return dtype == SVOL_BF16 ? fwd_launch<bf16_t, 2>(c) : dtype == SVOL_F16 ? fwd_launch<f16_t, 2>(c) : fwd_launch<float, 2>(c);
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_fwd_bf16_launch : svol_attn_fwd_f16_launch)(c);
-    AttnArgs p{};
-    attn_fill(p, c);
-    dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)H, (unsigned)B);
-    hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), 0, c.stream, p);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
+    return fwd_launch<float, 1>(c);
 }
 int svol_attn_fwd_dropout(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
                           int64_t ldo, float* lse2, const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
@@ -569,20 +639,10 @@ static int attn_bwd_impl(const void* q, int64_t ldq, const void* k, int64_t ldk,
     c.scale = scale; c.premul = q_premul; c.ws = static_cast<float*>(ws); c.ws_bytes = ws_bytes;
     c.drop_p = drop_p; c.drop_seed = drop_seed; c.drop_step = drop_step; c.flags = flags; c.ev_prep = ev_prep; c.stream = reinterpret_cast<hipStream_t>(stream);
     if (const int rc = check_call(c, true, B, H, Lq, Lk, dh, dtype)) return rc;
-    if (dh > 32) return svol_attn_wide_bwd_launch(c, dtype);   // (no dQ image: SVOL_ATTN_DQ_PREZEROED means nothing there)
+    // (the generic kernels keep no dQ image: SVOL_ATTN_DQ_PREZEROED means nothing to them)
+    if (dh > 32) return dtype == SVOL_BF16 ? bwd_launch<bf16_t, 2>(c) : dtype == SVOL_F16 ? bwd_launch<f16_t, 2>(c) : bwd_launch<float, 2>(c);
     if (svol_is16(dtype)) return (dtype == SVOL_BF16 ? svol_attn_bwd_bf16_launch : svol_attn_bwd_f16_launch)(c);
-    AttnArgs p{};
-    attn_fill(p, c);
-    const int64_t total = B * Lq * H;
-    dim3 gd((unsigned)((total + 255) / 256));
-    dim3 gq((unsigned)((Lq + 127) / 128), (unsigned)H, (unsigned)B);
-    dim3 gk((unsigned)((Lk + 127) / 128), (unsigned)H, (unsigned)B);
-    hipLaunchKernelGGL(attn_delta_kernel<float>, gd, dim3(256), 0, c.stream, p);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, gq, dim3(256), 0, c.stream, p);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<float>, gk, dim3(256), 0, c.stream, p);
-    if (ev_prep) (void)hipEventRecord(static_cast<hipEvent_t>(ev_prep), c.stream);
-    SVOL_CHECK_LAUNCH();
-    return SVOL_OK;
+    return bwd_launch<float, 1>(c);
 }
 
 int svol_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,

@@ -42,7 +42,3 @@ template <typename A> static inline void attn_fill(A& p, const AttnCall& c) {
 SVOL_ATTN_H16_ENTRIES(bf16)
 SVOL_ATTN_H16_ENTRIES(f16)
 #undef SVOL_ATTN_H16_ENTRIES
-
-// attention_wide.hip: head widths 32 < dh <= 64 of a validated call, f32 / bf16 / fp16 (dtype: SVOL_*); no workspace
-int svol_attn_wide_fwd_launch(const AttnCall& c, int dtype);
-int svol_attn_wide_bwd_launch(const AttnCall& c, int dtype);

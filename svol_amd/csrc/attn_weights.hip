@@ -72,7 +72,7 @@ int launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const float* 
     if (dh == 8) SVOL_AW(8);
     else if (dh == 16) SVOL_AW(16);
     else if (dh == 32) SVOL_AW(32);
-    else if (dh == 40) SVOL_AW(40);   // the widths svol_attn_fwd serves above 32 (attention_wide.hip)
+    else if (dh == 40) SVOL_AW(40);   // the widths svol_attn_fwd serves above 32 (attention.hip, two d-tiles)
     else if (dh == 48) SVOL_AW(48);
     else if (dh == 56) SVOL_AW(56);
     else if (dh == 64) SVOL_AW(64);

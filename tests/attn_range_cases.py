@@ -78,7 +78,7 @@ def sp_ws_floats(B, H, Lq, Lk):
 
 def ws_floats(B, H, Lq, Lk, dh):
     """svol_attn_ws_bytes / 4"""
-    if dh > 32:                              # csrc/attention_wide.hip: no workspace
+    if dh > 32:                              # csrc/attention.hip, two d-tiles: no workspace
         return 0
     ks, _ = plan_ksplit(B, H, Lq, Lk, dh)
     if ks < 2:
@@ -101,7 +101,7 @@ def head_xcd(B, H, dh):
 def plan(B, H, Lq, Lk, dh, premul, has_kbias, ws_bytes=None, deterministic=False):
     """the kernels one forward and one backward of this launch take (drop_p = 0, the scratch ops.attn_fwd hands over unless given)
     -> dict(fwd, bwd, ksplit, tps, head_xcd)"""
-    if dh > 32:                              # csrc/attention_wide.hip: one forward, one backward, no key split, no head-to-XCD deal
+    if dh > 32:                              # csrc/attention.hip, two d-tiles: one forward, one backward, no key split, no head-to-XCD deal
         return dict(fwd='wide', bwd='wide', ksplit=1, tps=cdiv(Lk, KT), head_xcd=0)
     ws_bytes = 4 * ws_floats(B, H, Lq, Lk, dh) if ws_bytes is None else ws_bytes
     ws = ws_bytes > 0

@@ -1,4 +1,4 @@
-"""Attention at head widths 40-64 (csrc/attention_wide.hip) at peaked scores and irregular key masks: the case table, the fault
+"""Attention at head widths 40-64 (csrc/attention.hip's generic template at two d-tiles) at peaked scores and irregular key masks: the case table, the fault
 runners and the attention-weights reference (plain torch on the CPU, importable without the device library).  The machinery -- the
 planted inputs, the mask layouts, the figures -- is tests/attn_range_cases.py's, given this table instead of its own.
 tests/test_attn_wide_range_cases.py holds this file to fp64 on the CPU, tests/test_gpu_attn_wide_range.py runs the cases on the device.

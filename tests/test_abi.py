@@ -202,7 +202,7 @@ def test_attention_scratch_queries_agree_with_the_dispatch_twin():
         dims = (B, H, Lq, Lk, dh)
         ws = int(L.svol_attn_ws_bytes(*dims))
         assert ws == 4 * A.ws_floats(*dims), dims
-        if dh > 32:   # csrc/attention_wide.hip: no scratch, no single-pass image, whatever the scratch
+        if dh > 32:   # csrc/attention.hip's generic kernels at two d-tiles: no scratch, no single-pass image, whatever the scratch
             assert ws == 0 and int(L.svol_attn_bwd_sp_image_bytes(*dims, 1 << 30, 1)) == 0, dims
             assert A.plan(*dims, True, False) == dict(fwd='wide', bwd='wide', ksplit=1, tps=A.cdiv(Lk, A.KT), head_xcd=0), dims
         sp = 4 * A.sp_ws_floats(B, H, Lq, Lk)

@@ -1,5 +1,5 @@
-"""Attention at head widths 32 < dh <= 64 (csrc/attention_wide.hip: two d-tiles, f32 / bf16 / fp16 from one template) through
-ops.attn_fwd / ops.attn_bwd, i.e. svol_attn_fwd_dropout / svol_attn_bwd_dropout.
+"""The generic attention template of csrc/attention.hip through ops.attn_fwd / ops.attn_bwd, i.e. svol_attn_fwd_dropout /
+svol_attn_bwd_dropout: head widths 32 < dh <= 64 (two d-tiles, f32 / bf16 / fp16) and, in fp32, dh <= 32 (one d-tile).
 
 Inputs, reference and bars are those of tests/gpu_checks.py::check_attention: _rnd with seeds 30-33 (q and k scaled by 1.5), fp64 by
 autograd, whole-tensor rel_err at TOL[dtype] for o, 2 TOL[dtype] for dq / dk / dv, 1e-5 (fp32) / 3e-3 (16-bit) for lse2; each case with
@@ -11,6 +11,9 @@ Each case is the smallest shape that reaches a distinct way to go wrong (B, H, L
   (2,2,7,333,64,T)    few queries, many key tiles                 (1,4,200,256,64,F)  full key tiles
   (1,2,100,128,48,F)  zero-padded second d-tile                   (2,3,33,97,40,T)    zero-padded second d-tile, masked
   (1,1,1,1,64,F)      degenerate 1 x 1
+NARROW holds the one-tile instance <float, 1> to the same assertions and bars, fp32 only (16-bit operands at dh <= 32 take
+csrc/attention_bf16.hip): widths below one tile (8, 24), a ragged last query block, a ragged last key tile, dead keys and 1 x 1 — where a
+wrong chunk map or store guard in the template's traits would show.
 The 16-bit rounding model (attn_dropout_ref.emulate with rounder(dtype) against ::reference) stays within 0.42 of its bar at every one
 of them, both premuls, without dropout and with dropout 0.1 / 0.25 under the twin's mask (worst: bf16 o of the 7 x 333 case).  Measured
 on the device: 0.43 of the bar at the worst (the same tensor), fp32 below 0.06 (profiles/attn_wide.md).
@@ -38,11 +41,17 @@ LSE_BAR = {FP32: 1e-5, BF16: 3e-3, FP16: 3e-3}
 CASES = [(2, 4, 70, 150, 64, True), (1, 2, 129, 64, 64, False), (2, 2, 7, 333, 64, True), (1, 4, 200, 256, 64, False),
          (1, 2, 100, 128, 48, False), (2, 3, 33, 97, 40, True), (1, 1, 1, 1, 64, False)]
 DROP_CASES = CASES[:-1]   # (the 1 x 1 case's reference gradients vanish)
+# one d-tile, fp32 only (16-bit operands at dh <= 32 take csrc/attention_bf16.hip, which has other bars and uses atomics)
+NARROW = [(2, 4, 70, 150, 32, True), (1, 2, 129, 64, 24, False), (2, 3, 33, 97, 8, True), (1, 1, 1, 1, 16, False)]
+POINTS = [(c, d) for c in CASES for d in DTYPES] + [(c, FP32) for c in NARROW]
+DROP_POINTS = [(c, d) for c in DROP_CASES for d in DTYPES] + [(c, FP32) for c in NARROW[:-1]]
+ZONE_POINTS = [(c, d) for c in (CASES[0], CASES[5]) for d in DTYPES] + [(NARROW[1], FP32)]
 DROP_SEED = (7 << 44) + (3 << 12) + 1   # the model's form (base << 44) + (step << 12) + site
 NEG0 = -2147483648   # 0x80000000 as int32: fp32 -0.0 (tests/test_gpu_guards.py)
 SVOL_E_UNSUPPORTED = -2   # include/svol_hip.h
 _cid = lambda c: 'B{}H{}q{}k{}d{}{}'.format(*c[:5], 'm' if c[5] else '')
 _did = lambda d: R.DT_NAME[d]
+_pids = lambda points: [f'{_cid(c)}-{_did(d)}' for c, d in points]
 
 
 def _kbias(case):
@@ -142,8 +151,7 @@ def hold(case, dtype, c, got, what):
 
 
 @pytest.mark.parametrize('premul_on', [False, True], ids=['plain', 'premul'])
-@pytest.mark.parametrize('dtype', DTYPES, ids=_did)
-@pytest.mark.parametrize('case', CASES, ids=_cid)
+@pytest.mark.parametrize('case,dtype', POINTS, ids=_pids(POINTS))
 def test_forward_and_backward_against_fp64(case, dtype, premul_on):
     c = point(case, dtype, premul_on, 0.0)
     a = launch(case, c)
@@ -158,8 +166,7 @@ def test_forward_and_backward_against_fp64(case, dtype, premul_on):
 
 @pytest.mark.parametrize('p', [0.1, 0.25], ids=lambda p: f'p{p}')
 @pytest.mark.parametrize('premul_on', [False, True], ids=['plain', 'premul'])
-@pytest.mark.parametrize('dtype', DTYPES, ids=_did)
-@pytest.mark.parametrize('case', DROP_CASES, ids=_cid)
+@pytest.mark.parametrize('case,dtype', DROP_POINTS, ids=_pids(DROP_POINTS))
 def test_dropout_against_fp64_under_the_twins_mask(case, dtype, premul_on, p):
     c = point(case, dtype, premul_on, p)
     a = launch(case, c, p)
@@ -220,8 +227,7 @@ class RedZone:
         return int((rest != NEG0).sum())
 
 
-@pytest.mark.parametrize('dtype', DTYPES, ids=_did)
-@pytest.mark.parametrize('case', [CASES[0], CASES[5]], ids=_cid)
+@pytest.mark.parametrize('case,dtype', ZONE_POINTS, ids=_pids(ZONE_POINTS))
 def test_outputs_stay_inside_their_buffers(case, dtype):
     """o, dq, dk, dv as interior row / column ranges of sentinel-filled buffers (ld > H dh), lse2 and delta as interior ranges too"""
     from svol_amd import _lib, ops
@@ -229,7 +235,7 @@ def test_outputs_stay_inside_their_buffers(case, dtype):
     d = H * dh
     c = point(case, dtype, True, 0.0)
     q, k, v, do = (c[n].to(DEV) for n in ('q', 'k', 'v', 'do'))
-    kb = c['kb'].to(DEV)
+    kb = None if c['kb'] is None else c['kb'].to(DEV)
     zo, zq, zk, zv = RedZone(B * Lq, d, dtype), RedZone(B * Lq, d, dtype), RedZone(B * Lk, d, dtype), RedZone(B * Lk, d, dtype)
     zl, zd = RedZone(1, B * H * Lq, FP32, pad_cols=64), RedZone(1, 3 * B * H * Lq, FP32, pad_cols=64)
     lse2, delta = zl.view[0], zd.view[0]

@@ -1,4 +1,4 @@
-"""The head-width 40-64 attention kernels (csrc/attention_wide.hip) and the attention weights recomputed from their lse2
+"""The head-width 40-64 attention kernels (csrc/attention.hip at two d-tiles) and the attention weights recomputed from their lse2
 (csrc/attn_weights.hip) on the device at peaked scores and irregular key masks, against fp64.  Cases, layouts and faults:
 tests/attn_wide_range_cases.py; planted inputs and figures: tests/attn_range_cases.py.
 

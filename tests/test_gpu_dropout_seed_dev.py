@@ -83,7 +83,7 @@ def test_neighbouring_counters_give_independent_masks():
 # ----------------------------------------------------------------------------------------------------------------------
 PROBE_K = 3
 PROBE_SEED = R.SEEDS[1]
-W64 = (2, 4, 130, 256, 64, 'none')   # U1's size class at head width 64: csrc/attention_wide.hip
+W64 = (2, 4, 130, 256, 64, 'none')   # U1's size class at head width 64: csrc/attention.hip at two d-tiles
 PROBES = [('U1', BF16), ('S2', BF16), ('M1', FP32), ('W64', BF16)]
 
 

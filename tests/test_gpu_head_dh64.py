@@ -1,7 +1,7 @@
 """--nheads 4 / --hidden_dim choices whose heads are wider than 32, through the product modules: the SVANet head and the enc/dec
 Transformer against reference-generated fixtures with two heads of 64 or of 48 (tests/golden/make_golden_dh64.py; the CPU oracle is
 held to the same fixtures in tests/test_oracle_golden_dh64.py), and one training step at hidden_dim 256 / nheads 4 through build_model.
-Every attention launch here goes to csrc/attention_wide.hip; the bars are those of the checks called, none new."""
+Every attention launch here goes to the generic template of csrc/attention.hip at two d-tiles; the bars are those of the checks called, none new."""
 import pytest
 import torch
 

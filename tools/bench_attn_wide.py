@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Attention at head width 64 (csrc/attention_wide.hip) beside the same build's head width 32 launches of equal FLOPs.
+"""Attention at head width 64 (csrc/attention.hip's generic template at two d-tiles) beside the same build's head width 32 launches of
+equal FLOPs.
 
 Forward and backward alone, device events, warm, the median of repeated blocks; a wide block and a narrow block alternate so that
 both see the same machine state.  Shapes: video self-attention (B = 8, L = 6272) and the object queries' cross-attention (100 queries
-against 6272 keys), H x dh = 4 x 64 against 8 x 32, bf16 and fp16.  One JSON line per launch pair.
+against 6272 keys), H x dh = 4 x 64 against 8 x 32, fp32, bf16 and fp16.  One JSON line per launch pair.  In fp32 the two columns are
+the template's two instances (<float, 2> and <float, 1>); at 16 bits the 8 x 32 column is csrc/attention_bf16.hip.
 
-    python tools/bench_attn_wide.py [--blocks 7] [--iters 10]
+--tree DIR times the svol_amd (and its built library) of another checkout, e.g. a parent commit's, with this same script.
+
+    python tools/bench_attn_wide.py [--blocks 7] [--iters 10] [--tree DIR]
 """
 import argparse
 import json
@@ -14,12 +18,10 @@ import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-
-from svol_amd import ops  # noqa: E402
+import torch
 
 LOG2E = 1.4426950408889634
+ops = None   # svol_amd.ops of the chosen checkout (main)
 
 
 def make(B, H, Lq, Lk, dh, dtype):
@@ -64,9 +66,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--blocks', type=int, default=7)
     ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    help='the checkout whose svol_amd is imported (default: this one)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
-    for dtype, dn in ((torch.bfloat16, 'bf16'), (torch.float16, 'fp16')):
+    global ops
+    sys.path.insert(0, os.path.abspath(a.tree))
+    from svol_amd import ops
+    assert os.path.abspath(ops.__file__).startswith(os.path.abspath(a.tree) + os.sep), ops.__file__
+    for dtype, dn in ((torch.float32, 'fp32'), (torch.bfloat16, 'bf16'), (torch.float16, 'fp16')):
         for tag, B, Lq, Lk in (('self', 8, 6272, 6272), ('cross', 8, 100, 6272)):
             wf, wb = make(B, 4, Lq, Lk, 64, dtype)
             nf, nb = make(B, 8, Lq, Lk, 32, dtype)
