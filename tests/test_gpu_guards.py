@@ -12,53 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-NEG0 = -2147483648  # 0x80000000 as int32: fp32 -0.0
-
-
-class GuardArena:
-    """One int32 allocation of -0.0 words; take() returns tensors of it separated by guard zones (also one in front of the first and
-    one behind the last); check() verifies every word outside the taken ranges."""
-
-    def __init__(self, guard_bytes=1 << 18):
-        self.guard = guard_bytes // 4
-        self.req = []
-
-    def plan(self, name, shape, dtype):
-        self.req.append((name, tuple(shape), dtype))
-
-    def build(self):
-        off = self.guard
-        self.slots = {}
-        for name, shape, dtype in self.req:
-            n = 1
-            for s in shape:
-                n *= s
-            words = (n * torch.empty((), dtype=dtype).element_size() + 3) // 4
-            words = (words + 63) // 64 * 64          # 256-byte aligned starts
-            self.slots[name] = (off, words, shape, dtype)
-            off += words + self.guard
-        self.buf = torch.full((off,), NEG0, dtype=torch.int32, device='cuda')
-        out = {}
-        for name, (o, w, shape, dtype) in self.slots.items():
-            n = 1
-            for s in shape:
-                n *= s
-            out[name] = self.buf[o:o + w].view(dtype)[:n].view(shape)
-        return out
-
-    def check(self, what):
-        keep = torch.ones_like(self.buf, dtype=torch.bool)
-        for name, (o, w, shape, dtype) in self.slots.items():
-            n = 1
-            for s in shape:
-                n *= s
-            used = (n * torch.empty((), dtype=dtype).element_size() + 3) // 4
-            keep[o:o + used] = False
-        bad = (self.buf != NEG0) & keep
-        if bool(bad.any()):
-            idx = int(torch.nonzero(bad)[0])
-            near = [nm for nm, (o, w, _, _) in self.slots.items() if o - self.guard <= idx < o + w + self.guard]
-            raise AssertionError(f'{what}: guard word {idx} changed ({int(bad.sum())} words in all); nearest buffer(s): {near}')
+from tests.guard_arena import NEG0, GuardArena   # noqa: F401  (the arena lives in tests/guard_arena.py)
 
 
 def _qkv(B, Lq, Lk, d, dtype, seed):
