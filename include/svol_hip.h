@@ -376,7 +376,11 @@ int svol_attn_bwd_dropout_sd(const void* q, int64_t ldq, const void* k, int64_t 
  *   a[b,l]        = mean_h softmax_l(scores[b,h,:])
  *   y             = LN1(x * (1 + a)) ;  ypos = y + pos
  * x32 is the fp32 residual stream [B*L, D]; pos / y / ypos are `dtype`; y32 fp32 (may be NULL).
- * ws: fp32 workspace of B*H*(L+2) floats (scores, then per-(b,h) max and sum). */
+ * ws: fp32 workspace of B*H*(L+2) floats (scores, then per-(b,h) max and sum).
+ * Limits of the family (svol_gate_fwd / _bwd, svol_gate_vectors_fwd / _bwd and their _multi forms): D % 4 == 0, D <= 1024,
+ * H <= 32 (above eight heads the score pass and the backward apply pass run once per group of eight heads); the vectors also need
+ * D % H == 0.  The fused-score entries below (svol_layernorm_gate_scores_fwd, svol_gate_fwd_scored) take H <= 8.  Anything beyond
+ * returns SVOL_E_UNSUPPORTED and writes nothing. */
 int svol_gate_fwd(const float* x32, const void* pos, const float* u, const float* gamma, const float* beta,
                   float* y32, void* y, void* ypos, float* a, float* mean, float* rstd, float* ws, int64_t B,
                   int64_t L, int64_t D, int64_t H, int dtype, void* stream);

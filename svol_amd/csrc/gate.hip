@@ -13,12 +13,15 @@
 namespace {
 
 constexpr int GP = 4;  // max passes: D <= 1024
-constexpr int GH = 8;  // max heads
+constexpr int GH = 8;  // heads per group: what one pass keeps in registers, and what one store_head_sums butterfly reduces
+constexpr int GHMAX = 32;  // max heads: up to four groups of GH (the WIDE instantiations below; the fused-score entries stay at GH)
 
 // 8 head sums over 64 lanes as ONE reduce-scatter butterfly: the xor-1 partners split the heads (each keeps four and adds the
 // partner's four), the xor-2 partners split again (two each), then two values ride the remaining four steps — 14 exchanges instead
-// of 8 x 6.  Lane q of quad 0 ends with heads {4*(q&1) + 2*(q>>1), +1} and stores them: scores[b, hh, l].
-__device__ __forceinline__ void store_head_sums(const float (&part)[GH], float* __restrict__ scores, int b, int l, int L, int H, int lane) {
+// of 8 x 6.  Lane q of quad 0 ends with heads {4*(q&1) + 2*(q>>1), +1} of the group of eight that starts at head h0 and stores
+// them: scores[b, h0 + hh, l].
+__device__ __forceinline__ void store_head_sums(const float (&part)[GH], float* __restrict__ scores, int b, int l, int L, int H, int lane,
+                                                int h0 = 0) {
     const bool b0 = lane & 1, b1 = lane & 2;
     float h4[4], h2[2];
 #pragma unroll
@@ -47,20 +50,24 @@ __device__ __forceinline__ void store_head_sums(const float (&part)[GH], float* 
         h2[i] = __builtin_bit_cast(float, r32.lo) + __builtin_bit_cast(float, r32.hi);
     }
     if (lane < 4) {
-        const int hh0 = 4 * (lane & 1) + 2 * (lane >> 1);
+        const int hh0 = h0 + 4 * (lane & 1) + 2 * (lane >> 1);
         if (hh0 < H) scores[((int64_t)b * H + hh0) * L + l] = h2[0];
         if (hh0 + 1 < H) scores[((int64_t)b * H + hh0 + 1) * L + l] = h2[1];
     }
 }
 
 // scores[b,hh,l] = (x+pos)[b,l,:] . u[b,hh,:]      grid = (ceil(L / (4*rpw)), B), one wave per row
-template <typename T, int NP>
+// WIDE (GH < H <= GHMAX; the launchers): one launch per group of GH heads, this one for heads hbase .. hbase + GH - 1 — the
+// eight-head pass with its u rows, its butterfly and its stores moved by hbase.  WIDE = false is the pass for H <= GH as it always
+// was: hbase is not read, h0 is the constant 0 and the instruction stream is the one from before the parameter existed.
+template <typename T, int NP, bool WIDE = false>
 __global__ __launch_bounds__(256) void gate_scores_kernel(const float* __restrict__ x, const T* __restrict__ pos,
                                                           const float* __restrict__ u, float* __restrict__ scores, int L,
-                                                          int D, int H, int rpw) {
+                                                          int D, int H, int rpw, int hbase) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int l0 = (blockIdx.x * 4 + wave) * rpw;
+    const int h0 = WIDE ? hbase : 0;
     float ur[GH][NP][4];
 #pragma unroll
     for (int hh = 0; hh < GH; ++hh)
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(256) void gate_scores_kernel(const float* __restric
         for (int j = 0; j < NP; ++j) {
             const int c = (lane + 64 * j) * 4;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ur[hh][j][e] = (hh < H && c < D) ? u[((int64_t)b * H + hh) * D + c + e] : 0.f;
+            for (int e = 0; e < 4; ++e) ur[hh][j][e] = (h0 + hh < H && c < D) ? u[((int64_t)b * H + h0 + hh) * D + c + e] : 0.f;
         }
     const int lend = min(l0 + rpw, L);
     Vec4<float> xv[NP], nxv[NP];
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(256) void gate_scores_kernel(const float* __restric
                 }
             }
         }
-        store_head_sums(part, scores, b, l, L, H, lane);
+        store_head_sums(part, scores, b, l, L, H, lane, h0);
 #pragma unroll
         for (int j = 0; j < NP; ++j) { xv[j] = nxv[j]; pv[j] = npv[j]; }
     }
@@ -134,7 +141,8 @@ __global__ __launch_bounds__(256) void gate_stats_kernel(const float* __restrict
 }
 
 // a[b,l] = mean_h softmax ; s1 = x*(1+a) ; y = LN(s1) ; ypos = y + pos        one wave per row
-template <typename T, int NP>
+// WIDE (GH < H <= GHMAX): lane h holds head h's score and statistics, as in gate_bwd_ln_kernel, and the mean is a wave sum
+template <typename T, int NP, bool WIDE = false>
 __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict__ x, const T* __restrict__ pos,
                                                          const float* __restrict__ scores, const float* __restrict__ mx,
                                                          const float* __restrict__ sm, const float* __restrict__ gamma,
@@ -152,12 +160,19 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict
     Vec4<float> t[NP], gv[NP], bv[NP];
     Vec4<T> pv[NP];
     float sc[GH], mxv[GH], smv[GH];
+    if constexpr (WIDE) {
+        const int bh = b * H + (lane < H ? lane : 0);
+        sc[0] = scores[(int64_t)bh * L + l];
+        mxv[0] = mx[bh];
+        smv[0] = sm[bh];
+    } else {
 #pragma unroll
     for (int hh = 0; hh < GH; ++hh) {
         const int bh = b * H + (hh < H ? hh : 0);
         sc[hh] = scores[(int64_t)bh * L + l];
         mxv[hh] = mx[bh];
         smv[hh] = sm[bh];
+    }
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
@@ -170,9 +185,13 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict
         }
     }
     float a = 0.f;
+    if constexpr (WIDE) {
+        a = wave_sum(lane < H ? __expf(sc[0] - mxv[0]) / smv[0] : 0.f);
+    } else {
 #pragma unroll
     for (int hh = 0; hh < GH; ++hh)
         if (hh < H) a += __expf(sc[hh] - mxv[hh]) / smv[hh];
+    }
     a /= (float)H;
     float v[NP][4];
     float s = 0.f;
@@ -460,16 +479,19 @@ __global__ __launch_bounds__(256) void gate_bwd_ln_kernel(const float* __restric
 }
 
 // backward pass 3: dscore[hh] = p_hh[l] * (da[l]/H - c[b,hh]) ; dx += sum_hh dscore*u ; du += dscore*(x+pos)
-template <typename T, int NP>
+// WIDE (GH < H <= GHMAX): one launch per group of GH heads, one after the other on the stream (each adds its score term to dx), this
+// one for heads hbase .. hbase + GH - 1; WIDE = false as in gate_scores_kernel
+template <typename T, int NP, bool WIDE = false>
 __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __restrict__ x, const T* __restrict__ pos,
                                                              const float* __restrict__ u, const float* __restrict__ scores,
                                                              const float* __restrict__ mx, const float* __restrict__ sm,
                                                              const float* __restrict__ da, const float* __restrict__ cc,
                                                              float* __restrict__ dx, float* __restrict__ du, int L, int D,
-                                                             int H, int rpw, float* __restrict__ det_du) {
+                                                             int H, int rpw, float* __restrict__ det_du, int hbase) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int l0 = (blockIdx.x * 4 + wave) * rpw;
+    const int h0 = WIDE ? hbase : 0;
     float ur[GH][NP][4], dur[GH][NP][4];
 #pragma unroll
     for (int hh = 0; hh < GH; ++hh)
@@ -478,7 +500,7 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
             const int c = (lane + 64 * j) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                ur[hh][j][e] = (hh < H && c < D) ? u[((int64_t)b * H + hh) * D + c + e] : 0.f;
+                ur[hh][j][e] = (h0 + hh < H && c < D) ? u[((int64_t)b * H + h0 + hh) * D + c + e] : 0.f;
                 dur[hh][j][e] = 0.f;
             }
         }
@@ -493,9 +515,9 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
     float mxr[GH], isr[GH], ccr[GH], sc[GH], nsc[GH], dar = 0.f, ndar = 0.f;
 #pragma unroll
     for (int hh = 0; hh < GH; ++hh) {
-        mxr[hh] = hh < H ? mx[b * H + hh] : 0.f;
-        isr[hh] = hh < H ? 1.f / sm[b * H + hh] : 0.f;
-        ccr[hh] = hh < H ? cc[b * H + hh] : 0.f;
+        mxr[hh] = h0 + hh < H ? mx[b * H + h0 + hh] : 0.f;
+        isr[hh] = h0 + hh < H ? 1.f / sm[b * H + h0 + hh] : 0.f;
+        ccr[hh] = h0 + hh < H ? cc[b * H + h0 + hh] : 0.f;
         sc[hh] = nsc[hh] = 0.f;
     }
     auto fetch = [&](int l, Vec4<float> (&xr)[NP], Vec4<T> (&pr)[NP], Vec4<float> (&dr)[NP], float (&sr)[GH], float& dr1) {
@@ -511,7 +533,7 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
         }
 #pragma unroll
         for (int hh = 0; hh < GH; ++hh)
-            if (hh < H) sr[hh] = scores[((int64_t)b * H + hh) * L + l];
+            if (h0 + hh < H) sr[hh] = scores[((int64_t)b * H + h0 + hh) * L + l];
         dr1 = da[row];
     };
     if (l0 < lend) fetch(l0, xv, pv, dv, sc, dar);
@@ -522,7 +544,7 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
         const float dal = dar / (float)H;
 #pragma unroll
         for (int hh = 0; hh < GH; ++hh) {
-            if (hh < H) {
+            if (h0 + hh < H) {
                 const float pp = __expf(sc[hh] - mxr[hh]) * isr[hh];
                 ds[hh] = pp * (dal - ccr[hh]);
             } else ds[hh] = 0.f;
@@ -572,10 +594,10 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
     }
     for (int i = threadIdx.x; i < GH * NP * 256; i += 256) {
         const int hh = i / (NP * 256), c = i % (NP * 256);
-        if (hh < H && c < D) {
+        if (h0 + hh < H && c < D) {
             // deterministic mode: the workgroup's row [H*D] of batch element b's block of the scratch (folded by the launcher)
-            if (det_du) det_du[(((int64_t)b * gridDim.x + blockIdx.x) * H + hh) * D + c] = red[i];
-            else atomicAdd(du + ((int64_t)b * H + hh) * D + c, red[i]);
+            if (det_du) det_du[(((int64_t)b * gridDim.x + blockIdx.x) * H + h0 + hh) * D + c] = red[i];
+            else atomicAdd(du + ((int64_t)b * H + h0 + hh) * D + c, red[i]);
         }
     }
 }
@@ -767,7 +789,7 @@ static int gate_fwd_impl(const float* x32, const void* pos, const float* u, cons
     if (!x32 || !pos || !u || !gamma || !beta || (!y && !y32) || !a || !mean || !rstd || !ws) return SVOL_E_INVALID;
     if (!aligned16(gamma) || !aligned16(beta)) return SVOL_E_INVALID;   // (16-byte vector loads of the affine parameters)
     if (B <= 0 || L <= 0 || D <= 0 || H <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || B > 65535 || L > (1 << 24)) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > (scored ? GH : GHMAX) || B > 65535 || L > (1 << 24)) return SVOL_E_UNSUPPORTED;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int np_ = D <= 256 ? 1 : (D <= 512 ? 2 : 4);
@@ -778,21 +800,30 @@ static int gate_fwd_impl(const float* x32, const void* pos, const float* u, cons
     dim3 g1((unsigned)((L + 4 * rpw - 1) / (4 * rpw)), (unsigned)B);
     const int64_t M = B * L;
     const unsigned g3 = (unsigned)((M + 3) / 4);
+    // H <= GH: the launches there always were.  Above: the score pass once per group of GH heads, the lane-per-head apply pass.
+#define SVOL_GATE_SC(TT, N, W, H0) hipLaunchKernelGGL((gate_scores_kernel<TT, N, W>), g1, dim3(256), 0, s, x32, (const TT*)pos, u, scores, (int)L, (int)D, (int)H, rpw, H0)
+#define SVOL_GATE_AP(TT, N, W, H0) hipLaunchKernelGGL((gate_apply_kernel<TT, N, W>), dim3(g3), dim3(256), 0, s, x32, (const TT*)pos, scores, mx, sm, gamma, beta, y32, (TT*)y, (TT*)ypos, a, mean, rstd, (int)L, (int)D, (int)H, M)
+#define SVOL_GATE_NP(LAUNCH, TT, W, H0)                                                                                     \
+    do {                                                                                                                    \
+        if (np_ == 1) LAUNCH(TT, 1, W, H0);                                                                                 \
+        else if (np_ == 2) LAUNCH(TT, 2, W, H0);                                                                            \
+        else LAUNCH(TT, 4, W, H0);                                                                                          \
+    } while (0)
 #define SVOL_GATE_FWD(TT)                                                                                                   \
     do {                                                                                                                    \
         if (scored) { }                                                                                                      \
-        else if (np_ == 1) hipLaunchKernelGGL((gate_scores_kernel<TT, 1>), g1, dim3(256), 0, s, x32, (const TT*)pos, u, scores, (int)L, (int)D, (int)H, rpw); \
-        else if (np_ == 2) hipLaunchKernelGGL((gate_scores_kernel<TT, 2>), g1, dim3(256), 0, s, x32, (const TT*)pos, u, scores, (int)L, (int)D, (int)H, rpw); \
-        else hipLaunchKernelGGL((gate_scores_kernel<TT, 4>), g1, dim3(256), 0, s, x32, (const TT*)pos, u, scores, (int)L, (int)D, (int)H, rpw); \
+        else if (H <= GH) SVOL_GATE_NP(SVOL_GATE_SC, TT, false, 0);                                                         \
+        else for (int h0 = 0; h0 < (int)H; h0 += GH) SVOL_GATE_NP(SVOL_GATE_SC, TT, true, h0);                              \
         hipLaunchKernelGGL(gate_stats_kernel, dim3((unsigned)(B * H)), dim3(256), 0, s, scores, mx, sm, (int)L);            \
-        if (np_ == 1) hipLaunchKernelGGL((gate_apply_kernel<TT, 1>), dim3(g3), dim3(256), 0, s, x32, (const TT*)pos, scores, mx, sm, gamma, beta, y32, (TT*)y, (TT*)ypos, a, mean, rstd, (int)L, (int)D, (int)H, M); \
-        else if (np_ == 2) hipLaunchKernelGGL((gate_apply_kernel<TT, 2>), dim3(g3), dim3(256), 0, s, x32, (const TT*)pos, scores, mx, sm, gamma, beta, y32, (TT*)y, (TT*)ypos, a, mean, rstd, (int)L, (int)D, (int)H, M); \
-        else hipLaunchKernelGGL((gate_apply_kernel<TT, 4>), dim3(g3), dim3(256), 0, s, x32, (const TT*)pos, scores, mx, sm, gamma, beta, y32, (TT*)y, (TT*)ypos, a, mean, rstd, (int)L, (int)D, (int)H, M); \
+        if (H <= GH) SVOL_GATE_NP(SVOL_GATE_AP, TT, false, 0);                                                              \
+        else SVOL_GATE_NP(SVOL_GATE_AP, TT, true, 0);                                                                       \
     } while (0)
     if (dtype == SVOL_BF16) SVOL_GATE_FWD(bf16_t);
     else if (dtype == SVOL_F16) SVOL_GATE_FWD(f16_t);
     else SVOL_GATE_FWD(float);
 #undef SVOL_GATE_FWD
+#undef SVOL_GATE_SC
+#undef SVOL_GATE_AP
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
@@ -842,7 +873,7 @@ int svol_gate_bwd(const float* dy32, const void* dy, const void* dy2, const floa
         !dgamma || !dbeta)
         return SVOL_E_INVALID;
     if (B <= 0 || L <= 0 || D <= 0 || H <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || B > 65535 || L > (1 << 24)) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > GHMAX || B > 65535 || L > (1 << 24)) return SVOL_E_UNSUPPORTED;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int np_ = D <= 256 ? 1 : (D <= 512 ? 2 : 4);
@@ -867,24 +898,26 @@ int svol_gate_bwd(const float* dy32, const void* dy, const void* dy2, const floa
     float* det_cc = det_mode ? det.p : nullptr;
     float* det_gb = det_mode ? det.p + n_cc : nullptr;
     float* det_du = det_mode ? det.p + n_cc + n_gb : nullptr;
+#define SVOL_GATE_LN(TT, N, W, H0) hipLaunchKernelGGL((gate_bwd_ln_kernel<TT, N>), dim3(g1), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, x32, a, gamma, mean, rstd, dx32, da, dgamma, dbeta, scores, mx, sm, cc, (int)L, (int)H, M, (int)D, rpw1, det_cc, det_gb)
+#define SVOL_GATE_BA(TT, N, W, H0) hipLaunchKernelGGL((gate_bwd_apply_kernel<TT, N, W>), g3, dim3(256), 0, s, x32, (const TT*)pos, u, scores, mx, sm, da, cc, dx32, du, (int)L, (int)D, (int)H, rpw3, det_du, H0)
 #define SVOL_GATE_BWD(TT)                                                                                                   \
     do {                                                                                                                    \
-        if (np_ == 1) hipLaunchKernelGGL((gate_bwd_ln_kernel<TT, 1>), dim3(g1), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, x32, a, gamma, mean, rstd, dx32, da, dgamma, dbeta, scores, mx, sm, cc, (int)L, (int)H, M, (int)D, rpw1, det_cc, det_gb); \
-        else if (np_ == 2) hipLaunchKernelGGL((gate_bwd_ln_kernel<TT, 2>), dim3(g1), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, x32, a, gamma, mean, rstd, dx32, da, dgamma, dbeta, scores, mx, sm, cc, (int)L, (int)H, M, (int)D, rpw1, det_cc, det_gb); \
-        else hipLaunchKernelGGL((gate_bwd_ln_kernel<TT, 4>), dim3(g1), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, x32, a, gamma, mean, rstd, dx32, da, dgamma, dbeta, scores, mx, sm, cc, (int)L, (int)H, M, (int)D, rpw1, det_cc, det_gb); \
+        SVOL_GATE_NP(SVOL_GATE_LN, TT, false, 0);                                                                           \
         if (det_mode) {                                                                                                     \
             det_fold(det_cc, (int)(g1 * 4), B * H, cc, B * H, s);                                                           \
             det_fold(det_gb, (int)g1, 2 * D, dgamma, D, s);                                                                 \
             det_fold(det_gb + D, (int)g1, 2 * D, dbeta, D, s);                                                              \
         }                                                                                                                   \
-        if (np_ == 1) hipLaunchKernelGGL((gate_bwd_apply_kernel<TT, 1>), g3, dim3(256), 0, s, x32, (const TT*)pos, u, scores, mx, sm, da, cc, dx32, du, (int)L, (int)D, (int)H, rpw3, det_du); \
-        else if (np_ == 2) hipLaunchKernelGGL((gate_bwd_apply_kernel<TT, 2>), g3, dim3(256), 0, s, x32, (const TT*)pos, u, scores, mx, sm, da, cc, dx32, du, (int)L, (int)D, (int)H, rpw3, det_du); \
-        else hipLaunchKernelGGL((gate_bwd_apply_kernel<TT, 4>), g3, dim3(256), 0, s, x32, (const TT*)pos, u, scores, mx, sm, da, cc, dx32, du, (int)L, (int)D, (int)H, rpw3, det_du); \
+        if (H <= GH) SVOL_GATE_NP(SVOL_GATE_BA, TT, false, 0);                                                              \
+        else for (int h0 = 0; h0 < (int)H; h0 += GH) SVOL_GATE_NP(SVOL_GATE_BA, TT, true, h0);                              \
     } while (0)
     if (dtype == SVOL_BF16) SVOL_GATE_BWD(bf16_t);
     else if (dtype == SVOL_F16) SVOL_GATE_BWD(f16_t);
     else SVOL_GATE_BWD(float);
 #undef SVOL_GATE_BWD
+#undef SVOL_GATE_LN
+#undef SVOL_GATE_BA
+#undef SVOL_GATE_NP
     if (det_mode) det_fold(det_du, (int)g3.x, H * D, du, H * D, s, (int)B, (int64_t)g3.x * H * D, H * D);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
@@ -893,7 +926,7 @@ int svol_gate_bwd(const float* dy32, const void* dy, const void* dy2, const floa
 int svol_gate_vectors_fwd(const float* skch, const float* W_in, const float* b_in, float* q_out, float* u_out, int64_t B, int64_t D,
                           int64_t H, void* stream) {
     if (!skch || !W_in || !b_in || !q_out || !u_out || B <= 0 || D <= 0 || H <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || D % H || B > 65535) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > GHMAX || D % H || B > 65535) return SVOL_E_UNSUPPORTED;
     if (!aligned16(W_in)) return SVOL_E_INVALID;
     hipLaunchKernelGGL(gate_vec_fwd_kernel, dim3((unsigned)H, (unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), skch,
                        W_in, b_in, q_out, u_out, (int)D, (int)H);
@@ -904,7 +937,7 @@ int svol_gate_vectors_fwd(const float* skch, const float* W_in, const float* b_i
 int svol_gate_vectors_bwd(const float* du, const float* skch, const float* W_in, const float* q, float* dq_ws, float* dskch,
                           float* dW_in, float* db_in, int64_t B, int64_t D, int64_t H, void* stream) {
     if (!du || !skch || !W_in || !q || !dq_ws || !dW_in || !db_in || B <= 0 || D <= 0 || H <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || D % H || B > 65535) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > GHMAX || D % H || B > 65535) return SVOL_E_UNSUPPORTED;
     if (!aligned16(W_in)) return SVOL_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gate_vec_bwd_a_kernel, dim3((unsigned)H, (unsigned)B), dim3(256), 0, s, du, W_in, dq_ws, (int)D, (int)H);
@@ -919,7 +952,7 @@ int svol_gate_vectors_bwd(const float* du, const float* skch, const float* W_in,
 int svol_gate_vectors_fwd_multi(const float* skch, const float* const* W_in, const float* const* b_in, float* const* q_out,
                                 float* const* u_out, int64_t n_layers, int64_t B, int64_t D, int64_t H, void* stream) {
     if (!skch || !W_in || !b_in || !q_out || !u_out || B <= 0 || D <= 0 || H <= 0 || n_layers <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || D % H || B > 65535 || n_layers > SVOL_GATE_VEC_MAX_LAYERS) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > GHMAX || D % H || B > 65535 || n_layers > SVOL_GATE_VEC_MAX_LAYERS) return SVOL_E_UNSUPPORTED;
     GateVecMulti g{};
     for (int l = 0; l < n_layers; ++l) {
         if (!W_in[l] || !b_in[l] || !q_out[l] || !u_out[l] || !aligned16(W_in[l])) return SVOL_E_INVALID;
@@ -935,7 +968,7 @@ int svol_gate_vectors_bwd_multi(const float* const* du, const float* skch, const
                                 float* const* dq_ws, float* const* dskch, float* const* dW_in, float* const* db_in, int64_t n_layers,
                                 int64_t B, int64_t D, int64_t H, void* stream) {
     if (!du || !skch || !W_in || !q || !dq_ws || !dW_in || !db_in || B <= 0 || D <= 0 || H <= 0 || n_layers <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > GP * 256 || H > GH || D % H || B > 65535 || n_layers > SVOL_GATE_VEC_MAX_LAYERS) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > GP * 256 || H > GHMAX || D % H || B > 65535 || n_layers > SVOL_GATE_VEC_MAX_LAYERS) return SVOL_E_UNSUPPORTED;
     GateVecMulti g{};
     for (int l = 0; l < n_layers; ++l) {
         if (!du[l] || !W_in[l] || !q[l] || !dq_ws[l] || !dW_in[l] || !db_in[l] || !aligned16(W_in[l])) return SVOL_E_INVALID;
