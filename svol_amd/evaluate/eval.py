@@ -108,7 +108,8 @@ def _max_ious(pk: _Packed, k: int) -> np.ndarray:
         return np.zeros((0,))
     cnt = np.diff(pk.pred_off)
     if np.any(cnt[pk.gt_rec] == 0):
-        raise ValueError('zero-size array to reduction operation maximum which has no identity')  # numpy's error
+        # numpy's error in the reference: np.array([]) has no box columns, compute_iou_batch_paired dies on box1[..., 0]
+        raise IndexError('index 0 is out of bounds for axis 1 with size 0')
     out = torch.empty((G,), dtype=torch.float64, device=dev)
     # named tensors: they must stay alive until the launch has been enqueued (a temporary's block would be recycled)
     pb, po = _t(pk.pred[:, :4], dev), _t(pk.pred_off, dev)

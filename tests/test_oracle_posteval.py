@@ -13,7 +13,8 @@ from oracle import posteval as O
 from svol_amd import synthetic as syn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-FIXTURES = sorted(glob.glob(os.path.join(HERE, 'golden', 'posteval_*.json')))
+FIXTURES = sorted(p for p in glob.glob(os.path.join(HERE, 'golden', 'posteval_*.json'))
+                  if not p.endswith('posteval_edges.json'))   # that one belongs to test_posteval_edge_cases.py
 
 
 def load_case(path):
