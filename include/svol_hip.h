@@ -182,6 +182,23 @@ int svol_adamw_flat_grouped(float* p, float* g, float* m, float* v, int64_t n, c
                             int32_t nseg, const float* hyper, int32_t ngroups, const float* state, const float* step_count,
                             float grad_mul, int zero, void* stream);
 int svol_flat_step_advance(float* step_count, const float* state, void* stream);
+/* An exponential moving average of the weights beside a flat optimizer's update (no counterpart in the reference, whose loop
+ * validates the raw weights); a new symbol only, the ABI version is unchanged.  One streaming launch over two flat, 16-byte
+ * aligned fp32 ranges of n floats, n % 4 == 0, issued behind the update launch of the same range on the same stream:
+ *   ema[i] = fmaf(1 - d, p[i] - ema[i], ema[i])         p is only read; 8 bytes read and 4 written per parameter
+ *   d = decay                                           warmup == 0
+ *   d = min(decay, (1 + t) / (10 + t))                  warmup != 0
+ * d is formed once per wave in double and 1 - d rounded to float once.  t is the 1-based index of the update being averaged and
+ * follows the updates really taken, from the source the update itself read:
+ *   step_count != NULL                     *step_count + 1    (the grouped / capturable path; state then only gives the flag)
+ *   state != NULL, step_count == NULL      state[3] + 1       (a DynamicLossScaler's vector or the clip state)
+ *   neither                                step               (the host's count, from 1)
+ * state != NULL and state[1] != 0: the update was skipped, nothing is written.  Launch it BEFORE svol_loss_scaler_update /
+ * svol_flat_step_advance, which clear the flag and move the count.  SVOL_E_INVALID on a null ema or p, n < 0, decay outside
+ * [0, 1] or NaN, or step < 1 with neither state nor step_count; SVOL_OK on n == 0; SVOL_E_UNSUPPORTED on n % 4 != 0, a
+ * misaligned range or n >= 2^41.  No allocation, no synchronisation: capture-safe. */
+int svol_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, int64_t step, const float* state,
+                  const float* step_count, void* stream);
 
 /* ---- GEMMs (nn.Linear and its backward) --------------------------------- */
 /* C[M,N] = act((A[M,K] * B[N,K]^T + bias[N]) * colscale[N]) + residual[M,N]

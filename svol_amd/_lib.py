@@ -67,6 +67,7 @@ SIGNATURES = {
     'svol_adam_flat_grouped': [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _i32, _p, _p, _f32, _int, _p],
     'svol_adamw_flat_grouped': [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _i32, _p, _p, _f32, _int, _p],
     'svol_flat_step_advance': [_p, _p, _p],
+    'svol_ema_flat': [_p, _p, _i64, _f32, _int, _i64, _p, _p, _p],
     'svol_conv_nhwc': [_p, _p, _i64, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_im2col': [_p, _i64, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
     'svol_maxpool_nhwc': [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],

@@ -19,6 +19,8 @@ reference command line parses unchanged.  Differences, all additive:
   run as shipped); ``--finetune_layers K`` restricts that to the last K layers and the final LayerNorm;
 * ``--clip_max_norm X`` (DETR's name; default 0.0 = off): ``parallel.build_optimizer`` clips the global gradient 2-norm to X inside
   the flat optimizers' step (the reference's loop does not clip);
+* ``--model_ema_decay X`` (default None = off): ``parallel.build_optimizer`` keeps an exponential moving average of the weights
+  with decay X on the device (``ema_decay``), for validation and the saved model (the reference's loop has no such average);
 * ``--lr_backbone X`` (DETR's name; default None = off): ``parallel.reference_param_groups`` puts the trainable backbone parameters
   into a param group of their own at learning rate X (the recipe the reference carries commented out, train.py:76-106).
 """
@@ -135,6 +137,9 @@ _EXTRA = [
                                        'LayerNorm (preprocess/sketch_vit_finetune.py); default: every parameter')),
     (('--clip_max_norm',), dict(type=float, default=0.0,
                                 help='clip the global gradient 2-norm inside the optimizer step (parallel.build_optimizer); 0 = off')),
+    (('--model_ema_decay',), dict(type=float, default=None,
+                                  help='keep an exponential moving average of the weights with this decay inside the optimizer step '
+                                       '(parallel.build_optimizer: ema_decay); default: none')),
     (('--lr_backbone',), dict(type=float, default=None,
                               help='learning rate of the trainable backbone parameters, in a param group of their own '
                                    '(parallel.reference_param_groups); default: --lr, one group')),

@@ -20,6 +20,7 @@
 // another choice in the SGD and Adam updates (other result bits).
 // The grouped kernels (several param groups, a capturable step) are a third and fourth function beside them, further down: they read
 // every hyper-parameter and the step count from device tables and promise the parity bar, not the bits of the entries above.
+// The weight average (ema_flat_kernel, behind them) is a fifth, for the same reason: it shares nothing with the update bodies.
 #include "common.h"
 
 namespace {
@@ -295,6 +296,32 @@ int adam_grouped_launch(float* p, float* g, float* m, float* v, int64_t n, const
     return SVOL_OK;
 }
 
+// The weight average beside the update (parallel._FlatOptimizer(ema_decay=...)): ema += (1 - d) * (p - ema) over a flat range, one
+// more streaming pass behind the update launch (8 bytes read, 4 written per parameter).  A kernel of its own, not a flag of the
+// update kernels: see the header on what another way into those bodies does to their bits.  d is uniform: decay, or under warm-up
+// min(decay, (1 + t) / (10 + t)) with t the 1-based index of the update being averaged, read where that update read its count:
+// *step_count + 1 (grouped path), else state[3] + 1 (scaler or clip state), else the host's step.  Formed once per wave in double
+// (one division), so that 1 - d carries a single fp32 rounding; the element arithmetic is one explicit fma.  Nothing is written
+// when state[1] is set: the update was skipped, the average of the steps taken does not move.
+__global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n4, float decay,
+                                                       int warmup, float step, const float* __restrict__ state,
+                                                       const float* __restrict__ step_count) {
+    if (state && state[1] != 0.f) return;   // an overflowed step is skipped whole
+    double d = (double)decay;
+    if (warmup) {
+        const double t = step_count ? (double)*step_count + 1.0 : state ? (double)state[3] + 1.0 : (double)step;
+        d = fmin(d, (1.0 + t) / (10.0 + t));
+    }
+    const float w = (float)(1.0 - d);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 ee = *reinterpret_cast<f32x4*>(ema + 4 * i);
+    const f32x4 pp = *reinterpret_cast<const f32x4*>(p + 4 * i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ee[e] = fmaf(w, pp[e] - ee[e], ee[e]);
+    *reinterpret_cast<f32x4*>(ema + 4 * i) = ee;
+}
+
 __global__ void flat_step_advance_kernel(float* step_count, const float* state) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (!state || state[1] == 0.f) *step_count += 1.f;
@@ -391,6 +418,19 @@ int svol_adamw_flat_grouped(float* p, float* g, float* m, float* v, int64_t n, c
 int svol_flat_step_advance(float* step_count, const float* state, void* stream) {
     if (!step_count) return SVOL_E_INVALID;
     hipLaunchKernelGGL(flat_step_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), step_count, state);
+    SVOL_CHECK_LAUNCH();
+    return SVOL_OK;
+}
+
+int svol_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, int64_t step, const float* state,
+                  const float* step_count, void* stream) {
+    if (!ema || !p || n < 0 || !(decay >= 0.f && decay <= 1.f) || (!state && !step_count && step < 1)) return SVOL_E_INVALID;
+    if (n == 0) return SVOL_OK;
+    if (n % 4 != 0 || !aligned16(ema) || !aligned16(p)) return SVOL_E_UNSUPPORTED;
+    const int64_t blocks = (n / 4 + 255) / 256;
+    if (blocks >= (1ll << 31)) return SVOL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(ema_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ema, p, n / 4, decay,
+                       warmup, (float)step, state, step_count);
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }

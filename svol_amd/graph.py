@@ -34,7 +34,10 @@ class GraphedTrainStep:
         loss dict per frame; the total is summed over the frames and the list of dicts is handed back), optimizer: a CAPTURABLE
         optimizer — a flat optimizer of svol_amd.parallel built with ``capturable=True`` (its step count and hyper-parameters live on the device; a scheduler's
         edits of ``param_groups`` reach the replays through its ``push_hyper()``, called here before every replay) or a torch one
-        (e.g. AdamW(fused=True, capturable=True)), reducer: BucketedGradAllReduce (world size 1)."""
+        (e.g. AdamW(fused=True, capturable=True)), reducer: BucketedGradAllReduce (world size 1).  A flat optimizer that keeps a
+        weight average (``ema_decay=``) needs nothing further: its ``svol_ema_flat`` launches sit in the captured ``step()`` behind
+        each bucket's update and read the overflow flag and the count of updates from the device, so every replay averages the
+        weights it has just written, at the right warm-up index."""
         if reducer.world != 1:
             raise NotImplementedError('graph capture is used for single-process steps; multi-GPU runs stay eager so '
                                       'that the RCCL all-reduce overlaps with backward')

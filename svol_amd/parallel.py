@@ -23,6 +23,7 @@ MI355X-first differences:
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Iterable, List, Optional
 
 import torch
@@ -400,7 +401,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     def __init__(self, reducer: 'BucketedGradAllReduce', defaults: dict, params, zero_grads: bool, step_in_backward: bool,
-                 max_grad_norm: Optional[float] = None, capturable: bool = False):
+                 max_grad_norm: Optional[float] = None, capturable: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
         owned = [p for b in reducer.buckets for p in b['params']]
         plist = list(params) if params is not None else owned
         self._params_given = params is not None
@@ -442,6 +444,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
             for k, _ in self._STATE:
                 st[k] = torch.zeros_like(flat_p)
             self.flat.append(st)
+        # The weight average (see FlatAdamW): a clone of every bucket's flat parameters, taken behind the re-homing copy.  A setting of
+        # the object, like max_grad_norm: not a key of param_groups, not in state_dict().  None: no buffer, no launch.
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f'ema_decay must lie in [0, 1] or be None (off), got {ema_decay}')
+        self._ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_swapped = False   # inside averaged_weights(): 'p' holds the average and 'ema' the weights
+        if self._ema_decay is not None:
+            for st in self.flat:
+                st['ema'] = st['p'].clone()
         self.zero_grads = bool(zero_grads)
         self.step_in_backward = bool(step_in_backward)
         self._stepped = [False] * len(self.flat)
@@ -590,6 +602,19 @@ class _FlatOptimizer(torch.optim.Optimizer):
         _lib.check(rc, name)
         if zero:
             b['clean'] = True
+        self._ema(bi, stream, t=t if state is None else 0, state=state)
+
+    def _ema(self, bi, stream, t=0, state=None, count=None):
+        """Bucket ``bi``'s weight average on ``stream``, directly behind its update launch and driven by what drove that update:
+        the same ``state`` vector (nothing is averaged on an overflowed step) and the same source of the count of updates taken
+        (``count``, a raw device pointer, on the grouped path; else ``state[3]``; else the host's ``t``), which is the warm-up's
+        index.  Nothing at all with ``ema_decay=None``."""
+        if self._ema_decay is None:
+            return
+        st = self.flat[bi]
+        rc = _lib.lib().svol_ema_flat(_ptr(st['ema']), _ptr(st['p']), st['p'].numel(), self._ema_decay, int(self.ema_warmup), int(t),
+                                      _ptr(state), count, stream)
+        _lib.check(rc, 'svol_ema_flat')
 
     def _clip_state(self, gmul, stream):
         """max_grad_norm set: one sum-of-squares launch per bucket, then one launch that turns the sums into a state vector of the
@@ -606,6 +631,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._ema_swapped:
+            raise RuntimeError('step() inside averaged_weights(): the parameters hold the average')
         if self._grouped:
             self._step_grouped()
             return loss
@@ -660,13 +687,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
         count = sc.state.data_ptr() + 12 if sc is not None else _ptr(self._step_dev)
         zero = state is None and self.zero_grads   # (a skipped step zeroes nothing: under a state vector the reducer's own fill runs)
         name = self._KERNEL + '_grouped'
-        for b, st, (ends, groups) in zip(self.reducer.buckets, self.flat, self._seg_dev):
+        for bi, (b, st, (ends, groups)) in enumerate(zip(self.reducer.buckets, self.flat, self._seg_dev)):
             rc = getattr(L, name)(_ptr(st['p']), _ptr(b['flat']), *(_ptr(st[k]) for k, _ in self._STATE), st['p'].numel(), _ptr(ends),
                                   _ptr(groups), ends.numel(), _ptr(self._hyper_dev), len(self.param_groups),
                                   _ptr(state), *((count,) if self._HAS_STEP else ()), gmul, int(zero), stream)
             _lib.check(rc, name)
             if zero:
                 b['clean'] = True
+            self._ema(bi, stream, state=state, count=count)   # in front of the count's advance: the flag and the count the update saw
         if sc is not None:
             _lib.check(L.svol_loss_scaler_update(_ptr(sc.state), sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
                                                  sc.max_scale, stream), 'svol_loss_scaler_update')
@@ -679,6 +707,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         that wrote them or read its parameters in this step."""
         if self._scaler is not None or self._max_grad_norm is not None or self._stepped[bi]:
             return   # (the overflow check and the gradient norm span all buckets)
+        if self._ema_swapped:
+            raise RuntimeError('a backward with step_in_backward inside averaged_weights(): the parameters hold the average')
         world = self.reducer.world
         self._launch(bi, stream, (1.0 / world if world > 1 else 1.0) / float(self.loss_scale), t=self.t + 1)
         self._stepped[bi] = True
@@ -690,6 +720,107 @@ class _FlatOptimizer(torch.optim.Optimizer):
         bi, off, n = self._slot[id(p)]
         st = self.flat[bi]
         return tuple(st[k][off:off + n].view_as(p) for k, _ in self._STATE)
+
+    # The weight average (ema_decay=...): readers, checkpoint state and the exchange for validation.  All of it is off the hot path.
+    ema_decay = property(lambda self: self._ema_decay)
+
+    def _need_ema(self, what):
+        if self._ema_decay is None:
+            raise RuntimeError(f'{what}: this optimizer was built with ema_decay=None')
+
+    def ema_views(self, p):
+        """The average of parameter ``p``: shaped like it, a view of the bucket's flat ``'ema'`` buffer (no copy).  Inside
+        ``averaged_weights()`` the buffers are exchanged and this view holds the raw weights."""
+        self._need_ema('ema_views')
+        bi, off, n = self._slot[id(p)]
+        return self.flat[bi]['ema'][off:off + n].view_as(p)
+
+    def _averaged(self, p):
+        """the average of ``p`` wherever it lives right now"""
+        return p.detach() if self._ema_swapped else self.ema_views(p)
+
+    @torch.no_grad()
+    def ema_state_dict(self, model: torch.nn.Module):
+        """``model.state_dict()`` with every parameter of a gradient bucket replaced by a clone of its average.  Buffers (BatchNorm
+        statistics) and parameters outside the buckets (the reducer's skip list, frozen ones) keep their live values."""
+        self._need_ema('ema_state_dict')
+        sd = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in self._slot and name in sd:
+                sd[name] = self._averaged(p).clone()
+        return sd
+
+    @torch.no_grad()
+    def ema_extra_state(self):
+        """What a checkpoint carries besides ``ema_state_dict``: ``{'decay', 'warmup', 'step', 'params'}``, ``params`` the averages
+        without names, numbered by position in the groups' parameter lists as torch numbers ``state_dict()['state']``; ``step`` the
+        updates taken (a host read), which the warm-up continues from under a rule whose own state carries no step (SGD)."""
+        self._need_ema('ema_extra_state')
+        out, i = {}, 0
+        for g in self.param_groups:
+            for j, p in enumerate(g['params']):
+                if id(p) in self._slot:
+                    out[i + j] = self._averaged(p).clone()
+            i += len(g['params'])
+        return {'decay': self._ema_decay, 'warmup': self.ema_warmup, 'step': self.steps_taken(), 'params': out}
+
+    @torch.no_grad()
+    def load_ema_extra_state(self, d):
+        """Restore the averages from ``ema_extra_state()``'s dict, by position; ``None``: re-seed them from the current parameters
+        (a checkpoint written without an average).  ``decay`` / ``warmup`` stay what this optimizer was built with: they are
+        settings of the loop, as ``max_grad_norm`` is.  Call it after ``load_state_dict``."""
+        self._need_ema('load_ema_extra_state')
+        if self._ema_swapped:
+            raise RuntimeError('load_ema_extra_state() inside averaged_weights()')
+        if d is None:
+            for st in self.flat:
+                st['ema'].copy_(st['p'])
+            return
+        plist = [p for g in self.param_groups for p in g['params']]
+        todo = []
+        for pos, p in enumerate(plist):
+            if id(p) not in self._slot:
+                continue
+            t = d['params'].get(pos)
+            if t is None:
+                raise ValueError(f'parameter {pos} has a gradient bucket here and no average in the loaded state')
+            if t.numel() != p.numel():
+                raise ValueError(f'parameter {pos}: an average of {t.numel()} elements for {p.numel()} weights')
+            todo.append((p, t))
+        for p, t in todo:
+            self.ema_views(p).copy_(t.reshape(p.shape))
+        if not self._HAS_STEP and 'step' in d:
+            self.t = int(d['step'])
+            self._sync_count()
+
+    def _exchange(self):
+        with torch.no_grad():
+            for st in self.flat:
+                tmp = st['p'].clone()
+                st['p'].copy_(st['ema'])
+                st['ema'].copy_(tmp)
+            # caches keyed on a parameter's version (the extractors' frozen-path copies) must see the exchange; the head's and the
+            # block plans' 16-bit copies are re-cast from the flat buffers at the next forward anyway (params._WeightCache.new_epoch)
+            torch.autograd.graph.increment_version([p for g in self.param_groups for p in g['params'] if id(p) in self._slot])
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with optimizer.averaged_weights(): validate(model)``: on entry the flat parameters and the averages are exchanged, bucket
+        by bucket, with plain copies on the current stream (the parameters are views, so the model now IS the averaged model); on
+        exit they are exchanged back, and parameters and averages are bit for bit what they were.  The model's 16-bit weight copies
+        follow at its next forward.  No ``step()`` inside; raises when nested and inside a stream capture."""
+        self._need_ema('averaged_weights')
+        if self._ema_swapped:
+            raise RuntimeError('averaged_weights() is already entered')
+        if self.flat[0]['p'].is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('averaged_weights() inside a stream capture: the exchange is not part of a training step')
+        self._exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._ema_swapped = False
 
     def state_dict(self):
         """The schema of the torch optimizer of the same name.  A parameter has a state entry iff it has a slot in a gradient
@@ -806,7 +937,8 @@ class FlatAdamW(_FlatOptimizer):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None, capturable: bool = False):
+                 max_grad_norm: Optional[float] = None, capturable: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
         """zero_grads: the update kernel zeroes each gradient bucket behind its read (``svol_adamw_flat_zero``) and the reducer's next
         ``zero_grad()`` skips its fill — the reference loop's ``optimizer.zero_grad()`` (train.py:222) folded into ``step()``; for a
         loop that reads no ``param.grad`` between ``step()`` and ``zero_grad()``.
@@ -833,9 +965,18 @@ class FlatAdamW(_FlatOptimizer):
         (``graph.GraphedTrainStep``): the step count lives on the device, and hyper-parameters reach the kernels through
         ``push_hyper()``, which ``step()`` calls itself except while capturing.  (An attribute of this object, not of the param
         groups: their ``capturable`` key stays torch's default, so that a checkpoint written here loads into a CPU torch optimizer.)
-        With one group and ``capturable=False`` the step is the plain path, launch for launch what it was."""
+        With one group and ``capturable=False`` the step is the plain path, launch for launch what it was.
+        ema_decay: keep an exponential moving average of the weights on the device, ``ema += (1 - d) * (p - ema)`` after every update
+        really taken: one more streaming launch per bucket (``svol_ema_flat``, 12 bytes per parameter) directly behind the
+        bucket's update, on its stream, under the same overflow flag and the same count of updates — in ``step()`` on every path,
+        in a captured step, and during backward under ``step_in_backward``.  A step the loss scaler skips moves neither the average
+        nor its warm-up.  ``ema_warmup``: ``d = min(ema_decay, (1 + t) / (10 + t))`` at the t-th update, so that the average
+        forgets the initial weights early on.  The average starts as a copy of the weights and lives in ``flat[i]['ema']``;
+        ``ema_views(p)``, ``ema_state_dict(model)`` and ``averaged_weights()`` read it, ``ema_extra_state()`` /
+        ``load_ema_extra_state()`` carry it through checkpoints (utils.checkpoint does both).  A setting of this object like
+        ``max_grad_norm``: not in ``param_groups``, not in ``state_dict()``.  None (the default): no buffer and no launch."""
         super().__init__(reducer, self._defaults(lr, betas, eps, weight_decay), params, zero_grads, step_in_backward, max_grad_norm,
-                         capturable)
+                         capturable, ema_decay, ema_warmup)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -874,8 +1015,10 @@ class FlatAdam(FlatAdamW):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None, capturable: bool = False):
-        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward, max_grad_norm, capturable)
+                 max_grad_norm: Optional[float] = None, capturable: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
+        super().__init__(reducer, lr, betas, eps, weight_decay, params, zero_grads, step_in_backward, max_grad_norm, capturable,
+                         ema_decay, ema_warmup)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -905,11 +1048,13 @@ class FlatSGD(_FlatOptimizer):
 
     def __init__(self, reducer: 'BucketedGradAllReduce', lr=1e-3, momentum=0.9, weight_decay=0.0,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, zero_grads: bool = False, step_in_backward: bool = False,
-                 max_grad_norm: Optional[float] = None, capturable: bool = False):
-        """zero_grads, step_in_backward, max_grad_norm, capturable and the list-of-dicts ``params``: see FlatAdamW."""
+                 max_grad_norm: Optional[float] = None, capturable: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
+        """zero_grads, step_in_backward, max_grad_norm, capturable, ema_decay / ema_warmup and the list-of-dicts ``params``: see
+        FlatAdamW."""
         defaults = dict(lr=float(lr), momentum=float(momentum), dampening=0, weight_decay=float(weight_decay), nesterov=False,
                         maximize=False, foreach=None, differentiable=False, fused=None)
-        super().__init__(reducer, defaults, params, zero_grads, step_in_backward, max_grad_norm, capturable)
+        super().__init__(reducer, defaults, params, zero_grads, step_in_backward, max_grad_norm, capturable, ema_decay, ema_warmup)
 
     momentum = property(lambda self: self.param_groups[0]['momentum'])
 
@@ -949,8 +1094,10 @@ def build_optimizer(args, reducer: 'BucketedGradAllReduce', params: Optional[Ite
     """The optimizer ``args.optimizer`` names, as the reference's train_setup builds it (train.py:94-99: SGD with momentum 0.9, Adam,
     AdamW, each with ``lr=args.lr, weight_decay=args.wd``), over ``reducer``'s flat buckets.  ``params``: the reference's parameter
     list or torch's list of group dicts, e.g. ``reference_param_groups(model, args)`` (see FlatAdamW); ``kw``: zero_grads /
-    step_in_backward / max_grad_norm / capturable.  ``args.clip_max_norm`` > 0 (DETR's option, configs.py) becomes ``max_grad_norm``
-    unless ``kw`` names one."""
+    step_in_backward / max_grad_norm / capturable / ema_decay / ema_warmup.  ``args.clip_max_norm`` > 0 (DETR's option, configs.py)
+    becomes ``max_grad_norm`` and ``args.model_ema_decay`` (not None) ``ema_decay``, each unless ``kw`` names one."""
+    if 'ema_decay' not in kw and getattr(args, 'model_ema_decay', None) is not None:
+        kw['ema_decay'] = float(args.model_ema_decay)
     if 'max_grad_norm' not in kw and (getattr(args, 'clip_max_norm', 0) or 0) > 0:
         kw['max_grad_norm'] = float(args.clip_max_norm)
     if args.optimizer == 'sgd':

@@ -51,6 +51,12 @@ def save_checkpoint(path, model, optimizer, lr_scheduler, iter_i: int, args, amp
     rng = {n: m.dropout_state() for n, m in model.named_modules() if hasattr(m, 'dropout_state')}
     if rng:
         ckpt['svol_dropout'] = rng
+    # likewise outside the reference's schema, and only from an optimizer that keeps a weight average (parallel: ema_decay):
+    # 'model_ema', the model's state dict with the averaged weights, keyed like 'model'; 'ema', what the optimizer needs to go on
+    if getattr(optimizer, 'ema_decay', None) is not None:
+        ema_sd = optimizer.ema_state_dict(model)
+        ckpt['model_ema'] = OrderedDict(('module.' + k, v) for k, v in ema_sd.items()) if ddp_prefix else ema_sd
+        ckpt['ema'] = optimizer.ema_extra_state()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(ckpt, path)
     return path
@@ -84,6 +90,10 @@ def load_checkpoint(path, model, optimizer=None, lr_scheduler=None, resume_all: 
     if resume_all:
         if optimizer is not None and ckpt.get('optimizer') is not None:
             optimizer.load_state_dict(ckpt['optimizer'])
+        if getattr(optimizer, 'ema_decay', None) is not None:
+            # the optimizer keeps a weight average: continue the file's, or start one from the parameters just loaded
+            optimizer.load_ema_extra_state(ckpt.get('ema'))
+            info['ema'] = 'restored' if ckpt.get('ema') is not None else 'reseeded from the loaded parameters'
         if lr_scheduler is not None and ckpt.get('lr_scheduler') is not None:
             lr_scheduler.load_state_dict(ckpt['lr_scheduler'])
         info['start_iter'] = ckpt['iter'] + 1

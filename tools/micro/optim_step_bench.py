@@ -37,6 +37,10 @@ untimed, beside bench.py's clock probe: the shader clock the chip held under it.
     (e) torch AdamW fused capturable     torch.optim.AdamW(fused=True, capturable=True): what a captured step uses today
 
 The run count per bucket of (b), (c), (d) is printed and stored with the result.
+
+--ema times the weight average (ema_decay, parallel.py: one svol_ema_flat launch per bucket behind the update, 12 B / parameter),
+same protocol, six rows: flat AdamW, flat Adam and flat SGD without an average (the rows of the plain run) and each with
+ema_decay=0.999.  Printed besides: the time the average adds per step and the bytes/s of that added time at 12 B / parameter.
 """
 import argparse
 import json
@@ -90,8 +94,9 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--clip', action='store_true', help='time the clipped step: rows (a) to (e) of the module docstring')
     ap.add_argument('--groups', action='store_true', help='time the grouped / capturable step: rows (a) to (e) of the module docstring')
+    ap.add_argument('--ema', action='store_true', help='time the weight average: the three flat optimizers without and with ema_decay')
     a = ap.parse_args()
-    assert not (a.clip and a.groups), '--clip or --groups'
+    assert a.clip + a.groups + a.ema <= 1, '--clip, --groups or --ema'
     assert a.block * a.blocks >= 500, 'at least 500 timed steps per optimizer'
     from svol_amd import parallel
     from svol_amd import synthetic as syn
@@ -142,6 +147,16 @@ def main():
         opts['(e) torch AdamW fused capturable'] = torch.optim.AdamW(live, lr=1e-4, weight_decay=1e-4, fused=True, capturable=True)
         bytes_per = {k: 28 for k in opts}
         probed = list(opts)[:4]
+    elif a.ema:
+        mk = {'flat AdamW': lambda **e: parallel.FlatAdamW(reducer, **kw, **e), 'flat Adam': lambda **e: parallel.FlatAdam(reducer, **kw, **e),
+              'flat SGD': lambda **e: parallel.FlatSGD(reducer, momentum=0.9, **kw, **e)}
+        opts, bytes_per = {}, {}
+        for k, f in mk.items():     # (off and on next to each other in the turn order)
+            opts[k], opts[k + ' + ema'] = f(), f(ema_decay=0.999)
+            bytes_per[k] = 20 if 'SGD' in k else 28
+            bytes_per[k + ' + ema'] = bytes_per[k] + 12
+        assert all(('ema' in st) == k.endswith('+ ema') for k, o in opts.items() for st in o.flat)
+        probed = list(opts)
     else:
         opts = {'flat AdamW': parallel.FlatAdamW(reducer, **kw), 'flat Adam': parallel.FlatAdam(reducer, **kw),
                 'flat SGD': parallel.FlatSGD(reducer, momentum=0.9, **kw)}
@@ -195,6 +210,13 @@ def main():
                           'bytes_per_s': bw, 'share_of_hbm_peak': bw / HBM_PEAK, 'share_of_hbm_copy': bw / HBM_COPY}
         print(f'{k:{wid}s} {" ".join(f"{x:.4f}" for x in ms):28s} {med:8.4f} {max(ms) - min(ms):8.4f} {bytes_per[k]:8d} {bw / 1e12:7.2f} '
               f'{bw / HBM_PEAK:7.1%} {bw / HBM_COPY:8.1%}')
+    if a.ema:
+        res['ema_added'] = {}
+        for k in [k for k in opts if not k.endswith('+ ema')]:
+            add = res['rows'][k + ' + ema']['median_ms'] - res['rows'][k]['median_ms']
+            bw = 12 * n_flat / (add * 1e-3) if add > 0 else float('inf')
+            res['ema_added'][k] = {'added_ms': add, 'bytes_per_s': bw, 'share_of_hbm_copy': bw / HBM_COPY}
+            print(f'{k}: the average adds {add:.4f} ms per step = {bw / 1e12:.2f} TB/s at 12 B / parameter ({bw / HBM_COPY:.1%} of 6.29)')
     for k, c in sclk.items():
         print(f'shader clock under {k}: ' + (f'{c["median"]:.3f} GHz median (p10 {c["p10"]:.3f}, p90 {c["p90"]:.3f}, {c["windows"]} windows '
                                              f'of {c["window_us"]} us)' if c else 'not sampled'))
