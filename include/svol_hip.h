@@ -559,6 +559,29 @@ int svol_ingest_resize(const uint8_t* src, int64_t n, int64_t H, int64_t W, int6
                        const int32_t* xtab, int64_t kx, const int32_t* ytab, int64_t ky, const float* lut, const uint8_t* flip,
                        void* out, int64_t o_n, int64_t o_c, int64_t o_h, int64_t o_w, int64_t OH, int64_t OW, int out_dtype,
                        void* stream);
+/* svol_ingest_resize's contract generalised to the sketch input and to Pillow's other filters (the reference makes every QuickDraw
+ * sketch by Image.fromarray(255 - bitmap.reshape(28, 28)).resize((224, 224), Image.BICUBIC), preprocess/quickdraw_array_to_pil.py:36,
+ * and opens sketch files with .convert('RGB') before Resize((224,224)) + ToTensor(), lib/dataset/svol_dataset.py:212-229):
+ *   s[y, x, c]  = invert ? 255 - src[y, x, c] : src[y, x, c]                           where the byte is staged, BEFORE the taps
+ *   t[y, x, c]  = clip8((2^21 + sum_i s[y, xs[x] + i, c] * kx_tab[x, i]) >> 22)        int32, arithmetic shift, clamp to [0, 255]
+ *   u[y', x, c] = clip8((2^21 + sum_j t[ys[y'] + j, x, c] * ky_tab[y', j]) >> 22)      likewise
+ *   out[img, c, y', flip[img] ? OW-1-x : x] = (out_dtype) lut[c][u[y', x, min(c, src_channels - 1)]]
+ * src_channels 3: as above, c = 0..2 at channel stride 1.  src_channels 1: src[img, y, x] is one byte per pixel (what .convert('RGB')
+ * replicates); one channel goes through both passes and the three output channels are made at the store.  s_w is the pixel stride in
+ * bytes and stays free (an RGBA view, one channel of an interleaved image, a cropped view).  invert 0 / 1.  The taps are SIGNED:
+ * svol_amd.ingest.resample_tables(in, out, filter) for filter = box, bilinear, hamming, bicubic (a = -0.5) or lanczos, i.e. Pillow's
+ * precompute_coeffs + normalize_coeffs_8bpc; 255 * sum_i |tap_i| + 2^21 < 2^31 holds for all of them, so int32 never overflows.  An
+ * axis of unchanged size has the identity's taps under every filter (Pillow skips that pass).  Inverting the result is NOT the same as
+ * inverting the source under a filter with negative lobes: the clamps sit at the other end.
+ * Everything else is svol_ingest_resize's: flip, the strided fp32 NCHW / 16-bit NHWC store, nothing read outside the addressed
+ * bytes, kx, ky <= 64 (box up to a 62-fold, bilinear / hamming a 31-fold, bicubic a 15-fold, lanczos a 10-fold downscale per axis),
+ * OH, OW <= 16384, H, W <= 2^24, the window growth bound ceil((t-1) in/out) + k (it holds for any support s, as k = 2 ceil(s) + 1),
+ * n == 0 -> SVOL_OK without a launch, SVOL_E_INVALID for src_channels other than 1 / 3 or invert other than 0 / 1.  No atomics, no
+ * scratch, no allocation, no synchronisation: capture-safe.  A new symbol only: the ABI version is unchanged. */
+int svol_ingest_resample(const uint8_t* src, int64_t n, int64_t H, int64_t W, int64_t s_n, int64_t s_h, int64_t s_w, int src_channels,
+                         int invert, const int32_t* xtab, int64_t kx, const int32_t* ytab, int64_t ky, const float* lut,
+                         const uint8_t* flip, void* out, int64_t o_n, int64_t o_c, int64_t o_h, int64_t o_w, int64_t OH, int64_t OW,
+                         int out_dtype, void* stream);
 
 /* ---- ViT-B/16 feature extractor pieces (the Hugging Face ViTModel the reference's ViT backbone calls,
  * lib/modeling/backbone.py:30,48; inference only) ----------------------------------------------------------------

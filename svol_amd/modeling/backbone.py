@@ -45,7 +45,7 @@ import torch
 from torch import nn
 
 from .. import _lib, layers, ops, params
-from ..ingest import FrameIngest, is_raw_frames
+from ..ingest import FrameIngest, is_raw_frames, sketch_frames
 from ..ops import _DT, _ptr, _stream
 
 
@@ -387,13 +387,20 @@ class ViTBackbone(nn.Module):
     Raw frames — uint8 [B,T,H,W,3] (sketch [B,1,H,W,3]), or a list of B tensors [T,H_b,W_b,3] of any sizes — first go through the
     FrameIngest this backbone owns: what ViTFeatureExtractor(images=[frame]) does inside the reference's forward (backbone.py:31,49:
     PIL bilinear resize to 224 x 224, x 1/255, mean / std 0.5), bit for bit, into the fp32 NCHW pixel_values the extractor takes.
-    ``pixel_preset`` overrides 'vit'.  Float inputs take exactly the path they always took."""
+    ``pixel_preset`` overrides 'vit'.  ``sketch_filter`` / ``sketch_invert`` give the sketch an ingest of its own, with another of
+    Pillow's filters and / or inverted source bytes (preprocess/quickdraw_array_to_pil.py:36 is sketch_filter='bicubic',
+    sketch_invert=True on the 28 x 28 bitmaps); a raw sketch may be grey, uint8 [B,1,H,W] or [B,1,H,W,1] (what .convert('RGB')
+    replicates, svol_dataset.py:212-229).  With both unset the sketch goes through the frames' ingest.  Float inputs take exactly
+    the path they always took."""
 
     def __init__(self, video_backbone: ViTExtractor, sketch_backbone: ViTExtractor, use_sketch_cls_token: bool = True,
-                 frames_per_launch: int = 512, pixel_preset=None):
+                 frames_per_launch: int = 512, pixel_preset=None, sketch_filter=None, sketch_invert=False):
         super().__init__()
         s = video_backbone.cfg.image_size
         self.ingest = FrameIngest((s, s), pixel_preset or 'vit', out='nchw_f32')
+        self.sketch_ingest = self.ingest
+        if sketch_filter is not None or sketch_invert:
+            self.sketch_ingest = FrameIngest((s, s), pixel_preset or 'vit', out='nchw_f32', filter=sketch_filter or 'bilinear', invert=sketch_invert)
         self.video_backbone = video_backbone
         self.sketch_backbone = sketch_backbone
         self.use_sketch_cls_token = use_sketch_cls_token
@@ -404,7 +411,7 @@ class ViTBackbone(nn.Module):
         with torch.set_grad_enabled(self.sketch_backbone.uses_autograd() or self.video_backbone.uses_autograd()):
             B = len(src_video)
             if is_raw_frames(src_sketch):
-                src_sketch = self.ingest(src_sketch)
+                src_sketch = self.sketch_ingest(sketch_frames(src_sketch))
                 src_sketch = src_sketch.view(B, -1, *src_sketch.shape[-3:])
             if is_raw_frames(src_video):
                 src_video = self.ingest(src_video)

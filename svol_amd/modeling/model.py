@@ -3,7 +3,8 @@
 ``build_model(args)`` / ``SketchLocalizationModel.forward(src_sketch, src_video, src_sketch_mask,
 src_video_mask)`` keep the reference's signatures and the ``backbone.`` / ``head.`` state-dict
 prefixes.  The online extractors also take RAW frames — uint8 ``[B,T,H,W,3]`` / ``[B,1,H,W,3]`` or lists of ``[T,H_b,W_b,3]`` — and
-resize and normalise them on the device (svol_amd/ingest.py; ``args.pixel_preset`` overrides the backbone's preset).  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
+resize and normalise them on the device (svol_amd/ingest.py; ``args.pixel_preset`` overrides the backbone's preset; ``args.sketch_filter`` / ``args.sketch_invert`` give the sketch another of
+Pillow's filters / inverted source bytes, and a raw sketch may be grey, ``[B,1,H,W]``).  ``--backbone features`` plugs pre-extracted features in at the measured boundary (SURVEY.md D3);
 ``--backbone vit`` runs the ViT-B/16 extractor of ``backbone.py`` on the device for every frame and the sketch
 (SURVEY.md §8 f1), frozen unless ``args.train_backbone`` is 1 (``--finetune_layers K``: only the last K layers and the final
 LayerNorm train, as preprocess/sketch_vit_finetune.py does).  ``--compute_dtype fp16`` gives both ViT extractors fp16 operands, in the
@@ -43,6 +44,8 @@ def build_backbone(args):
         args.input_vid_dim = getattr(args, 'input_vid_dim', 512)
         args.input_skch_dim = getattr(args, 'input_skch_dim', 512)
         return FeatureBackbone()
+    # the sketch's own ingest (svol_amd/ingest.py): set on the args object like pixel_preset, no command-line flag
+    sk = dict(sketch_filter=getattr(args, 'sketch_filter', None), sketch_invert=bool(getattr(args, 'sketch_invert', False)))
     if 'vit' in args.backbone:  # backbone.py:117-132: ViT-B/16 for frames and sketch, 768-wide features
         from .backbone import ViTBackbone, ViTExtractor, vit_base_config
         args.input_vid_dim = 768
@@ -55,7 +58,7 @@ def build_backbone(args):
         cd = 'fp16' if getattr(args, 'compute_dtype', 'bf16') == 'fp16' else 'bf16'   # (module docstring)
         return ViTBackbone(ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
                            ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
-                           pixel_preset=getattr(args, 'pixel_preset', None))
+                           pixel_preset=getattr(args, 'pixel_preset', None), **sk)
     if 'resnet' in args.backbone:  # backbone.py:133-152: ResNet-34 on the frames (7x7 tokens), ResNet-18 + avgpool on the sketch
         from .resnet import ResNetBackbone, resnet18, resnet34
         args.input_vid_dim = 512
@@ -72,7 +75,7 @@ def build_backbone(args):
         sync = bool(getattr(args, 'sync_bn', False))   # train.py:65-68: apex convert_syncbn_model
         return ResNetBackbone(resnet34(compute_dtype=cd, trainable=tb, sync_bn=sync),
                               resnet18(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync),
-                              pixel_preset=getattr(args, 'pixel_preset', None))
+                              pixel_preset=getattr(args, 'pixel_preset', None), **sk)
     raise NotImplementedError(f"backbone '{args.backbone}' is not part of the MI355X build (the reference has it commented out)")
 
 

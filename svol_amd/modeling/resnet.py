@@ -38,7 +38,7 @@ import torch
 from torch import nn
 
 from .. import ops, params, wgrad
-from ..ingest import FrameIngest, is_raw_frames
+from ..ingest import FrameIngest, is_raw_frames, sketch_frames
 
 _DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32,
            torch.bfloat16: torch.bfloat16, torch.float16: torch.float16, torch.float32: torch.float32}
@@ -358,14 +358,22 @@ class ResNetBackbone(nn.Module):
     Raw frames — uint8 [N,T,H,W,3] (sketch [N,1,H,W,3]), or a list of N tensors [T,H_b,W_b,3] of any sizes — go through the
     FrameIngest this backbone owns (svol_dataset.py:218-229: Resize((224,224)) + ToTensor(); ``pixel_preset`` overrides
     'totensor'): with two extractors of one 16-bit type (bf16 or fp16) it writes the NHWC image in that type, which the stem's
-    im2col reads directly.  Float inputs take exactly the path they always took."""
+    im2col reads directly.  ``sketch_filter`` / ``sketch_invert`` give the sketch an ingest of its own, with another of Pillow's
+    filters and / or inverted source bytes (preprocess/quickdraw_array_to_pil.py:36 is sketch_filter='bicubic', sketch_invert=True
+    on the 28 x 28 bitmaps); a raw sketch may be grey, uint8 [N,1,H,W] or [N,1,H,W,1] (what .convert('RGB') replicates,
+    svol_dataset.py:212-229).  With both unset the sketch goes through the frames' ingest.  Float inputs take exactly the path
+    they always took."""
 
-    def __init__(self, video_backbone, sketch_backbone, pixel_preset=None):
+    def __init__(self, video_backbone, sketch_backbone, pixel_preset=None, sketch_filter=None, sketch_invert=False):
         super().__init__()
         self.video_backbone = video_backbone
         self.sketch_backbone = sketch_backbone
         self.nhwc = video_backbone.compute_dtype in _H16 and sketch_backbone.compute_dtype == video_backbone.compute_dtype
-        self.ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out=_NHWC_OUT[video_backbone.compute_dtype] if self.nhwc else 'nchw_f32')
+        out = _NHWC_OUT[video_backbone.compute_dtype] if self.nhwc else 'nchw_f32'
+        self.ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out=out)
+        self.sketch_ingest = self.ingest
+        if sketch_filter is not None or sketch_invert:
+            self.sketch_ingest = FrameIngest((224, 224), pixel_preset or 'totensor', out=out, filter=sketch_filter or 'bilinear', invert=sketch_invert)
 
     def forward(self, sketch_batch, video_batch):
         if is_raw_frames(sketch_batch) or is_raw_frames(video_batch):
@@ -378,11 +386,11 @@ class ResNetBackbone(nn.Module):
     def _forward_raw(self, sketch_batch, video_batch):
         N = len(video_batch)
 
-        def run(extractor, x):
+        def run(extractor, x, ingest):
             if is_raw_frames(x):
-                pix = self.ingest(x)
+                pix = ingest(x)
                 return extractor(pix.flatten(0, 1) if pix.dim() == 5 else pix, nhwc=self.nhwc)
             return extractor(x.flatten(0, 1))
-        src_sketch = run(self.sketch_backbone, sketch_batch).view(N, -1, self.sketch_backbone.out_channels)
-        tok = run(self.video_backbone, video_batch)                             # [N*T, h*w, C]
+        src_sketch = run(self.sketch_backbone, sketch_frames(sketch_batch), self.sketch_ingest).view(N, -1, self.sketch_backbone.out_channels)
+        tok = run(self.video_backbone, video_batch, self.ingest)                         # [N*T, h*w, C]
         return src_sketch, tok.reshape(N, -1, tok.shape[2])

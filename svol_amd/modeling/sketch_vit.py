@@ -24,7 +24,9 @@ state-dict keys of ``ViTForImageClassification`` (``vit.*``, ``classifier.*``). 
     loss(pixel_values, targets)  (mean cross-entropy, top-1 hits) through svol_softmax_xent.
 
 Not here: the script's host-side data loop (ImageFolder, albumentations, file writing); hand over ``pixel_values``, or uint8 frames
-through ``svol_amd.ingest.FrameIngest``.
+through ``svol_amd.ingest.FrameIngest``: ``FrameIngest((224, 224), 'vit', filter=..., invert=...)`` takes grey sketches
+(``[n,H,W]`` uint8, what ``ImageFolder``'s ``.convert('RGB')`` replicates) and any of Pillow's filters, so QuickDraw's raw 28 x 28
+bitmaps enter as ``filter='bicubic', invert=True`` (preprocess/quickdraw_array_to_pil.py:36).
 """
 from __future__ import annotations
 

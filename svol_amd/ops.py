@@ -479,6 +479,24 @@ def ingest_resize(src, xtab, kx, ytab, ky, lut, flip, out, out_strides, OH, OW):
     return out
 
 
+def ingest_resample(src, xtab, kx, ytab, ky, lut, flip, out, out_strides, OH, OW, invert=False):
+    """ingest_resize generalised: any of Pillow's filters (signed taps: svol_amd.ingest.resample_tables(in, out, filter)), grey
+    sources, and an inversion of the source bytes before the taps.  src is uint8 [n,H,W,3] (channel stride 1) or a grey [n,H,W]
+    (any strides); the three output channels of a grey source are lut[c][u].  See svol_ingest_resample in include/svol_hip.h."""
+    grey = src.dim() == 3
+    if src.dtype != torch.uint8 or not (grey or (src.dim() == 4 and src.shape[3] == 3 and (not src.shape[0] or src.stride(3) == 1))):
+        raise _lib.SvolHipError(f'ingest_resample takes uint8 [n,H,W,3] with channel stride 1 or uint8 [n,H,W], got {src.dtype} {tuple(src.shape)}')
+    n, H, W = src.shape[:3]
+    if n == 0:   # (an empty tensor has no data pointer to pass)
+        return out
+    o_n, o_c, o_h, o_w = out_strides
+    rc = _lib.lib().svol_ingest_resample(_ptr(src), n, H, W, src.stride(0), src.stride(1), src.stride(2), 1 if grey else 3, int(bool(invert)),
+                                         _ptr(xtab), kx, _ptr(ytab), ky, _ptr(lut), _ptr(flip), _ptr(out), o_n, o_c, o_h, o_w, OH, OW,
+                                         _dt(out), _stream())
+    _lib.check(rc, 'svol_ingest_resample')
+    return out
+
+
 def conv_nhwc(x, w, bias, act, N, H, W, C, kh, kw, stride, pad, residual=None):
     """convolution of an NHWC activation [N*H*W, C] with folded weights w [Cout, kh*kw*C (+pad)] -> (y [N*Ho*Wo, Cout], Ho, Wo).
     The implicit-GEMM kernel when the shape fits it (bf16 or fp16, C % 32 == 0), else im2col + gemm_nt."""
