@@ -267,7 +267,10 @@ int svol_act_bwd(const void* dy, const void* aux, void* dpre, int act, int64_t n
  * a captured hipGraph draws a fresh mask on every replay; the stand-alone and attention dropouts have the same rule at their
  * own stride (svol_dropout_sd below: seed + (seed_step_dev[0] << 12)).  mean/rstd
  * fp32 [M] are saved for backward.  nn.LayerNorm + nn.Dropout of svanet.py:168-178; post-norms
- * cross_modal_transformer.py:127-158. */
+ * cross_modal_transformer.py:127-158.
+ * Limits (forward and backward): D % 4 == 0 and D <= 4096, else SVOL_E_UNSUPPORTED.  D <= 1024: one wave per row; 1024 < D <= 4096
+ * (2048-wide ResNet-50 / I3D features, concat_to_seq on ViT features): one workgroup of four waves per row, the same contract — every
+ * output combination, x_f32, pos / pos_rows, the same dropout keep function of (seed, row, column), accumulating sinks in the backward. */
 int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float* beta, float* y32, void* y,
                        void* ypos, const void* pos, int64_t pos_rows, float* mean, float* rstd, int64_t M, int64_t D,
                        float dropout_p, uint64_t seed, const int64_t* seed_offset_dev, int dtype, void* stream);

@@ -82,7 +82,7 @@ _OPTIONS = [
     (('--aspect_ratio_grouping',), dict(type=bool, default=False)),
     # model
     (('--sketch_head',), dict(type=str, default='svanet', choices=['svanet', 'sketch_detr', 'svanet_variants'])),
-    (('--backbone',), dict(type=str, default='vit', choices=['vit', 'resnet', 's3d', 'features'])),
+    (('--backbone',), dict(type=str, default='vit', choices=['vit', 'resnet', 'resnet50', 's3d', 'features'])),
     (('--hidden_dim',), dict(type=int, default=256)),
     (('--nheads',), dict(type=int, default=8)),
     (('--num_layers',), dict(type=int, default=4)),
@@ -116,8 +116,8 @@ _OPTIONS = [
 _EXTRA = [
     (('--compute_dtype',), dict(type=str, default='bf16', choices=['bf16', 'fp16', 'fp32'],
                                 help='element type of the HIP kernels (fp32 accumulate either way)')),
-    (('--input_vid_dim',), dict(type=int, default=512, help='feature width with --backbone features')),
-    (('--input_skch_dim',), dict(type=int, default=512, help='feature width with --backbone features')),
+    (('--input_vid_dim',), dict(type=int, default=512, help='feature width with --backbone features (up to 4096)')),
+    (('--input_skch_dim',), dict(type=int, default=512, help='feature width with --backbone features (up to 4096)')),
     # the enc/dec Transformer heads (sketch_detr, svanet_variants) read these; the reference never defines them, which is
     # why its own --sketch_head sketch_detr cannot be built from its option surface
     (('--enc_layers',), dict(type=int, default=6)),

@@ -1,11 +1,12 @@
 // LayerNorm (+dropout, +positional add) and sine positional encoding — HBM-bound row kernels.
 // One wave (64 lanes) per row, 4 contiguous elements per lane per pass (8 B bf16 / 16 B f32
-// coalesced loads), fp32 statistics, wave shuffle reductions (no LDS).
+// coalesced loads), fp32 statistics, wave shuffle reductions (no LDS).  Rows wider than 1024 columns (up to 4096): one
+// workgroup of four waves per row, the row sums exchanged through LDS (lnw_fwd_kernel / lnw_bwd_kernel).
 #include "common.h"
 
 namespace {
 
-constexpr int LN_MAX_PASSES = 4;  // D <= 4 * 64 * 4 = 1024
+constexpr int LN_MAX_PASSES = 4;  // one wave per row: D <= 4 * 64 * 4 = 1024; wider rows (to LNW_MAX_D) take the lnw_* kernels below
 
 // T  = element type of the compute-dtype outputs / gradients, TX = element type of the LN input
 // (float when the input is the fp32 residual stream).
@@ -199,6 +200,207 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     }
 }
 
+// ---- wide rows: 1024 < D <= 4096 (pre-extracted 2048-d features, ResNet-50 tokens, concat_to_seq on ViT features) -----------------
+// One wave per row would hold 64 values per lane per array at D = 4096; the backward's three per-column accumulators alone would be
+// 192 registers.  Here the four waves of a workgroup share a row: thread t owns the 4-column vectors (t + 256 j) * 4, j < NV
+// (NV = passes of 1024 columns: 2, 3 or 4 — at most 16 columns per lane per array), the two row sums go wave_sum -> four LDS words ->
+// one barrier.  Every column belongs to exactly ONE thread of the workgroup, so the backward's column reductions need no fold across
+// waves: the workgroup's sums pass through LDS only to reach the sinks (or the deterministic mode's scratch row) in lane order.
+constexpr int LNW_MAX_D = 4096;
+
+template <typename T, typename TX, int NV>
+__global__ __launch_bounds__(256) void lnw_fwd_kernel(const TX* __restrict__ x, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float* __restrict__ y32,
+                                                      T* __restrict__ y, T* __restrict__ ypos, const T* __restrict__ pos,
+                                                      int64_t pos_rows, float* __restrict__ mean, float* __restrict__ rstd,
+                                                      int64_t M, int D, float p, float inv_keep, uint64_t seed0,
+                                                      const int64_t* __restrict__ soff) {
+    __shared__ float red[2][4];
+    const uint64_t seed = seed0 + (soff ? ((uint64_t)soff[0] << 8) : 0ull);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row = blockIdx.x;   // one row per workgroup (grid = M)
+    const TX* xr = x + row * D;
+    const T* pr = pos ? pos + (row % pos_rows) * D : nullptr;
+    // as in the narrow kernel: every load of the row goes out before the first reduction
+    Vec4<TX> t[NV];
+    Vec4<T> pv[NV];
+    Vec4<float> gv[NV], bv[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+        if (c < D) {
+            t[j].load(xr + c);
+            if (pr) pv[j].load(pr + c);
+            gv[j].load(gamma + c);
+            bv[j].load(beta + c);
+        }
+    }
+    float v[NV][4];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[j][e] = c < D ? t[j].get(e) : 0.f;
+            s += v[j][e];
+        }
+    }
+    s = wave_sum(s);
+    if (lane == 0) red[0][wave] = s;
+    __syncthreads();
+    const float mu = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+        if (c < D) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mu; q += d * d; }
+        }
+    }
+    q = wave_sum(q);
+    if (lane == 0) red[1][wave] = q;
+    __syncthreads();
+    const float rs = rsqrtf(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D + 1e-5f);
+    if (tid == 0) { mean[row] = mu; rstd[row] = rs; }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+        if (c < D) {
+            Vec4<T> o, op;
+            Vec4<float> o32;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float r = (v[j][e] - mu) * rs * gv[j].get(e) + bv[j].get(e);
+                if (p > 0.f) r *= dropout_scale(seed, (uint64_t)row, (uint32_t)(c + e), p, inv_keep);
+                o.set(e, r);
+                o32.set(e, r);
+                if (pr) op.set(e, r + pv[j].get(e));
+            }
+            if (y32) o32.store(y32 + row * D + c);
+            if (y) o.store(y + row * D + c);
+            if (ypos) op.store(ypos + row * D + c);
+        }
+    }
+}
+
+// A workgroup walks `rows_per_wg` consecutive rows; the NEXT row's operands are fetched before the current row's sums are exchanged
+// (one barrier per row: the LDS words alternate by row parity, so a wave that runs ahead writes the other set).
+template <typename T, typename TX, int NV>
+__global__ __launch_bounds__(256) void lnw_bwd_kernel(const float* __restrict__ dy32, const T* __restrict__ dy,
+                                                      const T* __restrict__ dy2, const TX* __restrict__ x,
+                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, float* __restrict__ dx32,
+                                                      T* __restrict__ dx, float* __restrict__ dgamma,
+                                                      float* __restrict__ dbeta, float* __restrict__ dxsum, int64_t M, int D,
+                                                      float p, float inv_keep, uint64_t seed0, const int64_t* __restrict__ soff, int rows_per_wg,
+                                                      float* __restrict__ det_part) {
+    __shared__ float red[2][2][4];
+    const uint64_t seed = seed0 + (soff ? ((uint64_t)soff[0] << 8) : 0ull);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
+    const int64_t rend = (r0 + rows_per_wg < M) ? r0 + rows_per_wg : M;
+    float dg[NV][4], db[NV][4], dxs[NV][4], gm[NV][4];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { dg[j][e] = 0.f; db[j][e] = 0.f; dxs[j][e] = 0.f; gm[j][e] = c < D ? gamma[c + e] : 0.f; }
+    }
+    struct Row { Vec4<float> a32[NV]; Vec4<T> a[NV], b[NV]; Vec4<TX> xv[NV]; float mu, rs; };
+    auto fetch = [&](int64_t row, Row& r) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (tid + 256 * j) * 4;
+            if (c < D) {
+                if (dy32) r.a32[j].load(dy32 + row * D + c);
+                if (dy) r.a[j].load(dy + row * D + c);
+                if (dy2) r.b[j].load(dy2 + row * D + c);
+                r.xv[j].load(x + row * D + c);
+            }
+        }
+        r.mu = mean[row];
+        r.rs = rstd[row];
+    };
+    Row cur, nxt;
+    if (r0 < rend) fetch(r0, cur);
+    int par = 0;
+    for (int64_t row = r0; row < rend; ++row) {   // (r0, rend are uniform over the workgroup: every thread meets every barrier)
+        if (row + 1 < rend) fetch(row + 1, nxt);
+        const float mu = cur.mu, rs = cur.rs;
+        float g[NV][4], xh[NV][4];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (tid + 256 * j) * 4;
+            if (c < D) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float d = (dy32 ? cur.a32[j].get(e) : 0.f) + (dy ? cur.a[j].get(e) : 0.f) + (dy2 ? cur.b[j].get(e) : 0.f);
+                    if (p > 0.f) d *= dropout_scale(seed, (uint64_t)row, (uint32_t)(c + e), p, inv_keep);
+                    const float h = (cur.xv[j].get(e) - mu) * rs;
+                    xh[j][e] = h;
+                    dg[j][e] += d * h;
+                    db[j][e] += d;
+                    const float gg = d * gm[j][e];
+                    g[j][e] = gg;
+                    s1 += gg;
+                    s2 += gg * h;
+                }
+            }
+        }
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        if (lane == 0) { red[par][0][wave] = s1; red[par][1][wave] = s2; }
+        __syncthreads();
+        s1 = ((red[par][0][0] + red[par][0][1]) + (red[par][0][2] + red[par][0][3])) / (float)D;
+        s2 = ((red[par][1][0] + red[par][1][1]) + (red[par][1][2] + red[par][1][3])) / (float)D;
+        par ^= 1;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (tid + 256 * j) * 4;
+            if (c < D) {
+                Vec4<T> o;
+                Vec4<float> o32;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float r = rs * (g[j][e] - s1 - xh[j][e] * s2);
+                    dxs[j][e] += r;
+                    o.set(e, r);
+                    o32.set(e, r);
+                }
+                if (dx32) o32.store(dx32 + row * D + c);
+                if (dx) o.store(dx + row * D + c);
+            }
+        }
+        cur = nxt;
+    }
+    // every column has ONE owner in the workgroup, so there is nothing to fold; the sums still go through LDS so that consecutive lanes
+    // add to consecutive addresses (a lane owns 4 neighbouring columns: straight from registers a wave's atomic instruction would spread
+    // over 8 cache lines, and each line would be visited by 4 instructions)
+    __shared__ float acc[3][NV * 1024];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = (tid + 256 * j) * 4;
+        if (c < D) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { acc[0][c + e] = dg[j][e]; acc[1][c + e] = db[j][e]; acc[2][c + e] = dxs[j][e]; }
+        }
+    }
+    __syncthreads();
+    if (det_part) {   // deterministic mode: this workgroup's row of the scratch, folded in index order by det_fold
+        float* part = det_part + (int64_t)blockIdx.x * 3 * D;
+        for (int c = tid; c < D; c += 256) { part[c] = acc[0][c]; part[D + c] = acc[1][c]; part[2 * D + c] = acc[2][c]; }
+        return;
+    }
+    for (int c = tid; c < D; c += 256) {
+        atomicAdd(dgamma + c, acc[0][c]);
+        atomicAdd(dbeta + c, acc[1][c]);
+        if (dxsum) atomicAdd(dxsum + c, acc[2][c]);
+    }
+}
+
 // position_encoding.py:51-71 — one workgroup per batch row: inclusive scan of the mask over L,
 // then pos[l, 2i] = sin(x / t_i), pos[l, 2i+1] = cos(x / t_i) with x = cumsum/(last+1e-6)*2pi.
 // grid = (ceil(L/64), B): every block re-reduces the (tiny) mask prefix it needs, then writes 64 tokens.
@@ -303,21 +505,29 @@ int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float
     if (!aligned16(gamma) || !aligned16(beta)) return SVOL_E_INVALID;   // (16-byte vector loads of the affine parameters)
     if ((ypos != nullptr) != (pos != nullptr)) return SVOL_E_INVALID;
     if (pos && pos_rows <= 0) return SVOL_E_INVALID;
-    if (D % 4 || D > LN_MAX_PASSES * 256) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > LNW_MAX_D) return SVOL_E_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return SVOL_E_INVALID;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     if (M == 0) return SVOL_OK;
     const float inv_keep = 1.f / (1.f - dropout_p);
-    const unsigned grid = (unsigned)((M + 3) / 4);
+    const bool wide = D > LN_MAX_PASSES * 256;
+    if (wide && M > 0x7fffffffll) return SVOL_E_UNSUPPORTED;   // (one workgroup per row)
+    const unsigned grid = wide ? (unsigned)M : (unsigned)((M + 3) / 4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 #define SVOL_LNF(TT, TXX, NPP)                                                                                              \
     hipLaunchKernelGGL((ln_fwd_kernel<TT, TXX, NPP>), dim3(grid), dim3(256), 0, s, (const TXX*)x, gamma, beta, y32, (TT*)y,      \
                        (TT*)ypos, (const TT*)pos, pos_rows, mean, rstd, M, (int)D, dropout_p, inv_keep, seed, seed_offset_dev)
-#define SVOL_LNF_NP(TT, TXX)                     \
-    do {                                         \
-        if (D <= 256) SVOL_LNF(TT, TXX, 1);      \
-        else if (D <= 512) SVOL_LNF(TT, TXX, 2); \
-        else SVOL_LNF(TT, TXX, 4);               \
+#define SVOL_LNWF(TT, TXX, NVV)                                                                                             \
+    hipLaunchKernelGGL((lnw_fwd_kernel<TT, TXX, NVV>), dim3(grid), dim3(256), 0, s, (const TXX*)x, gamma, beta, y32, (TT*)y,     \
+                       (TT*)ypos, (const TT*)pos, pos_rows, mean, rstd, M, (int)D, dropout_p, inv_keep, seed, seed_offset_dev)
+#define SVOL_LNF_NP(TT, TXX)                      \
+    do {                                          \
+        if (D <= 256) SVOL_LNF(TT, TXX, 1);       \
+        else if (D <= 512) SVOL_LNF(TT, TXX, 2);  \
+        else if (!wide) SVOL_LNF(TT, TXX, 4);     \
+        else if (D <= 2048) SVOL_LNWF(TT, TXX, 2); \
+        else if (D <= 3072) SVOL_LNWF(TT, TXX, 3); \
+        else SVOL_LNWF(TT, TXX, 4);               \
     } while (0)
     if (dtype == SVOL_BF16 && x_f32) SVOL_LNF_NP(bf16_t, float);
     else if (dtype == SVOL_BF16) SVOL_LNF_NP(bf16_t, bf16_t);
@@ -325,6 +535,7 @@ int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float
     else if (dtype == SVOL_F16) SVOL_LNF_NP(f16_t, f16_t);
     else SVOL_LNF_NP(float, float);
 #undef SVOL_LNF_NP
+#undef SVOL_LNWF
 #undef SVOL_LNF
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
@@ -336,16 +547,21 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
                        int dtype, void* stream) {
     if ((!dy32 && !dy && !dy2) || !x || !gamma || !mean || !rstd || (!dx && !dx32) || !dgamma || !dbeta || M < 0 || D <= 0)
         return SVOL_E_INVALID;
-    if (D % 4 || D > LN_MAX_PASSES * 256) return SVOL_E_UNSUPPORTED;
+    if (D % 4 || D > LNW_MAX_D) return SVOL_E_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return SVOL_E_INVALID;
     if (!svol_is16(dtype) && dtype != SVOL_F32) return SVOL_E_INVALID;
     if (M == 0) return SVOL_OK;
     const float inv_keep = 1.f / (1.f - dropout_p);
     // ~2048 waves (512 workgroups); each wave walks `rpw` consecutive rows; one set of atomics per workgroup
-    int64_t rpw = (M + 2047) / 2048;
+    // (wide rows: as many workgroups as are resident at once — three to four per CU at NV = 2, two at NV = 3 / 4 — each walking `rpw`
+    // consecutive rows with all four waves on one row.  Fewer leave HBM latency uncovered, more only add sink atomics:
+    // profiles/layernorm_wide.md)
+    const bool wide = D > LN_MAX_PASSES * 256;
+    const int64_t lnw_wgs = D <= 2048 ? 1024 : 512;
+    int64_t rpw = wide ? (M + lnw_wgs - 1) / lnw_wgs : (M + 2047) / 2048;
     if (rpw < 1) rpw = 1;
     const int64_t waves = (M + rpw - 1) / rpw;
-    const unsigned grid = (unsigned)((waves + 3) / 4);
+    const unsigned grid = wide ? (unsigned)waves : (unsigned)((waves + 3) / 4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool det_mode = svol_deterministic();
     DetScratch det(det_mode ? (size_t)grid * 3 * (size_t)D : 0, s);   // deterministic mode: per-workgroup rows, folded below
@@ -357,11 +573,18 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     hipLaunchKernelGGL((ln_bwd_kernel<TT, TXX, NPP>), dim3(grid), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, (const TXX*)x, \
                        gamma, mean, rstd, dx32, (TT*)dx, dgamma, dbeta, dx_colsum, M, (int)D, dropout_p, inv_keep, seed,              \
                        seed_offset_dev, (int)rpw, det.p)
-#define SVOL_LNB_NP(TT, TXX)                  \
-    do {                                      \
-        if (D <= 256) SVOL_LNB(TT, TXX, 1);   \
-        else if (D <= 512) SVOL_LNB(TT, TXX, 2); \
-        else SVOL_LNB(TT, TXX, 4);            \
+#define SVOL_LNWB(TT, TXX, NVV)                                                                                                      \
+    hipLaunchKernelGGL((lnw_bwd_kernel<TT, TXX, NVV>), dim3(grid), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, (const TXX*)x, \
+                       gamma, mean, rstd, dx32, (TT*)dx, dgamma, dbeta, dx_colsum, M, (int)D, dropout_p, inv_keep, seed,               \
+                       seed_offset_dev, (int)rpw, det.p)
+#define SVOL_LNB_NP(TT, TXX)                      \
+    do {                                          \
+        if (D <= 256) SVOL_LNB(TT, TXX, 1);       \
+        else if (D <= 512) SVOL_LNB(TT, TXX, 2);  \
+        else if (!wide) SVOL_LNB(TT, TXX, 4);     \
+        else if (D <= 2048) SVOL_LNWB(TT, TXX, 2); \
+        else if (D <= 3072) SVOL_LNWB(TT, TXX, 3); \
+        else SVOL_LNWB(TT, TXX, 4);               \
     } while (0)
     if (dtype == SVOL_BF16 && x_f32) SVOL_LNB_NP(bf16_t, float);
     else if (dtype == SVOL_BF16) SVOL_LNB_NP(bf16_t, bf16_t);
@@ -369,6 +592,7 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     else if (dtype == SVOL_F16) SVOL_LNB_NP(f16_t, f16_t);
     else SVOL_LNB_NP(float, float);
 #undef SVOL_LNB_NP
+#undef SVOL_LNWB
 #undef SVOL_LNB
     if (det_mode) {
         det_fold(det.p, (int)grid, 3 * D, dgamma, D, s);

@@ -11,7 +11,8 @@ LayerNorm train, as preprocess/sketch_vit_finetune.py does).  ``--compute_dtype 
 frozen and the trainable path alike; a bf16 or fp32 head keeps the bf16 extractors (the short-sequence attention kernels have no fp32
 form).  Its default stays frozen, unlike the ResNet's: the reference's
 ViT backbone cannot run as shipped (``device`` is undefined in ViTBackbone.forward, backbone.py:30), so no reference run
-trains it, and existing users of ``--backbone vit`` keep the frozen extractors; ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4), frozen by default,
+trains it, and existing users of ``--backbone vit`` keep the frozen extractors; ``--backbone resnet`` the ResNet-34 / ResNet-18 extractors of ``resnet.py`` (f4)
+(``--backbone resnet50``: the reference's third pair, ResNet-50 for frames and sketch, 2048-wide features, same switches), frozen by default,
 trained with the head when ``args.train_backbone`` is set (what the reference's train.py does); they run in ``args.compute_dtype``,
 fp16 included in both modes.
 """
@@ -34,6 +35,26 @@ class FeatureBackbone(nn.Module):
         if src_video.dim() == 4:
             src_video = src_video.flatten(1, 2)
         return src_sketch, src_video
+
+
+def _resnet_backbone(args, video_net, sketch_net, width, sk):
+    """the ResNet pair of either depth: sets both input widths, reads --train_backbone / --freeze_backbone / --sync_bn / --compute_dtype"""
+    from .resnet import ResNetBackbone
+    args.input_vid_dim = width
+    args.input_skch_dim = width
+    cd = getattr(args, 'compute_dtype', 'bf16')
+    # the torchvision IMAGENET1K_V1 weights are loaded by the caller (load_state_dict with the reference's backbone.* keys) —
+    # nothing is downloaded here.  The reference TRAINS its backbone: train.py:72 hands every parameter of build_model(args) to
+    # the optimiser and model.train() puts BatchNorm into batch-statistics mode (its --freeze_backbone flag is parsed and never
+    # read).  So a reference-style run gets the trainable extractors (csrc/resnet_train.hip) by default; --freeze_backbone — dead
+    # in the reference, honoured here — or --train_backbone 0 selects the frozen, BatchNorm-folded extractors (inference, or the
+    # features-are-fixed setting bench.py --workload resnet measures without --train-backbone).
+    tb = getattr(args, 'train_backbone', None)
+    tb = (not bool(getattr(args, 'freeze_backbone', False))) if tb is None else bool(tb)
+    sync = bool(getattr(args, 'sync_bn', False))   # train.py:65-68: apex convert_syncbn_model
+    return ResNetBackbone(video_net(compute_dtype=cd, trainable=tb, sync_bn=sync),
+                          sketch_net(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync),
+                          pixel_preset=getattr(args, 'pixel_preset', None), **sk)
 
 
 def build_backbone(args):
@@ -59,23 +80,12 @@ def build_backbone(args):
         return ViTBackbone(ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
                            ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
                            pixel_preset=getattr(args, 'pixel_preset', None), **sk)
+    if args.backbone == 'resnet50':  # backbone.py:143-147: ResNet-50 on the frames and, average-pooled, on the sketch; 2048-wide features
+        from .resnet import resnet50
+        return _resnet_backbone(args, resnet50, resnet50, 2048, sk)
     if 'resnet' in args.backbone:  # backbone.py:133-152: ResNet-34 on the frames (7x7 tokens), ResNet-18 + avgpool on the sketch
-        from .resnet import ResNetBackbone, resnet18, resnet34
-        args.input_vid_dim = 512
-        args.input_skch_dim = 512
-        cd = getattr(args, 'compute_dtype', 'bf16')
-        # the torchvision IMAGENET1K_V1 weights are loaded by the caller (load_state_dict with the reference's backbone.* keys) —
-        # nothing is downloaded here.  The reference TRAINS its backbone: train.py:72 hands every parameter of build_model(args) to
-        # the optimiser and model.train() puts BatchNorm into batch-statistics mode (its --freeze_backbone flag is parsed and never
-        # read).  So a reference-style run gets the trainable extractors (csrc/resnet_train.hip) by default; --freeze_backbone — dead
-        # in the reference, honoured here — or --train_backbone 0 selects the frozen, BatchNorm-folded extractors (inference, or the
-        # features-are-fixed setting bench.py --workload resnet measures without --train-backbone).
-        tb = getattr(args, 'train_backbone', None)
-        tb = (not bool(getattr(args, 'freeze_backbone', False))) if tb is None else bool(tb)
-        sync = bool(getattr(args, 'sync_bn', False))   # train.py:65-68: apex convert_syncbn_model
-        return ResNetBackbone(resnet34(compute_dtype=cd, trainable=tb, sync_bn=sync),
-                              resnet18(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync),
-                              pixel_preset=getattr(args, 'pixel_preset', None), **sk)
+        from .resnet import resnet18, resnet34
+        return _resnet_backbone(args, resnet34, resnet18, 512, sk)
     raise NotImplementedError(f"backbone '{args.backbone}' is not part of the MI355X build (the reference has it commented out)")
 
 

@@ -1,4 +1,5 @@
-"""torchvision-style BasicBlock ResNet feature extractor (ResNet-18 / ResNet-34) on the MI355X kernels — SURVEY.md §8 f4.
+"""torchvision-style ResNet feature extractors (BasicBlock: ResNet-18 / ResNet-34; Bottleneck: ResNet-50) on the MI355X kernels —
+SURVEY.md §8 f4.
 
 The reference builds ``nn.Sequential(*list(resnet34(...).children())[:-2])`` for the frames and
 ``nn.Sequential(*list(resnet18(...).children())[:-1])`` for the sketch (backbone.py:133-152) and turns the frame feature
@@ -24,6 +25,12 @@ into the optimiser, and ``model.train()`` puts torchvision's BatchNorm into batc
 
 — plus max pooling with its argmax and the sketch branch's average pooling as Functions.  Activations bf16 / fp16 NHWC, statistics,
 parameters and parameter gradients fp32.
+
+Bottleneck (ResNet-50, backbone.py:143-147: frames ``[:-2]``, sketch ``[:-1]``, 2048-wide features): three units per block —
+conv1 1x1, conv2 3x3 CARRYING the stride (torchvision's v1.5 layout), conv3 1x1 to 4 * planes with the ReLU after the identity add — and
+a downsample in the first block of every stage (stage 4 too: 64 -> 256 at stride 1).  The same units in both modes; the 1x1 stride-1
+data gradients go through the same-size-convolution branch of ``_ConvBnFn.backward``, the stride-2 3x3 and the stride-2 1x1 downsample
+through GEMM + col2im.  ``nn.Sequential(*list(torchvision.models.resnet50().children())[:-2])`` state dicts load as they are.
 
 compute_dtype: 'bf16' (default), 'fp16' (what the reference's apex amp runs; both modes) or 'fp32' (frozen mode only, explicit
 im2col + fp32 GEMM).  fp16 runs the same kernels with fp16 operands (v_mfma_*_f16 at bf16's rate, three more mantissa bits, five
@@ -58,6 +65,26 @@ class BasicBlock(nn.Module):
         self.downsample = None
         if stride != 1 or inplanes != planes:
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
+        self.stride = stride
+
+
+class Bottleneck(nn.Module):
+    """torchvision.models.resnet.Bottleneck parameter layout: conv1/bn1 (1x1), conv2/bn2 (3x3, carries the stride), conv3/bn3 (1x1 to
+    4 * planes), downsample.{0,1}."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 1, 1, 0, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, 1, 0, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.downsample = None
+        if stride != 1 or inplanes != planes * self.expansion:
+            self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * self.expansion, 1, stride, bias=False),
+                                            nn.BatchNorm2d(planes * self.expansion))
         self.stride = stride
 
 
@@ -221,8 +248,12 @@ class _AvgPoolFn(torch.autograd.Function):
 
 class ResNetExtractor(nn.Module):
     def __init__(self, depths=(2, 2, 2, 2), widths=(64, 128, 256, 512), stem=64, avgpool=False, compute_dtype='bf16', trainable=False,
-                 sync_bn=False):
+                 sync_bn=False, block='basic'):
         super().__init__()
+        if block not in ('basic', 'bottleneck'):
+            raise ValueError(f"block must be 'basic' or 'bottleneck', got {block!r}")
+        self.block = block   # 'bottleneck': widths are the blocks' planes, a stage's output has 4 x as many channels
+        expansion = Bottleneck.expansion if block == 'bottleneck' else 1
         # --sync_bn (apex.parallel.convert_syncbn_model, train.py:65-68 / test.py:61): train-mode BatchNorm statistics over the
         # GLOBAL batch of all ranks of the default process group; no effect at world size 1 or on the frozen extractor
         self.sync_bn = bool(sync_bn)
@@ -232,8 +263,8 @@ class ResNetExtractor(nn.Module):
         for li, (n, planes) in enumerate(zip(depths, widths)):
             blocks = []
             for bi in range(n):
-                blocks.append(BasicBlock(inplanes, planes, (1 if li == 0 else 2) if bi == 0 else 1))
-                inplanes = planes
+                blocks.append((Bottleneck if block == 'bottleneck' else BasicBlock)(inplanes, planes, (1 if li == 0 else 2) if bi == 0 else 1))
+                inplanes = planes * expansion
             self.add_module(str(4 + li), nn.Sequential(*blocks))
         self.n_layers = len(depths)
         self.out_channels = inplanes
@@ -264,7 +295,10 @@ class ResNetExtractor(nn.Module):
         for li in range(self.n_layers):
             for bi, blk in enumerate(getattr(self, str(4 + li))):
                 pre = f'{4 + li}.{bi}.'
-                f['blocks'].append((blk.stride, blk.conv1.out_channels, fold(pre + 'conv1', blk.conv1, blk.bn1), fold(pre + 'conv2', blk.conv2, blk.bn2),
+                convs = [fold(pre + 'conv1', blk.conv1, blk.bn1), fold(pre + 'conv2', blk.conv2, blk.bn2)]
+                if self.block == 'bottleneck':
+                    convs.append(fold(pre + 'conv3', blk.conv3, blk.bn3))
+                f['blocks'].append((blk.stride, blk.conv1.out_channels, *convs,
                                     fold(pre + 'downsample.0', blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
         if dt == torch.float16:
             finite = torch.stack([torch.isfinite(w).all() for _, w in units]).tolist()   # one host read for the whole fold
@@ -312,6 +346,16 @@ class ResNetExtractor(nn.Module):
             for blk in getattr(self, str(4 + li)):
                 s_, planes = blk.stride, blk.conv1.out_channels
                 Ho, Wo = (H + 2 - 3) // s_ + 1, (W + 2 - 3) // s_ + 1
+                if self.block == 'bottleneck':
+                    t = _ConvBnFn.apply(y, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, None, (n, H, W, C, 1, 1, 1, 0), True, blk.bn1, dt, sync)
+                    t = _ConvBnFn.apply(t, blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, None, (n, H, W, planes, 3, 3, s_, 1), True, blk.bn2, dt, sync)
+                    idt = y
+                    if blk.downsample is not None:
+                        idt = _ConvBnFn.apply(y, blk.downsample[0].weight, blk.downsample[1].weight, blk.downsample[1].bias, None,
+                                              (n, H, W, C, 1, 1, s_, 0), False, blk.downsample[1], dt, sync)
+                    y = _ConvBnFn.apply(t, blk.conv3.weight, blk.bn3.weight, blk.bn3.bias, idt, (n, Ho, Wo, planes, 1, 1, 1, 0), True, blk.bn3, dt, sync)
+                    H, W, C = Ho, Wo, blk.conv3.out_channels
+                    continue
                 t = _ConvBnFn.apply(y, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, None, (n, H, W, C, 3, 3, s_, 1), True, blk.bn1, dt, sync)
                 idt = y
                 if blk.downsample is not None:
@@ -334,7 +378,16 @@ class ResNetExtractor(nn.Module):
         del cols
         C = w0.shape[0]
         y, H, W = ops.maxpool_nhwc(y, n, H, W, C, 3, 2, 1)
-        for stride, planes, (w1, b1), (w2, b2), down in f['blocks']:
+        for stride, planes, (w1, b1), (w2, b2), *rest in f['blocks']:
+            down = rest[-1]
+            if self.block == 'bottleneck':
+                w3, b3 = rest[0]
+                t = ops.conv_nhwc(y, w1, b1, ops.ACT_RELU, n, H, W, C, 1, 1, 1, 0)[0]
+                t, Ho, Wo = ops.conv_nhwc(t, w2, b2, ops.ACT_RELU, n, H, W, planes, 3, 3, stride, 1)
+                idt = ops.conv_nhwc(y, down[0], down[1], ops.ACT_NONE, n, H, W, C, 1, 1, stride, 0)[0] if down is not None else y
+                y = ops.conv_nhwc(t, w3, b3, ops.ACT_RELU_RES, n, Ho, Wo, planes, 1, 1, 1, 0, residual=idt)[0]
+                H, W, C = Ho, Wo, w3.shape[0]
+                continue
             t, Ho, Wo = ops.conv_nhwc(y, w1, b1, ops.ACT_RELU, n, H, W, C, 3, 3, stride, 1)
             idt = ops.conv_nhwc(y, down[0], down[1], ops.ACT_NONE, n, H, W, C, 1, 1, stride, 0)[0] if down is not None else y
             y, _, _ = ops.conv_nhwc(t, w2, b2, ops.ACT_RELU_RES, n, Ho, Wo, planes, 3, 3, 1, 1, residual=idt)
@@ -350,6 +403,11 @@ def resnet18(avgpool=False, compute_dtype='bf16', trainable=False, sync_bn=False
 
 def resnet34(avgpool=False, compute_dtype='bf16', trainable=False, sync_bn=False):
     return ResNetExtractor((3, 4, 6, 3), avgpool=avgpool, compute_dtype=compute_dtype, trainable=trainable, sync_bn=sync_bn)
+
+
+def resnet50(avgpool=False, compute_dtype='bf16', trainable=False, sync_bn=False):
+    """torchvision's ResNet-50 without its classifier (and, for the frames, without its average pool): 2048-wide features"""
+    return ResNetExtractor((3, 4, 6, 3), avgpool=avgpool, compute_dtype=compute_dtype, trainable=trainable, sync_bn=sync_bn, block='bottleneck')
 
 
 class ResNetBackbone(nn.Module):

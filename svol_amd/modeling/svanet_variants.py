@@ -139,6 +139,6 @@ def build_svanet(args):
     sketch_position_embed, video_position_embed = build_position_encoding(args)
     return SVANet(
         transformer, sketch_position_embed, video_position_embed, mode=args.mode,
-        input_dim=args.feat_dim if args.backbone != 'resnet' else 512, num_queries=args.num_queries,
+        input_dim={'resnet': 512, 'resnet50': 2048}.get(args.backbone, args.feat_dim), num_queries=args.num_queries,
         input_dropout=args.input_dropout, aux_loss=args.aux_loss, use_sketch_pos=args.use_sketch_pos,
         n_input_proj=args.n_input_proj, vis_mode=args.vis_mode, compute_dtype=getattr(args, 'compute_dtype', 'bf16'))
