@@ -728,6 +728,32 @@ int svol_attn_cls_fwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk
 int svol_attn_cls_bwd_h16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                           const void* dout, int64_t lddo, const float* lse2, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                           int64_t lddv, int64_t n, int64_t H, int64_t L, int64_t dh, float scale, int dtype, void* stream);
+/* ---- many queries, few keys: video tokens attending to the sketch's tokens (the "V2 (7x7)" lines, cross_modal_transformer.py:129-135;
+ * csrc/attn_fewkeys.hip).  The contract of svol_attn_fwd / svol_attn_bwd -- row-major operands with their own leading dimensions, head h
+ * in columns [h*dh, (h+1)*dh), kbias [B, Lk] fp32 0 / -inf or NULL, lse2 [B, H, Lq] in the log2 domain, q_premul as there, P and dS
+ * rounded to the operand type before their products, dq the gradient with respect to the UNscaled q -- for the shapes the families above
+ * serve badly: dtype SVOL_BF16 or SVOL_F16, dh in {32, 64}, 1 <= Lk <= 256, any 1 <= Lq <= 2^30 (B, H <= 65535).  Anything else returns
+ * SVOL_E_UNSUPPORTED before any launch and writes nothing (the caller then runs svol_attn_fwd / svol_attn_bwd).  Pointers to 16-bit
+ * operands and ws 16-byte aligned, lse2 / kbias 4-byte aligned, leading dimensions multiples of 8 and >= H*dh (SVOL_E_UNSUPPORTED
+ * otherwise); a null operand, lse2 or ws, B, H or Lq < 1, or ws_bytes below svol_attn_fewkeys_ws_bytes() is SVOL_E_INVALID.
+ * Order of the checks: first the limits on dtype, dh and Lk (Lk < 1 included: SVOL_E_UNSUPPORTED, whatever the pointers are), then
+ * null pointers and B, H, Lq < 1 (SVOL_E_INVALID), then the sizes above the limits, leading dimensions and alignment
+ * (SVOL_E_UNSUPPORTED), last the backward's ws (null or short: SVOL_E_INVALID; misaligned: SVOL_E_UNSUPPORTED).
+ * K and V of a (batch, head) are staged once per workgroup, which walks svol_attn_fewkeys_chunk_rows(Lq) = 256 ceil(Lq / 2048) queries
+ * (a function of Lq alone: at most 8 chunks).  The backward writes fp32 dK / dV partials per (batch, head, chunk) to ws and a second
+ * kernel adds them in chunk order and rounds them into dk / dv: no atomics, the same bits every run; nothing is allocated inside the
+ * library.  Keys >= Lk and queries >= Lq are never read or written.  A key with kbias = -inf has P = 0 exactly and its K / V rows are
+ * not used (they may hold NaN): its dk and dv rows are exactly 0.  A batch row whose keys are ALL masked is the caller's error (NaN, as
+ * in torch).  svol_attn_fewkeys_ws_bytes returns 0 for a shape outside the limits.  New symbols only: the ABI version is unchanged. */
+int64_t svol_attn_fewkeys_chunk_rows(int64_t Lq);
+int64_t svol_attn_fewkeys_ws_bytes(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh);
+int svol_attn_fewkeys_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse2,
+                          const float* kbias, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, float scale, float q_premul, int dtype,
+                          void* stream);
+int svol_attn_fewkeys_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                          const void* d_o, int64_t lddo, const float* lse2, const float* kbias, void* dq, int64_t lddq, void* dk, int64_t lddk,
+                          void* dv, int64_t lddv, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t dh, float scale, float q_premul,
+                          void* ws, int64_t ws_bytes, int dtype, void* stream);
 /* svol_softmax_xent: nn.CrossEntropyLoss() and its gradient (sketch_vit_finetune.py:107,141-142) on fp32 logits [n, C] (leading
  *   dimension ld), int64 targets [n], 1 <= C <= 1024 (more: SVOL_E_UNSUPPORTED): loss [1] = the mean over rows, dlogits [n, C] (lddl) =
  *   (softmax - onehot) / n, correct [1] = the number of rows whose argmax is their target.  The sum over rows has a fixed order (same

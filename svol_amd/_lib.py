@@ -100,6 +100,12 @@ SIGNATURES = {
     'svol_attn_cls_fwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _f32, _int, _p],
     'svol_attn_cls_bwd_h16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64,
                               _i64, _f32, _int, _p],
+    # many queries, few keys (csrc/attn_fewkeys.hip)
+    'svol_attn_fewkeys_chunk_rows': [_i64],
+    'svol_attn_fewkeys_ws_bytes': [_i64, _i64, _i64, _i64, _i64],
+    'svol_attn_fewkeys_fwd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _int, _p],
+    'svol_attn_fewkeys_bwd': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64,
+                              _i64, _i64, _i64, _i64, _i64, _f32, _f32, _p, _i64, _int, _p],
     'svol_softmax_xent': [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _p],
     'svol_posenc_sine': [_p, _p, _i64, _i64, _i64, _int, _p],
     'svol_attn_ws_bytes': [_i64, _i64, _i64, _i64, _i64],
@@ -185,6 +191,8 @@ def lib():
         L.svol_attn_ws_bytes.restype = _i64
         L.svol_attn_bwd_sp_image_bytes.restype = _i64
         L.svol_grad_sqnorm_ws_bytes.restype = _i64
+        L.svol_attn_fewkeys_chunk_rows.restype = _i64
+        L.svol_attn_fewkeys_ws_bytes.restype = _i64
         L.svol_block_slot_names.restype = ctypes.c_char_p
         L.svol_block_slot_names.argtypes = [_int]
         _LIB = L

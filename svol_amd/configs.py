@@ -140,6 +140,10 @@ _EXTRA = [
     (('--model_ema_decay',), dict(type=float, default=None,
                                   help='keep an exponential moving average of the weights with this decay inside the optimizer step '
                                        '(parallel.build_optimizer: ema_decay); default: none')),
+    (('--sketch_attn',), dict(type=str, default='gate', choices=['gate', 'tokens'],
+                              help="how the video meets the sketch in svanet: 'gate' = one sketch token gates the video tokens (the "
+                                   "reference's V1 lines); 'tokens' = every video token attends to the sketch's tokens (its V2 lines: "
+                                   "grid features, several sketches; --use_sketch_pos / --num_input_sketches apply)")),
     (('--lr_backbone',), dict(type=float, default=None,
                               help='learning rate of the trainable backbone parameters, in a param group of their own '
                                    '(parallel.reference_param_groups); default: --lr, one group')),

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import (ACT_GELU, ACT_NONE, ACT_RELU, _DT, _ptr, _stream, act_bwd, attn_bwd, attn_fwd, attn_weights_mean, cast, colsum,
                   dropout, dropout_add, gemm_nt, gemm_nt_dact, gemm_nt_split, layernorm_bwd, layernorm_fwd)
 from .params import SPLIT_V, GradGroup, claim, sink_view, unless_sunk, weights
@@ -235,8 +235,11 @@ class AttnLNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, self_attn,
-                need_weights=False, drop=None):
-        """drop = (p, seed_attention, seed_residual[, seed_dev]): training-mode dropout of the enc/dec attention blocks — on the attention
+                need_weights=False, drop=None, core=None):
+        """core = 'fewkeys' (cross configuration): the attention core runs on the many-queries / few-keys kernels
+        (ops.attn_fewkeys_fwd / _bwd) where ops.attn_fewkeys_ok takes the shape, ops.attn_fewkeys_faster says they were measured
+        faster and there is no dropout; otherwise, and always with core None, on attn_fwd / attn_bwd.  'fewkeys!' skips the speed rule.
+        drop = (p, seed_attention, seed_residual[, seed_dev]): training-mode dropout of the enc/dec attention blocks — on the attention
         probabilities (nn.MultiheadAttention(dropout=p)) and on the block output before the residual add (dropout1 / dropout2,
         transformer.py:158-177,216-247).  The returned attention weights stay those of the undropped softmax.  seed_dev: a device int64
         step counter (ops.attn_fwd), kept alive on ctx, not a differentiable input; backward regenerates the masks through the same
@@ -286,7 +289,16 @@ class AttnLNFn(torch.autograd.Function):
             gemm_nt_split(a_v, Wv_hilo, b_in[2 * d:], out=v)
         else:
             gemm_nt(a_v, Wc[2 * d:], b_in[2 * d:], out=v)
-        o, lse2 = attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul, drop=(drop[0], drop[1], _sd(drop)) if drop is not None else None)
+        if core not in (None, 'fewkeys', 'fewkeys!'):
+            raise _lib.SvolHipError(f'AttnLNFn: unknown attention core {core!r}')
+        # 'fewkeys': where the kernels take the shape AND were measured faster than attn_fwd / attn_bwd (ops.attn_fewkeys_faster);
+        # 'fewkeys!': wherever they take the shape (benchmarks, tests)
+        fewkeys = (core in ('fewkeys', 'fewkeys!') and not self_attn and drop is None and ops.attn_fewkeys_ok(dkv, Lk, dh)
+                   and (core == 'fewkeys!' or ops.attn_fewkeys_faster(Lk, dh)))
+        if fewkeys:
+            o, lse2 = ops.attn_fewkeys_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul)
+        else:
+            o, lse2 = attn_fwd(q, k, v, B, H, Lq, Lk, dh, kbias, premul, drop=(drop[0], drop[1], _sd(drop)) if drop is not None else None)
         att = attn_weights_mean(q, k, lse2, B, H, Lq, Lk, dh, kbias, premul) if need_weights else None
         if drop is not None:
             r32 = xq32.reshape(B * Lq, d)
@@ -295,7 +307,7 @@ class AttnLNFn(torch.autograd.Function):
         else:
             s32 = gemm_nt(cast(o, dt) if mixed else o, Woc, b_o, residual=xq32.reshape(B * Lq, d), out_f32=True)
         ctx.WcT, ctx.WoT, ctx.dims, ctx.self_attn, ctx.premul = WcT, WoT, (B, H, Lq, Lk, dh, d), self_attn, premul
-        ctx.mixed, ctx.Wq32T = mixed, Wq32T
+        ctx.mixed, ctx.Wq32T, ctx.fewkeys = mixed, Wq32T, fewkeys
         ctx.pos_shape = pos_out.shape if pos_out is not None else None
         ctx.has_ln = gamma is not None
         nig = ctx.needs_input_grad
@@ -354,7 +366,10 @@ class AttnLNFn(torch.autograd.Function):
             dq = torch.empty((B * Lq, d), dtype=q.dtype, device=g.device)
             dkv = torch.empty((B * Lk, 2 * d), dtype=k.dtype, device=g.device)
             dk, dv = dkv[:, :d], dkv[:, d:]
-            attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias, ctx.premul, drop=adrop)
+            if ctx.fewkeys:
+                ops.attn_fewkeys_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias, ctx.premul)
+            else:
+                attn_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias, ctx.premul, drop=adrop)
             if mixed:
                 dq = cast(dq, dt)
             grads.tn(dq, a_qp, W_IN, B_IN, slice(0, d))
@@ -366,7 +381,7 @@ class AttnLNFn(torch.autograd.Function):
             shk = (B, Lk, d)
             dx = (None, dxq_pos.view(shq), dxk_pos.view(shk), dxv.view(shk))
         n_ = unless_sunk
-        return (ds32.view(shq),) + dx + grads.finish() + (n_(sbo, dbo), n_(sg, dg), n_(sbt, dbt), dpos, None, None, None, None, None)
+        return (ds32.view(shq),) + dx + grads.finish() + (n_(sbo, dbo), n_(sg, dg), n_(sbt, dbt), dpos, None, None, None, None, None, None)
 
 
 class LNStreamFn(torch.autograd.Function):
@@ -429,9 +444,12 @@ def self_attn_ln(x32, x, x_pos, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, k
 
 
 def cross_attn_ln(xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias,
-                  need_weights=False, drop=None):
+                  need_weights=False, drop=None, core=None):
+    if core is None:   # (exactly the call it always was)
+        return AttnLNFn.apply(xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, False,
+                              need_weights, drop)
     return AttnLNFn.apply(xq32, xq, xq_pos, xk_pos, xv, W_in, b_in, W_o, b_o, gamma, beta, pos_out, H, kbias, False,
-                          need_weights, drop)
+                          need_weights, drop, core)
 
 
 def ln_stream(x32, gamma, beta, pos, dtype, want32=False):

@@ -394,8 +394,9 @@ class ViTBackbone(nn.Module):
     the path they always took."""
 
     def __init__(self, video_backbone: ViTExtractor, sketch_backbone: ViTExtractor, use_sketch_cls_token: bool = True,
-                 frames_per_launch: int = 512, pixel_preset=None, sketch_filter=None, sketch_invert=False):
+                 frames_per_launch: int = 512, pixel_preset=None, sketch_filter=None, sketch_invert=False, sketch_tokens='pooled'):
         super().__init__()
+        self.sketch_tokens = sketch_tokens   # 'grid': all 197 tokens of every sketch go to the head (--sketch_attn tokens)
         s = video_backbone.cfg.image_size
         self.ingest = FrameIngest((s, s), pixel_preset or 'vit', out='nchw_f32')
         self.sketch_ingest = self.ingest
@@ -417,7 +418,8 @@ class ViTBackbone(nn.Module):
                 src_video = self.ingest(src_video)
                 src_video = src_video.view(B, -1, *src_video.shape[-3:])
             sk = self.sketch_backbone(src_sketch.reshape(-1, *src_sketch.shape[2:]))
-            sk = sk[:, :1] if self.use_sketch_cls_token else sk[:, 1:].mean(1, keepdim=True)  # backbone.py:35-38
+            if self.sketch_tokens != 'grid':
+                sk = sk[:, :1] if self.use_sketch_cls_token else sk[:, 1:].mean(1, keepdim=True)  # backbone.py:35-38
             frames = src_video.reshape(-1, *src_video.shape[2:])
             outs = [self.video_backbone(frames[i:i + self.frames_per_launch])[:, 1:]
                     for i in range(0, frames.shape[0], self.frames_per_launch)]

@@ -177,9 +177,21 @@ def all_gate_vectors(layers, skch):
     return list(_GateVectorsAllFn.apply(skch, layers[0].nhead, *params))
 
 
+SKETCH_ATTN = ('gate', 'tokens')
+# the attention core of the tokens-mode video -> sketch attention: 'fewkeys' (csrc/attn_fewkeys.hip where its limits take the shape and
+# it was measured faster, ops.attn_fewkeys_faster), 'fewkeys!' (wherever its limits take the shape) or None (svol_attn_fwd / _bwd
+# always); tools/bench_sketch_tokens.py forces each family in turn
+TOKENS_CORE = 'fewkeys'
+
+
 class CrossModalTransformerLayer(nn.Module):
-    def __init__(self, d_model=512, nhead=8, dim_feedforward=D_FF):
+    def __init__(self, d_model=512, nhead=8, dim_feedforward=D_FF, sketch_attn='gate'):
+        """sketch_attn 'gate': the reference's "V1 (1x1)" lines (:121-127), one sketch token gating the video tokens; 'tokens': its
+        "V2 (7x7)" lines (:129-135), every video token attending to the sketch's tokens.  Same parameters in both modes."""
         super().__init__()
+        if sketch_attn not in SKETCH_ATTN:
+            raise ValueError(f'sketch_attn must be one of {SKETCH_ATTN}, not {sketch_attn!r}')
+        self.sketch_attn = sketch_attn
         self.sketch_video_cross_attn = nn.MultiheadAttention(d_model, nhead)
         self.norm1 = nn.LayerNorm(d_model)
         self.content_self_attn = nn.MultiheadAttention(d_model, nhead)
@@ -224,6 +236,22 @@ class CrossModalTransformerLayer(nn.Module):
         m32, m = layers.self_attn_ln(m32, m, mpos, *mha(self.content_self_attn), *n(self.norm2), None, h)
         return layers.mlp_ln(m32, m, *mlp(self.mlp1), *n(self.norm3), pos)
 
+    def video_half_tokens(self, mem, pos, sketch):
+        """the video half with the "V2 (7x7)" lines (:129-135) in place of the gate: mem = norm1(src_vid + MHA(q = src_vid + vid_pos,
+        k = src_skch + skch_pos, v = src_skch)), padded sketch tokens masked; then :137-143 as they are.  mem = the stream triple
+        (fp32, compute-dtype copy, copy + pos); sketch = (sk, sk_pos, sk_kbias): [B,Ls,d] compute dtype twice and [B,Ls] fp32 0 / -inf.
+        Per-op path: the block program svol_video_half_* contains the gate."""
+        h = self.nhead
+        n = lambda m: (m.weight, m.bias)
+        mha = lambda m: (m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias)
+        mlp = lambda m: (m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias)
+        mem32, m, mpos = mem
+        sk, sk_pos, sk_kbias = sketch
+        m32, m, mpos = layers.cross_attn_ln(mem32, m, mpos, sk_pos, sk, *mha(self.sketch_video_cross_attn), *n(self.norm1), pos, h, sk_kbias,
+                                            core=TOKENS_CORE)
+        m32, m = layers.self_attn_ln(m32, m, mpos, *mha(self.content_self_attn), *n(self.norm2), None, h)
+        return layers.mlp_ln(m32, m, *mlp(self.mlp1), *n(self.norm3), pos)
+
     def query_half(self, out, m, mpos, qpos, kbias):
         """the "decoder-like" half, :145-158: object queries attend to themselves, then to the video tokens."""
         return self.query_cross(self.query_self(out, qpos, m.dtype), m, mpos, qpos, kbias)
@@ -252,9 +280,10 @@ class CrossModalTransformerLayer(nn.Module):
 
 
 class CrossModalTransformer(nn.Module):
-    def __init__(self, d_model=512, nhead=8, num_layers=6, dim_feedforward=D_FF):
+    def __init__(self, d_model=512, nhead=8, num_layers=6, dim_feedforward=D_FF, sketch_attn='gate'):
         super().__init__()
-        layer = CrossModalTransformerLayer(d_model, nhead, dim_feedforward)
+        self.sketch_attn = sketch_attn
+        layer = CrossModalTransformerLayer(d_model, nhead, dim_feedforward, sketch_attn)
         self.layers = nn.ModuleList([copy.deepcopy(layer) for _ in range(num_layers)])
         for p in self.parameters():  # reference _reset_parameters, :22-25
             if p.dim() > 1:
@@ -262,8 +291,10 @@ class CrossModalTransformer(nn.Module):
         self.d_model, self.nhead, self.num_layers = d_model, nhead, num_layers
         self._epoch_seen = -1
 
-    def forward(self, src_vid32, src_skch32, kbias, vid_pos, query_embed, us=None):
-        """src_vid32 [B,L,d] fp32 (projected video tokens = start of the fp32 residual stream),
+    def forward(self, src_vid32, src_skch32, kbias, vid_pos, query_embed, us=None, sketch=None):
+        """sketch_attn 'tokens': sketch = (sk [B,Ls,d], sk_pos [B,Ls,d], sk_kbias [B,Ls] fp32 0 / -inf) in the compute dtype replaces
+        src_skch32 and us (pass None).
+        src_vid32 [B,L,d] fp32 (projected video tokens = start of the fp32 residual stream),
         src_skch32 [B,d] fp32, kbias [B,L] fp32 additive key mask, vid_pos [B,L,d] compute dtype,
         query_embed [N,d] fp32 parameter; us: every layer's gate vectors when the caller computed them (all_gate_vectors; SVANet does,
         on the query stream beside the video projection).  Returns hs [num_layers,B,N,d] fp32."""
@@ -289,12 +320,23 @@ class CrossModalTransformer(nn.Module):
         # waits for a CU beside the other streams' kernels (15 us each).  Their autograd nodes get the lowest sequence numbers of the
         # transformer, so the engine runs their backward (two tiny launches per layer, 65 us each in the middle of the backward)
         # after everything else: 6 x 14 us at the end.  (svol_amd.parallel.arrival_order puts these parameters last accordingly.)
-        if us is None:
+        tokens = self.sketch_attn == 'tokens'
+        if tokens:   # no gate vectors; layer 0's stream triple from the projected video
+            if sketch is None:
+                raise _lib.SvolHipError("CrossModalTransformer(sketch_attn='tokens') needs sketch = (sk, sk_pos, sk_kbias)")
+            dt_v = vid_pos.dtype   # (x + pos is formed in fp32 and rounded once, as the LayerNorms that emit the later triples do)
+            mem = (src_vid32, layers.cast_ag(src_vid32, dt_v), layers.cast_ag(src_vid32 + vid_pos.float(), dt_v))
+            us = [None] * len(self.layers)
+        elif us is None:
             us = all_gate_vectors(list(self.layers), src_skch32)
         if not OVERLAP_QUERY_STREAM:
             out = initial_queries()
             for layer, u in zip(self.layers, us):
-                mem32, out = layer(mem32, src_skch32, out, vid_pos, qpos, kbias, u)
+                if tokens:
+                    mem = layer.video_half_tokens(mem, vid_pos, sketch)
+                    out = layer.query_half(out, mem[1], mem[2], qpos, kbias)
+                else:
+                    mem32, out = layer(mem32, src_skch32, out, vid_pos, qpos, kbias, u)
                 outputs.append(out[0])
             return torch.stack(outputs)
         # The query half of layer i (N = 100 object queries: skinny GEMMs, 64-512 workgroup attention launches, small
@@ -322,7 +364,9 @@ class CrossModalTransformer(nn.Module):
             # by that block)
             with torch.cuda.stream(side):
                 out_sa = layer.query_self(out, qpos, vid_pos.dtype)
-            if blocks.ENABLED and blocks.GATE_SCORES_FUSE and li + 1 < len(us):
+            if tokens:
+                m32, m, mpos = mem = layer.video_half_tokens(mem, vid_pos, sketch)
+            elif blocks.ENABLED and blocks.GATE_SCORES_FUSE and li + 1 < len(us):
                 m32, m, mpos, sc = layer.video_half(mem32, src_skch32, vid_pos, u, us[li + 1], sc)
             elif sc is not None:
                 m32, m, mpos = layer.video_half(mem32, src_skch32, vid_pos, u, None, sc)
@@ -343,4 +387,4 @@ class CrossModalTransformer(nn.Module):
 
 def build_cross_modal_transformer(args):
     return CrossModalTransformer(d_model=args.hidden_dim, nhead=args.nheads, num_layers=args.num_layers,
-                                 dim_feedforward=D_FF)
+                                 dim_feedforward=D_FF, sketch_attn=getattr(args, 'sketch_attn', 'gate'))

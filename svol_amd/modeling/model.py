@@ -37,6 +37,19 @@ class FeatureBackbone(nn.Module):
         return src_sketch, src_video
 
 
+SKETCH_TOKENS = ('pooled', 'grid')
+
+
+def _sketch_tokens(args):
+    """``args.sketch_tokens`` (set on the args object like pixel_preset, no command-line flag): 'pooled' = one token per sketch, what the
+    reference's extractors hand over; 'grid' = every token of the sketch extractor, 7 x 7 = 49 of a ResNet (no average pooling), 197 of
+    the ViT ([CLS] and the patches), for ``--sketch_attn tokens``."""
+    st = getattr(args, 'sketch_tokens', None) or 'pooled'
+    if st not in SKETCH_TOKENS:
+        raise ValueError(f'args.sketch_tokens must be one of {SKETCH_TOKENS}, not {st!r}')
+    return st
+
+
 def _resnet_backbone(args, video_net, sketch_net, width, sk):
     """the ResNet pair of either depth: sets both input widths, reads --train_backbone / --freeze_backbone / --sync_bn / --compute_dtype"""
     from .resnet import ResNetBackbone
@@ -53,7 +66,7 @@ def _resnet_backbone(args, video_net, sketch_net, width, sk):
     tb = (not bool(getattr(args, 'freeze_backbone', False))) if tb is None else bool(tb)
     sync = bool(getattr(args, 'sync_bn', False))   # train.py:65-68: apex convert_syncbn_model
     return ResNetBackbone(video_net(compute_dtype=cd, trainable=tb, sync_bn=sync),
-                          sketch_net(avgpool=True, compute_dtype=cd, trainable=tb, sync_bn=sync),
+                          sketch_net(avgpool=_sketch_tokens(args) == 'pooled', compute_dtype=cd, trainable=tb, sync_bn=sync),
                           pixel_preset=getattr(args, 'pixel_preset', None), **sk)
 
 
@@ -79,7 +92,7 @@ def build_backbone(args):
         cd = 'fp16' if getattr(args, 'compute_dtype', 'bf16') == 'fp16' else 'bf16'   # (module docstring)
         return ViTBackbone(ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
                            ViTExtractor(vit_base_config(), compute_dtype=cd, trainable=tb, train_layers=tl),
-                           pixel_preset=getattr(args, 'pixel_preset', None), **sk)
+                           pixel_preset=getattr(args, 'pixel_preset', None), sketch_tokens=_sketch_tokens(args), **sk)
     if args.backbone == 'resnet50':  # backbone.py:143-147: ResNet-50 on the frames and, average-pooled, on the sketch; 2048-wide features
         from .resnet import resnet50
         return _resnet_backbone(args, resnet50, resnet50, 2048, sk)
@@ -100,7 +113,8 @@ class SketchLocalizationModel(nn.Module):
         T = src_video[0].shape[0] if isinstance(src_video, (list, tuple)) else src_video.shape[1]
         src_sketch, src_video = self.backbone(src_sketch, src_video)
         # per-token masks: one sketch-mask entry per sketch token, one frame-mask entry per patch (model.py:21-22)
-        src_sketch_mask = src_sketch_mask.repeat_interleave(src_sketch.shape[1], dim=1)
+        # (n sketches, --num_input_sketches: a [B, n] mask over n * tokens sketch tokens; with one column the factor is what it always was)
+        src_sketch_mask = src_sketch_mask.repeat_interleave(src_sketch.shape[1] // src_sketch_mask.shape[1], dim=1)
         src_video_mask = src_video_mask.repeat_interleave(src_video.shape[1] // T, dim=1)
         return self.head(src_sketch, src_sketch_mask, src_video, src_video_mask)
 

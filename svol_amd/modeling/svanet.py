@@ -117,15 +117,30 @@ class SVANet(nn.Module):
             params.weights.new_epoch()  # re-cast every fp32 master weight once per forward (see params._WeightCache)
         if self.training:
             self._step += 1
+        # video tokens attending to the sketch's tokens ("V2 (7x7)", CrossModalTransformer(sketch_attn='tokens')) instead of the gate
+        tokens = getattr(self.transformer, 'sketch_attn', 'gate') == 'tokens'
         def mask_side(with_us):
             """what depends on the masks and the sketch only: position encoding, key bias, sketch projection, every layer's gate
             vectors (B*d-sized algebra; their backward is 2 launches per step that used to close the backward on the main stream)"""
             mask_f = src_video_mask.to(torch.float32)
             pos_video = self.video_position_embed(mask_f, d, dt)
-            skch = self._proj(self.input_sketch_proj, layers.cast_ag(src_sketch.float(), dt), 1)
-            skch = skch.reshape(skch.shape[0], -1)
             # key_padding_mask (True on pads) as an additive bias for the cross-attention kernel
             kbias = torch.zeros_like(mask_f).masked_fill_(mask_f == 0, float('-inf'))
+            if tokens:
+                # the sketch stays [B, Ls, d]: its compute-dtype copy (the values), the copy plus its positions (the keys) and the
+                # padded tokens as a key bias.  A padded token's features are replaced by zeros before the projection: whatever
+                # they hold (NaN included) reaches nothing.
+                smask = src_sketch_mask.to(torch.bool)
+                smask_f = smask.to(torch.float32)
+                x = src_sketch.float().masked_fill(~smask.unsqueeze(-1), 0.0)
+                sk32 = self._proj(self.input_sketch_proj, layers.cast_ag(x, dt), 1)
+                sk = layers.cast_ag(sk32, dt)
+                # (the sum is formed in fp32 and rounded once)
+                sk_pos = layers.cast_ag(sk32 + self.sketch_position_embed(smask_f, d, torch.float32), dt) if self.use_sketch_pos else sk
+                sk_kbias = torch.zeros_like(smask_f).masked_fill_(~smask, float('-inf'))
+                return pos_video, (sk, sk_pos, sk_kbias), kbias, None
+            skch = self._proj(self.input_sketch_proj, layers.cast_ag(src_sketch.float(), dt), 1)
+            skch = skch.reshape(skch.shape[0], -1)
             us = cmt.all_gate_vectors(list(self.transformer.layers), skch) if with_us else None
             return pos_video, skch, kbias, us
 
@@ -146,13 +161,16 @@ class SVANet(nn.Module):
             main.wait_event(casts_done)
             vid = self._proj(self.input_video_proj, xv, 0)
             main.wait_stream(side)
-            for t in [pos_video, skch, kbias] + list(us or []):
+            for t in [pos_video, kbias] + (list(skch) if tokens else [skch]) + list(us or []):
                 t.record_stream(main)   # allocated on the query stream, read by the video half on this one
         else:
             vid = self._proj(self.input_video_proj, layers.cast_ag(src_video.float(), dt), 0)
             pos_video, skch, kbias, us = mask_side(False)
-        hs = (self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight, us) if us is not None else
-              self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight))   # [NL,B,N,d] fp32
+        if tokens:
+            hs = self.transformer(vid, None, kbias, pos_video, self.query_embed.weight, sketch=skch)
+        else:
+            hs = (self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight, us) if us is not None else
+                  self.transformer(vid, skch, kbias, pos_video, self.query_embed.weight))   # [NL,B,N,d] fp32
         # heads run in fp32 (tiny; keeps logits / box coordinates at full precision)
         if layers.heads_fusable(hs, self.class_embed, self.bbox_embed):   # both heads, all layers, one launch (csrc/heads.hip)
             outputs_class, outputs_coord = layers.heads(hs, self.class_embed, self.bbox_embed)

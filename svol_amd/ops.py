@@ -435,6 +435,65 @@ def attn_cls_bwd(q, k, v, o, do, lse2, n, H, L, dh, dq, dk, dv):
                name)
 
 
+FEWKEYS_LMAX = 256   # keys of the many-queries / few-keys attention kernels (csrc/attn_fewkeys.hip)
+
+
+def attn_fewkeys_ok(dtype, Lk, dh) -> bool:
+    """whether svol_attn_fewkeys_fwd / _bwd take the shape: bf16 or fp16 operands, dh in {32, 64}, 1 <= Lk <= 256 (any Lq)"""
+    return dtype in (torch.bfloat16, torch.float16) and dh in (32, 64) and 1 <= Lk <= FEWKEYS_LMAX
+
+
+FEWKEYS_FASTER_LK32 = 197   # dh = 32: the largest key count at which the few-keys pair was measured faster than attn_fwd / attn_bwd
+
+
+def attn_fewkeys_faster(Lk, dh) -> bool:
+    """where the few-keys kernels were measured faster than the generic ones by more than the run-to-run spread
+    (profiles/sketch_tokens.md: B = 8, H = 8, bf16 and fp16).  dh = 32: Lk = 49 (2.1 x backward, 1.6 x forward) and 197 (1.14 x /
+    1.15 x), the margin shrinking with Lk, so key counts above 197 — not measured; at 256 the tuned 128-key kernels serve the generic
+    path — stay on the generic kernels.  dh = 64: Lk = 98, 5 x backward and 1.3 x forward against the two-pass kernels that serve
+    every key count at that width, so every Lk <= 256."""
+    return dh == 64 or Lk <= FEWKEYS_FASTER_LK32
+
+
+def attn_fewkeys_chunk(Lq: int) -> int:
+    """queries a workgroup of the few-keys kernels walks: a function of Lq alone (256 * ceil(Lq / 2048): at most 8 chunks per
+    (batch, head)); the backward's dK / dV partials are per chunk and are added in chunk order"""
+    return int(_lib.lib().svol_attn_fewkeys_chunk_rows(int(Lq)))
+
+
+def attn_fewkeys_ws_bytes(B, H, Lq, Lk, dh) -> int:
+    return int(_lib.lib().svol_attn_fewkeys_ws_bytes(B, H, Lq, Lk, dh))
+
+
+def attn_fewkeys_fwd(q, k, v, B, H, Lq, Lk, dh, kbias=None, premul=0.0):
+    """attn_fwd's contract on the few-keys kernels (Lk <= 256, many queries): q/k/v 2-D [B*L, >= H*dh] views (column slices allowed)
+    -> (o [B*Lq, H*dh], lse2 [B, H, Lq] fp32, log2 domain).  A shape outside attn_fewkeys_ok raises: the caller chooses the family."""
+    o = torch.empty((B * Lq, H * dh), dtype=q.dtype, device=q.device)
+    lse2 = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    wgrad.attn_forward(B * H * Lq * Lk)
+    tok = timer.start('attn_fewkeys_fwd', (B, H, Lq, Lk, dh))
+    rc = _lib.lib().svol_attn_fewkeys_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(lse2),
+                                          _ptr(kbias), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _dt(q), _stream())
+    timer.stop(tok)
+    _lib.check(rc, 'svol_attn_fewkeys_fwd')
+    return o, lse2
+
+
+def attn_fewkeys_bwd(q, k, v, o, do, lse2, B, H, Lq, Lk, dh, dq, dk, dv, kbias=None, premul=0.0):
+    """gradients of attn_fewkeys_fwd into dq / dk / dv (2-D views, column slices allowed).  The fp32 scratch of the per-chunk dK / dV
+    partials is a torch allocation; the sums have a fixed order (same bits every run)."""
+    do = do if do.stride(1) == 1 else do.contiguous()
+    wgrad.attn_backward(B * H * Lq * Lk)
+    n = attn_fewkeys_ws_bytes(B, H, Lq, Lk, dh)
+    ws = torch.empty((max(n, 4) // 4,), dtype=torch.float32, device=q.device)
+    tok = timer.start('attn_fewkeys_bwd', (B, H, Lq, Lk, dh))
+    rc = _lib.lib().svol_attn_fewkeys_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0), _ptr(do),
+                                          do.stride(0), _ptr(lse2), _ptr(kbias), _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv),
+                                          dv.stride(0), B, H, Lq, Lk, dh, 1.0 / math.sqrt(dh), float(premul), _ptr(ws), n, _dt(q), _stream())
+    timer.stop(tok)
+    _lib.check(rc, 'svol_attn_fewkeys_bwd')
+
+
 def softmax_xent(logits, targets):
     """nn.CrossEntropyLoss() of fp32 logits [n, C] (a row-strided view is fine) and int64 targets [n] -> (loss [1] fp32 = the mean over
     rows, dlogits [n, C] = (softmax - onehot) / n, correct [1] int32 = top-1 hits).  C <= 1024."""

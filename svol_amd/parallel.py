@@ -1143,9 +1143,11 @@ def unused_parameters(model: torch.nn.Module):
     dead = {'concat_to_seq': ('input_sketch_proj', 'input_video_proj', 'input_query_proj'),
             'append_to_seq': ('input_proj.', 'input_query_proj'),
             'concat_to_qry': ('input_proj.', 'input_sketch_proj')}.get(mode, ())
+    # sketch_attn 'tokens' (video tokens attending to the sketch's tokens): that MHA's value and output projections are used and train
+    tokens = any(getattr(m, 'sketch_attn', None) == 'tokens' for m in model.modules())
     out = []
     for name, p in model.named_parameters():
-        if 'sketch_video_cross_attn.out_proj' in name or 'class_head' in name or any(d in name for d in dead):
+        if ('sketch_video_cross_attn.out_proj' in name and not tokens) or 'class_head' in name or any(d in name for d in dead):
             out.append(p)
     return out
 
