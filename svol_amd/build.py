@@ -44,7 +44,7 @@ def _stale(target: str, deps) -> bool:
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attn_call.h'), os.path.join(CSRC, 'gemm_call.h'), os.path.join(os.path.dirname(HERE), 'include', 'svol_hip.h')]
+    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attn_call.h'), os.path.join(CSRC, 'gemm_call.h'), os.path.join(CSRC, 'ln_row.h'), os.path.join(os.path.dirname(HERE), 'include', 'svol_hip.h')]
     objdir = os.path.join(CSRC, 'build')
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()

@@ -6,9 +6,11 @@
 // u[b,h,:] = d_h^-1/2 * W_k,h^T q[b,h,:] (the k-bias adds a per-(b,h) constant that cancels in the
 // softmax), so the [L,d]x[d,d] K projection, the V projection, P.V and out_proj of the reference are
 // never computed.  Forward = 3 passes over x (scores, per-(b,h) max/sum, apply+LN1); backward = 3.
+// The LayerNorm of the apply pass and of the fused-score kernel is the shared row of ln_row.h (LnFwdRow, with its pre-scale and
+// y + pos hooks); the du fold of the backward apply pass is its ln_fold_columns.  gate_bwd_ln_kernel keeps its own LN1 backward text.
 #include <cstdlib>
 
-#include "common.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256) void gate_stats_kernel(const float* __restrict
     }
 }
 
-// a[b,l] = mean_h softmax ; s1 = x*(1+a) ; y = LN(s1) ; ypos = y + pos        one wave per row
+// a[b,l] = mean_h softmax ; s1 = x*(1+a) ; y = LN(s1) ; ypos = y + pos        one wave per row (the LN: ln_row.h, WPR = 1)
 // WIDE (GH < H <= GHMAX): lane h holds head h's score and statistics, as in gate_bwd_ln_kernel, and the mean is a wave sum
 template <typename T, int NP, bool WIDE = false>
 __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict__ x, const T* __restrict__ pos,
@@ -157,8 +159,7 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict
     const int b = (int)(row / L), l = (int)(row % L);
     // every global load of the wave's one row goes out before anything is reduced (scores, x, pos, gamma, beta): one memory
     // latency per wave instead of three (41 -> 3x us per [50176, 256] launch)
-    Vec4<float> t[NP], gv[NP], bv[NP];
-    Vec4<T> pv[NP];
+    LnFwdRow<T, NP> ln;
     float sc[GH], mxv[GH], smv[GH];
     if constexpr (WIDE) {
         const int bh = b * H + (lane < H ? lane : 0);
@@ -174,16 +175,7 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict
         smv[hh] = sm[bh];
     }
     }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < D) {
-            t[j].load(x + row * D + c);
-            pv[j].load(pos + row * D + c);
-            gv[j].load(gamma + c);
-            bv[j].load(beta + c);
-        }
-    }
+    ln.load(x, pos, row, gamma, beta, D);
     float a = 0.f;
     if constexpr (WIDE) {
         a = wave_sum(lane < H ? __expf(sc[0] - mxv[0]) / smv[0] : 0.f);
@@ -193,54 +185,17 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float* __restrict
         if (hh < H) a += __expf(sc[hh] - mxv[hh]) / smv[hh];
     }
     a /= (float)H;
-    float v[NP][4];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[j][e] = c < D ? t[j].get(e) * (1.f + a) : 0.f;
-            s += v[j][e];
-        }
-    }
-    const float mu = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < D) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mu; q += d * d; }
-        }
-    }
-    const float rs = rsqrtf(wave_sum(q) / (float)D + 1e-5f);
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; a_out[row] = a; }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < D) {
-            Vec4<T> o, op;
-            Vec4<float> o32;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float r = (v[j][e] - mu) * rs * gv[j].get(e) + bv[j].get(e);
-                o.set(e, r);
-                o32.set(e, r);
-                op.set(e, r + pv[j].get(e));
-            }
-            if (y32) o32.store(y32 + row * D + c);
-            if (y) o.store(y + row * D + c);
-            if (ypos) op.store(ypos + row * D + c);
-        }
-    }
+    ln.stats(1.f + a, D);   // the pre-scale hook: LN1 of x * (1 + a)
+    if (lane == 0) { mean[row] = ln.mu; rstd[row] = ln.rs; a_out[row] = a; }
+    ln.store(row, y32, y, ypos, D, nullptr);
 }
 
 // LN3 of layer i with the gate scores of layer i + 1 as its epilogue: the row this wave has just normalised IS
 // the next layer's x, pos is already in registers for the + pos output, and every layer's gate vectors exist before the layer loop
 // (cross_modal_transformer.py: all_gate_vectors) — so the next layer's score pass (one more read of x32 + pos: 77 MB, 33 us at cfg2)
-// is 32 FMAs per lane here.  One row per wave as in ln_fwd_kernel (norm.hip: same arithmetic, same order -> the same bits), the four
-// rows of a workgroup belong to one batch element (launcher: L % 4 == 0) whose u[b] is staged in LDS once per workgroup; the
+// is 32 FMAs per lane here.  One row per wave; the LayerNorm is LnFwdRow (ln_row.h), which rounds as ln_fwd_kernel<T, float, 1> (norm.hip)
+// does: same arithmetic, same order -> the same bits (tests/gpu_checks.py::check_gate_scores_fused asserts zero differing elements).
+// The four rows of a workgroup belong to one batch element (launcher: L % 4 == 0) whose u[b] is staged in LDS once per workgroup; the
 // products and the head butterfly are gate_scores_kernel's, so the scores carry the same bits as the stand-alone pass too.
 template <typename T, int NP>
 __global__ __launch_bounds__(256) void ln_scores_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -262,65 +217,16 @@ __global__ __launch_bounds__(256) void ln_scores_kernel(const float* __restrict_
             *reinterpret_cast<f32x4*>(su + i) = w;
         }
     }
-    const float* xr = x + row * D;
-    const T* pr = pos + row * D;
-    Vec4<float> t[NP], gv[NP], bv[NP];
-    Vec4<T> pv[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < D) {
-            t[j].load(xr + c);
-            pv[j].load(pr + c);
-            gv[j].load(gamma + c);
-            bv[j].load(beta + c);
-        }
-    }
-    float v[NP][4];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[j][e] = c < D ? t[j].get(e) : 0.f;
-            s += v[j][e];
-        }
-    }
-    const float mu = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < D) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mu; q += d * d; }
-        }
-    }
-    const float rs = rsqrtf(wave_sum(q) / (float)D + 1e-5f);
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+    LnFwdRow<T, NP> ln;
+    ln.load(x, pos, row, gamma, beta, D);
+    ln.stats(1.f, D);
+    if (lane == 0) { mean[row] = ln.mu; rstd[row] = ln.rs; }
     float tp[NP][4];   // (y + pos) in fp32: what gate_scores_kernel forms from the stored fp32 row and pos
 #pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
+    for (int j = 0; j < NP; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) tp[j][e] = 0.f;
-        if (c < D) {
-            Vec4<T> o, op;
-            Vec4<float> o32;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float r = (v[j][e] - mu) * rs * gv[j].get(e) + bv[j].get(e);
-                o.set(e, r);
-                o32.set(e, r);
-                op.set(e, r + pv[j].get(e));
-                tp[j][e] = r + pv[j].get(e);
-            }
-            if (y32) o32.store(y32 + row * D + c);
-            if (y) o.store(y + row * D + c);
-            if (ypos) op.store(ypos + row * D + c);
-        }
-    }
+    ln.store(row, y32, y, ypos, D, tp);
     __syncthreads();
     float part[GH];
 #pragma unroll
@@ -342,7 +248,9 @@ __global__ __launch_bounds__(256) void ln_scores_kernel(const float* __restrict_
     store_head_sums(part, scores, b, l, L, H, lane);
 }
 
-// backward pass 1: LN1 backward, dx_part = ds1*(1+a), da[row] = sum_d ds1*x ; dgamma/dbeta atomics.
+// backward pass 1 (kept on its own text, not on ln_row.h: its multi-pass instances fuse some products of the row sums into the sums and
+// round others, element by element, as the compiler happened to pack them; no shared body reproduces that, profiles/ln_row.md):
+// LN1 backward, dx_part = ds1*(1+a), da[row] = sum_d ds1*x ; dgamma/dbeta atomics.
 // NP = 16-byte column groups per lane (D <= 256 * NP): the row loop is latency-bound (one dependent load -> reduce -> store chain
 // per wave), so the NEXT row's four operand vectors are fetched before the current row is reduced, and the register arrays are sized
 // for the real width (the untemplated version carried four groups whatever D was: twice the registers, half the waves per SIMD).
@@ -574,24 +482,7 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_kernel(const float* __rest
         dar = ndar;
     }
     // du: fold the workgroup's four waves in LDS first (every wave of a batch element hits the same H*D addresses)
-    __shared__ float red[GH * NP * 256];
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int hh = 0; hh < GH; ++hh)
-#pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    const int c = (lane + 64 * j) * 4;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float* r = red + hh * NP * 256 + c + e;
-                        if (w == 0) *r = dur[hh][j][e];
-                        else *r += dur[hh][j][e];
-                    }
-                }
-        }
-        __syncthreads();
-    }
+    const float* red = ln_fold_columns<1>(dur, D);
     for (int i = threadIdx.x; i < GH * NP * 256; i += 256) {
         const int hh = i / (NP * 256), c = i % (NP * 256);
         if (h0 + hh < H && c < D) {

@@ -1,13 +1,20 @@
 // LayerNorm (+dropout, +positional add) and sine positional encoding — HBM-bound row kernels.
-// One wave (64 lanes) per row, 4 contiguous elements per lane per pass (8 B bf16 / 16 B f32
-// coalesced loads), fp32 statistics, wave shuffle reductions (no LDS).  Rows wider than 1024 columns (up to 4096): one
-// workgroup of four waves per row, the row sums exchanged through LDS (lnw_fwd_kernel / lnw_bwd_kernel).
-#include "common.h"
+// The backward row (prefetched operands, reduce, dx, column sums and their fold) lives in ln_row.h: ln_bwd_kernel is its plain user at
+// WPR = 1 and WPR = 4.  The forward kernels keep their own text.  One wave (64 lanes) per row, 4 contiguous elements per lane per pass (8 B bf16 / 16 B f32 coalesced loads), fp32
+// statistics, wave shuffle reductions (no LDS): WPR = 1.  Rows wider than 1024 columns (up to 4096): one workgroup of four waves per
+// row, the row sums exchanged through LDS: lnw_fwd_kernel, and the WPR = 4 instances of ln_bwd_kernel.
+#include "ln_row.h"
 
 namespace {
 
-constexpr int LN_MAX_PASSES = 4;  // one wave per row: D <= 4 * 64 * 4 = 1024; wider rows (to LNW_MAX_D) take the lnw_* kernels below
+constexpr int LN_MAX_PASSES = 4;  // one wave per row: D <= 4 * 64 * 4 = 1024; wider rows (to LNW_MAX_D) take the WPR = 4 instances
+// wide rows: 1024 < D <= 4096 (pre-extracted 2048-d features, ResNet-50 tokens, concat_to_seq on ViT features), NP = passes of 1024
+// columns: 2, 3 or 4 — at most 16 columns per lane per array
+constexpr int LNW_MAX_D = 4096;
 
+// The two forward kernels keep their own text (they are not built on LnFwdRow of ln_row.h): their multi-pass instances carry roundings
+// that no shared body reproduces — which of the first two squares of the variance sum is rounded before the fused chain starts is the
+// compiler's pick per instantiation (profiles/ln_row.md) — and svol_layernorm_fwd's outputs stay the parent's to the bit.
 // T  = element type of the compute-dtype outputs / gradients, TX = element type of the LN input
 // (float when the input is the fp32 residual stream).
 template <typename T, typename TX, int NP>
@@ -82,132 +89,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, c
     }
 }
 
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = (dy32 + dy + dypos) * gamma (dropout mask applied first)
-template <typename T, typename TX, int NP>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy32, const T* __restrict__ dy,
-                                                     const T* __restrict__ dy2, const TX* __restrict__ x,
-                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                     const float* __restrict__ rstd, float* __restrict__ dx32,
-                                                     T* __restrict__ dx, float* __restrict__ dgamma,
-                                                     float* __restrict__ dbeta, float* __restrict__ dxsum, int64_t M, int D,
-                                                     float p, float inv_keep, uint64_t seed0, const int64_t* __restrict__ soff, int rows_per_wave,
-                                                     float* __restrict__ det_part) {
-    const uint64_t seed = seed0 + (soff ? ((uint64_t)soff[0] << 8) : 0ull);
-    const int lane = threadIdx.x & 63;
-    const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t r0 = wave_id * rows_per_wave;
-    float dg[NP][4], db[NP][4], dxs[NP][4], gm[NP][4];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int c = (lane + 64 * j) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { dg[j][e] = 0.f; db[j][e] = 0.f; dxs[j][e] = 0.f; gm[j][e] = c < D ? gamma[c + e] : 0.f; }
-    }
-    // The row loop is a dependent load -> reduce -> store chain per wave: the NEXT row's operand vectors and statistics are
-    // fetched before the current row is reduced (round 2: 58 -> 4x us per [50176, 256] launch)
-    struct Row { Vec4<float> a32[NP]; Vec4<T> a[NP], b[NP]; Vec4<TX> xv[NP]; float mu, rs; };
-    auto fetch = [&](int64_t row, Row& r) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int c = (lane + 64 * j) * 4;
-            if (c < D) {
-                if (dy32) r.a32[j].load(dy32 + row * D + c);
-                if (dy) r.a[j].load(dy + row * D + c);
-                if (dy2) r.b[j].load(dy2 + row * D + c);
-                r.xv[j].load(x + row * D + c);
-            }
-        }
-        r.mu = mean[row];
-        r.rs = rstd[row];
-    };
-    const int64_t rend = (r0 + rows_per_wave < M) ? r0 + rows_per_wave : M;
-    Row cur, nxt;
-    if (r0 < rend) fetch(r0, cur);
-    for (int64_t row = r0; row < rend; ++row) {
-        if (row + 1 < rend) fetch(row + 1, nxt);
-        const float mu = cur.mu, rs = cur.rs;
-        float g[NP][4], xh[NP][4];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int c = (lane + 64 * j) * 4;
-            if (c < D) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d = (dy32 ? cur.a32[j].get(e) : 0.f) + (dy ? cur.a[j].get(e) : 0.f) + (dy2 ? cur.b[j].get(e) : 0.f);
-                    if (p > 0.f) d *= dropout_scale(seed, (uint64_t)row, (uint32_t)(c + e), p, inv_keep);
-                    const float h = (cur.xv[j].get(e) - mu) * rs;
-                    xh[j][e] = h;
-                    dg[j][e] += d * h;
-                    db[j][e] += d;
-                    const float gg = d * gm[j][e];
-                    g[j][e] = gg;
-                    s1 += gg;
-                    s2 += gg * h;
-                }
-            }
-        }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int c = (lane + 64 * j) * 4;
-            if (c < D) {
-                Vec4<T> o;
-                Vec4<float> o32;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float r = rs * (g[j][e] - s1 - xh[j][e] * s2);
-                    dxs[j][e] += r;
-                    o.set(e, r);
-                    o32.set(e, r);
-                }
-                if (dx32) o32.store(dx32 + row * D + c);
-                if (dx) o.store(dx + row * D + c);
-            }
-        }
-        cur = nxt;
-    }
-    // one set of atomics per WORKGROUP: the 4 waves' partial sums are combined in LDS first (every wave
-    // of every workgroup adding to the same D addresses is the contended-atomic worst case)
-    __shared__ float red[3][NP * 256];
-    const int wave = threadIdx.x >> 6;
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                const int c = (lane + 64 * j) * 4;
-                if (c < D) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (w == 0) { red[0][c + e] = dg[j][e]; red[1][c + e] = db[j][e]; red[2][c + e] = dxs[j][e]; }
-                        else { red[0][c + e] += dg[j][e]; red[1][c + e] += db[j][e]; red[2][c + e] += dxs[j][e]; }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (det_part) {   // deterministic mode: this workgroup's row of the scratch, folded in index order by det_fold
-        float* row = det_part + (int64_t)blockIdx.x * 3 * D;
-        for (int c = threadIdx.x; c < D; c += 256) { row[c] = red[0][c]; row[D + c] = red[1][c]; row[2 * D + c] = red[2][c]; }
-        return;
-    }
-    for (int c = threadIdx.x; c < D; c += 256) {
-        atomicAdd(dgamma + c, red[0][c]);
-        atomicAdd(dbeta + c, red[1][c]);
-        if (dxsum) atomicAdd(dxsum + c, red[2][c]);
-    }
-}
-
-// ---- wide rows: 1024 < D <= 4096 (pre-extracted 2048-d features, ResNet-50 tokens, concat_to_seq on ViT features) -----------------
-// One wave per row would hold 64 values per lane per array at D = 4096; the backward's three per-column accumulators alone would be
-// 192 registers.  Here the four waves of a workgroup share a row: thread t owns the 4-column vectors (t + 256 j) * 4, j < NV
-// (NV = passes of 1024 columns: 2, 3 or 4 — at most 16 columns per lane per array), the two row sums go wave_sum -> four LDS words ->
-// one barrier.  Every column belongs to exactly ONE thread of the workgroup, so the backward's column reductions need no fold across
-// waves: the workgroup's sums pass through LDS only to reach the sinks (or the deterministic mode's scratch row) in lane order.
-constexpr int LNW_MAX_D = 4096;
-
+// wide rows (WPR = 4 in the backward's terms): thread t owns the 4-column vectors (t + 256 j) * 4, j < NV, the two row sums go wave_sum ->
+// four LDS words -> one barrier
 template <typename T, typename TX, int NV>
 __global__ __launch_bounds__(256) void lnw_fwd_kernel(const TX* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float* __restrict__ y32,
@@ -285,120 +168,45 @@ __global__ __launch_bounds__(256) void lnw_fwd_kernel(const TX* __restrict__ x, 
     }
 }
 
-// A workgroup walks `rows_per_wg` consecutive rows; the NEXT row's operands are fetched before the current row's sums are exchanged
-// (one barrier per row: the LDS words alternate by row parity, so a wave that runs ahead writes the other set).
-template <typename T, typename TX, int NV>
-__global__ __launch_bounds__(256) void lnw_bwd_kernel(const float* __restrict__ dy32, const T* __restrict__ dy,
-                                                      const T* __restrict__ dy2, const TX* __restrict__ x,
-                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                      const float* __restrict__ rstd, float* __restrict__ dx32,
-                                                      T* __restrict__ dx, float* __restrict__ dgamma,
-                                                      float* __restrict__ dbeta, float* __restrict__ dxsum, int64_t M, int D,
-                                                      float p, float inv_keep, uint64_t seed0, const int64_t* __restrict__ soff, int rows_per_wg,
-                                                      float* __restrict__ det_part) {
-    __shared__ float red[2][2][4];
+// (NP, WPR) of the launch ladder -> the forward kernel
+template <typename T, typename TX, int NP, int WPR>
+constexpr auto ln_fwd_pick() {
+    if constexpr (WPR == 1) return &ln_fwd_kernel<T, TX, NP>;
+    else return &lnw_fwd_kernel<T, TX, NP>;
+}
+
+// An owner (wave at WPR = 1, workgroup at WPR = 4) walks `rows_per_owner` consecutive rows, the next row's operands in flight while
+// the current one is reduced.  WPR = 4: one barrier per row — the LDS words of the row sums alternate by row parity, so a wave that
+// runs ahead writes the other set — and r0, rend are uniform over the workgroup: every thread meets every barrier.
+template <typename T, typename TX, int NP, int WPR>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy32, const T* __restrict__ dy,
+                                                     const T* __restrict__ dy2, const TX* __restrict__ x,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                     const float* __restrict__ rstd, float* __restrict__ dx32,
+                                                     T* __restrict__ dx, float* __restrict__ dgamma,
+                                                     float* __restrict__ dbeta, float* __restrict__ dxsum, int64_t M, int D,
+                                                     float p, float inv_keep, uint64_t seed0, const int64_t* __restrict__ soff, int rows_per_owner,
+                                                     float* __restrict__ det_part) {
+    using Own = LnOwner<WPR>;
+    using Rows = LnBwdRows<T, TX, NP, WPR>;
     const uint64_t seed = seed0 + (soff ? ((uint64_t)soff[0] << 8) : 0ull);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
-    const int64_t rend = (r0 + rows_per_wg < M) ? r0 + rows_per_wg : M;
-    float dg[NV][4], db[NV][4], dxs[NV][4], gm[NV][4];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = (tid + 256 * j) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { dg[j][e] = 0.f; db[j][e] = 0.f; dxs[j][e] = 0.f; gm[j][e] = c < D ? gamma[c + e] : 0.f; }
-    }
-    struct Row { Vec4<float> a32[NV]; Vec4<T> a[NV], b[NV]; Vec4<TX> xv[NV]; float mu, rs; };
-    auto fetch = [&](int64_t row, Row& r) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c = (tid + 256 * j) * 4;
-            if (c < D) {
-                if (dy32) r.a32[j].load(dy32 + row * D + c);
-                if (dy) r.a[j].load(dy + row * D + c);
-                if (dy2) r.b[j].load(dy2 + row * D + c);
-                r.xv[j].load(x + row * D + c);
-            }
-        }
-        r.mu = mean[row];
-        r.rs = rstd[row];
-    };
-    Row cur, nxt;
-    if (r0 < rend) fetch(r0, cur);
+    const int64_t r0 = Own::index() * rows_per_owner;
+    const int64_t rend = (r0 + rows_per_owner < M) ? r0 + rows_per_owner : M;
+    Rows ln{dy32, dy, dy2, x, mean, rstd, D};
+    ln.init(gamma);
+    float (*slot)[4] = Own::template slots<4>();
+    typename Rows::Row cur, nxt;
+    if (r0 < rend) ln.fetch(r0, cur);
     int par = 0;
-    for (int64_t row = r0; row < rend; ++row) {   // (r0, rend are uniform over the workgroup: every thread meets every barrier)
-        if (row + 1 < rend) fetch(row + 1, nxt);
-        const float mu = cur.mu, rs = cur.rs;
-        float g[NV][4], xh[NV][4];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c = (tid + 256 * j) * 4;
-            if (c < D) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d = (dy32 ? cur.a32[j].get(e) : 0.f) + (dy ? cur.a[j].get(e) : 0.f) + (dy2 ? cur.b[j].get(e) : 0.f);
-                    if (p > 0.f) d *= dropout_scale(seed, (uint64_t)row, (uint32_t)(c + e), p, inv_keep);
-                    const float h = (cur.xv[j].get(e) - mu) * rs;
-                    xh[j][e] = h;
-                    dg[j][e] += d * h;
-                    db[j][e] += d;
-                    const float gg = d * gm[j][e];
-                    g[j][e] = gg;
-                    s1 += gg;
-                    s2 += gg * h;
-                }
-            }
-        }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        if (lane == 0) { red[par][0][wave] = s1; red[par][1][wave] = s2; }
-        __syncthreads();
-        s1 = ((red[par][0][0] + red[par][0][1]) + (red[par][0][2] + red[par][0][3])) / (float)D;
-        s2 = ((red[par][1][0] + red[par][1][1]) + (red[par][1][2] + red[par][1][3])) / (float)D;
+    for (int64_t row = r0; row < rend; ++row) {
+        if (row + 1 < rend) ln.fetch(row + 1, nxt);
+        if constexpr (WPR == 4) ln.row(cur, row, dx32, dx, p, inv_keep, seed, slot + 2 * par);
+        else ln.row(cur, row, dx32, dx, p, inv_keep, seed, nullptr);
         par ^= 1;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c = (tid + 256 * j) * 4;
-            if (c < D) {
-                Vec4<T> o;
-                Vec4<float> o32;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float r = rs * (g[j][e] - s1 - xh[j][e] * s2);
-                    dxs[j][e] += r;
-                    o.set(e, r);
-                    o32.set(e, r);
-                }
-                if (dx32) o32.store(dx32 + row * D + c);
-                if (dx) o.store(dx + row * D + c);
-            }
-        }
         cur = nxt;
     }
-    // every column has ONE owner in the workgroup, so there is nothing to fold; the sums still go through LDS so that consecutive lanes
-    // add to consecutive addresses (a lane owns 4 neighbouring columns: straight from registers a wave's atomic instruction would spread
-    // over 8 cache lines, and each line would be visited by 4 instructions)
-    __shared__ float acc[3][NV * 1024];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = (tid + 256 * j) * 4;
-        if (c < D) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[0][c + e] = dg[j][e]; acc[1][c + e] = db[j][e]; acc[2][c + e] = dxs[j][e]; }
-        }
-    }
-    __syncthreads();
-    if (det_part) {   // deterministic mode: this workgroup's row of the scratch, folded in index order by det_fold
-        float* part = det_part + (int64_t)blockIdx.x * 3 * D;
-        for (int c = tid; c < D; c += 256) { part[c] = acc[0][c]; part[D + c] = acc[1][c]; part[2 * D + c] = acc[2][c]; }
-        return;
-    }
-    for (int c = tid; c < D; c += 256) {
-        atomicAdd(dgamma + c, acc[0][c]);
-        atomicAdd(dbeta + c, acc[1][c]);
-        if (dxsum) atomicAdd(dxsum + c, acc[2][c]);
-    }
+    float* const sinks[3] = {dgamma, dbeta, dxsum};
+    ln_fold_columns<WPR>(ln.acc, sinks, det_part ? det_part + (int64_t)blockIdx.x * 3 * D : nullptr, D);
 }
 
 // position_encoding.py:51-71 — one workgroup per batch row: inclusive scan of the mask over L,
@@ -496,6 +304,26 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const float* t, const 
 }
 }  // namespace
 
+// The one ladder of the two LayerNorm launchers below (undefined after them; it reads their dtype, x_f32 and D): dtype x x_f32 ->
+// (T, TX), width -> (NP, WPR).  LAUNCH(T, TX, NP, WPR) is the caller's.
+#define SVOL_LN_WIDTH(LAUNCH, TT, TXX)                         \
+    do {                                                       \
+        if (D <= 256) LAUNCH(TT, TXX, 1, 1);                   \
+        else if (D <= 512) LAUNCH(TT, TXX, 2, 1);              \
+        else if (D <= LN_MAX_PASSES * 256) LAUNCH(TT, TXX, 4, 1); \
+        else if (D <= 2048) LAUNCH(TT, TXX, 2, 4);             \
+        else if (D <= 3072) LAUNCH(TT, TXX, 3, 4);             \
+        else LAUNCH(TT, TXX, 4, 4);                            \
+    } while (0)
+#define SVOL_LN_DISPATCH(LAUNCH)                                                   \
+    do {                                                                           \
+        if (dtype == SVOL_BF16 && x_f32) SVOL_LN_WIDTH(LAUNCH, bf16_t, float);     \
+        else if (dtype == SVOL_BF16) SVOL_LN_WIDTH(LAUNCH, bf16_t, bf16_t);        \
+        else if (dtype == SVOL_F16 && x_f32) SVOL_LN_WIDTH(LAUNCH, f16_t, float);  \
+        else if (dtype == SVOL_F16) SVOL_LN_WIDTH(LAUNCH, f16_t, f16_t);           \
+        else SVOL_LN_WIDTH(LAUNCH, float, float);                                  \
+    } while (0)
+
 extern "C" {
 
 int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float* beta, float* y32, void* y,
@@ -514,28 +342,10 @@ int svol_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float
     if (wide && M > 0x7fffffffll) return SVOL_E_UNSUPPORTED;   // (one workgroup per row)
     const unsigned grid = wide ? (unsigned)M : (unsigned)((M + 3) / 4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define SVOL_LNF(TT, TXX, NPP)                                                                                              \
-    hipLaunchKernelGGL((ln_fwd_kernel<TT, TXX, NPP>), dim3(grid), dim3(256), 0, s, (const TXX*)x, gamma, beta, y32, (TT*)y,      \
+#define SVOL_LNF(TT, TXX, NPP, WPRR)                                                                                        \
+    hipLaunchKernelGGL((ln_fwd_pick<TT, TXX, NPP, WPRR>()), dim3(grid), dim3(256), 0, s, (const TXX*)x, gamma, beta, y32, (TT*)y, \
                        (TT*)ypos, (const TT*)pos, pos_rows, mean, rstd, M, (int)D, dropout_p, inv_keep, seed, seed_offset_dev)
-#define SVOL_LNWF(TT, TXX, NVV)                                                                                             \
-    hipLaunchKernelGGL((lnw_fwd_kernel<TT, TXX, NVV>), dim3(grid), dim3(256), 0, s, (const TXX*)x, gamma, beta, y32, (TT*)y,     \
-                       (TT*)ypos, (const TT*)pos, pos_rows, mean, rstd, M, (int)D, dropout_p, inv_keep, seed, seed_offset_dev)
-#define SVOL_LNF_NP(TT, TXX)                      \
-    do {                                          \
-        if (D <= 256) SVOL_LNF(TT, TXX, 1);       \
-        else if (D <= 512) SVOL_LNF(TT, TXX, 2);  \
-        else if (!wide) SVOL_LNF(TT, TXX, 4);     \
-        else if (D <= 2048) SVOL_LNWF(TT, TXX, 2); \
-        else if (D <= 3072) SVOL_LNWF(TT, TXX, 3); \
-        else SVOL_LNWF(TT, TXX, 4);               \
-    } while (0)
-    if (dtype == SVOL_BF16 && x_f32) SVOL_LNF_NP(bf16_t, float);
-    else if (dtype == SVOL_BF16) SVOL_LNF_NP(bf16_t, bf16_t);
-    else if (dtype == SVOL_F16 && x_f32) SVOL_LNF_NP(f16_t, float);
-    else if (dtype == SVOL_F16) SVOL_LNF_NP(f16_t, f16_t);
-    else SVOL_LNF_NP(float, float);
-#undef SVOL_LNF_NP
-#undef SVOL_LNWF
+    SVOL_LN_DISPATCH(SVOL_LNF);
 #undef SVOL_LNF
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
@@ -553,7 +363,7 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     if (M == 0) return SVOL_OK;
     const float inv_keep = 1.f / (1.f - dropout_p);
     // ~2048 waves (512 workgroups); each wave walks `rpw` consecutive rows; one set of atomics per workgroup
-    // (wide rows: as many workgroups as are resident at once — three to four per CU at NV = 2, two at NV = 3 / 4 — each walking `rpw`
+    // (wide rows: as many workgroups as are resident at once — three to four per CU at NP = 2, two at NP = 3 / 4 — each walking `rpw`
     // consecutive rows with all four waves on one row.  Fewer leave HBM latency uncovered, more only add sink atomics:
     // profiles/layernorm_wide.md)
     const bool wide = D > LN_MAX_PASSES * 256;
@@ -569,30 +379,11 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     // NP = passes of 256 columns per row: the accumulator / operand arrays are sized by it (NP = 1 at d = 256: 76 VGPRs
     // instead of the 166 of the 4-pass instantiation; 46 us instead of 50 at [50176, 256] = 5.0 TB/s.  More waves or a next-row
     // prefetch do not help further: the end-of-workgroup atomics, then HBM, bound it)
-#define SVOL_LNB(TT, TXX, NPP)                                                                                                      \
-    hipLaunchKernelGGL((ln_bwd_kernel<TT, TXX, NPP>), dim3(grid), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, (const TXX*)x, \
-                       gamma, mean, rstd, dx32, (TT*)dx, dgamma, dbeta, dx_colsum, M, (int)D, dropout_p, inv_keep, seed,              \
+#define SVOL_LNB(TT, TXX, NPP, WPRR)                                                                                                 \
+    hipLaunchKernelGGL((ln_bwd_kernel<TT, TXX, NPP, WPRR>), dim3(grid), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, (const TXX*)x, \
+                       gamma, mean, rstd, dx32, (TT*)dx, dgamma, dbeta, dx_colsum, M, (int)D, dropout_p, inv_keep, seed,                  \
                        seed_offset_dev, (int)rpw, det.p)
-#define SVOL_LNWB(TT, TXX, NVV)                                                                                                      \
-    hipLaunchKernelGGL((lnw_bwd_kernel<TT, TXX, NVV>), dim3(grid), dim3(256), 0, s, dy32, (const TT*)dy, (const TT*)dy2, (const TXX*)x, \
-                       gamma, mean, rstd, dx32, (TT*)dx, dgamma, dbeta, dx_colsum, M, (int)D, dropout_p, inv_keep, seed,               \
-                       seed_offset_dev, (int)rpw, det.p)
-#define SVOL_LNB_NP(TT, TXX)                      \
-    do {                                          \
-        if (D <= 256) SVOL_LNB(TT, TXX, 1);       \
-        else if (D <= 512) SVOL_LNB(TT, TXX, 2);  \
-        else if (!wide) SVOL_LNB(TT, TXX, 4);     \
-        else if (D <= 2048) SVOL_LNWB(TT, TXX, 2); \
-        else if (D <= 3072) SVOL_LNWB(TT, TXX, 3); \
-        else SVOL_LNWB(TT, TXX, 4);               \
-    } while (0)
-    if (dtype == SVOL_BF16 && x_f32) SVOL_LNB_NP(bf16_t, float);
-    else if (dtype == SVOL_BF16) SVOL_LNB_NP(bf16_t, bf16_t);
-    else if (dtype == SVOL_F16 && x_f32) SVOL_LNB_NP(f16_t, float);
-    else if (dtype == SVOL_F16) SVOL_LNB_NP(f16_t, f16_t);
-    else SVOL_LNB_NP(float, float);
-#undef SVOL_LNB_NP
-#undef SVOL_LNWB
+    SVOL_LN_DISPATCH(SVOL_LNB);
 #undef SVOL_LNB
     if (det_mode) {
         det_fold(det.p, (int)grid, 3 * D, dgamma, D, s);
@@ -602,6 +393,9 @@ int svol_layernorm_bwd(const float* dy32, const void* dy, const void* dy2, const
     SVOL_CHECK_LAUNCH();
     return SVOL_OK;
 }
+
+#undef SVOL_LN_DISPATCH
+#undef SVOL_LN_WIDTH
 
 int svol_dropout_sd(const void* x, void* y, int64_t n, int64_t row_len, float p, uint64_t seed, const int64_t* seed_step_dev, int dtype,
                     void* stream) {

@@ -1,5 +1,5 @@
-"""svol_layernorm_fwd / _bwd on rows of 1024 < D <= 4096 columns (csrc/norm.hip: lnw_fwd_kernel / lnw_bwd_kernel, one workgroup of four
-waves per row) against fp64.
+"""svol_layernorm_fwd / _bwd on rows of 1024 < D <= 4096 columns (csrc/norm.hip: lnw_fwd_kernel and the WPR = 4 instances of ln_bwd_kernel, one
+workgroup of four waves per row) against fp64.
 
 The method is test_gpu_attn_dropout.py::test_layernorm_dropout_against_the_twin's: beta = 4 keeps a kept output away from 0, so the
 kept set is read off y and compared with the numpy twin of the keep function (tests/dropout_twin.py); y / dx / dgamma / dbeta are
