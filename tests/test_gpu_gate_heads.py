@@ -35,7 +35,8 @@ SHAPES = [(2, 37, 36, 9),        # one head past a group
           (1, 77, 512, 16),      # two 16-byte column groups per lane
           (2, 24, 528, 24),      # past 512 columns, three groups of heads
           (1, 21, 1024, 32),     # four column groups, four groups of heads
-          (3, 5, 64, 16)]        # a wave's row range crosses batch elements: the cc hand-over in gate_bwd_ln_kernel
+          (3, 5, 64, 16)]        # short videos, M = 15: one row per wave, so NO wave crosses a batch element here (the cc hand-over of
+                                 # gate_bwd_ln_kernel is reached by tests/test_gpu_row_kernels.py at 64 waves)
 _ids = lambda shapes: ['B%dL%dD%dH%d' % s for s in shapes]   # noqa: E731
 
 
